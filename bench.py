@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Benchmark of the CODLAD sampling hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4|cfg4share|cfg5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4|cfg4share|cfg5] [--full]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Default workload (BASELINE.json configs[1], "cfg2"): synthetic PED-shaped test set - 4 proteins with
@@ -15,10 +16,17 @@ job whose units (protein, frame, ensemble member) are dealt to the ranks longest
 are broadcast from rank 0 over RCCL before timing and every rank's coordinates are all-gathered inside the
 timed region.
 
-Prints ONE JSON line (rank 0).  `roofline` times the dominant kernel (the per-edge message MLP) with HIP
-events on its own stream and prices it against the matrix pipe it runs on; `cpu_baseline` times the CPU
-oracle (oracle/, a port of the reference's PyTorch-CPU path) on a bounded sample of the same workload;
-`f32_mfma` is the same job with every contraction on v_mfma_f32_32x32x2_f32 (IEEE fp32 products).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline
+(`value`, `ms_per_step`, ...).  `--full` adds the measurements that take runs of their own: `roofline` times
+the dominant kernel (the per-edge message MLP) with HIP events on its own stream and prices it against the
+matrix pipe it runs on; `cpu_baseline` times the CPU oracle (oracle/, a port of the reference's PyTorch-CPU
+path) on a bounded sample of the same workload; `f32_mfma` is the same job with every contraction on
+v_mfma_f32_32x32x2_f32 (IEEE fp32 products); `cfg5` (cfg2 only), `prepass_ms` and `recon_from_atoms` (cfg5).
+
+`--dump-outputs DIR` writes what the last timed step returned (rank 0): `xyz_<g>.npy`, the all-atom coordinates
+[structures, atoms, 3] of protein group g in job order, and `vq_indices.npy` (float64), the code of every residue.
+With several ranks `xyz_rank<r>.npy` holds rank r's all-gathered coordinates, flat.  Inputs are seeded, so two
+builds run with the same arguments can be compared file by file.
 """
 import argparse
 import ctypes as C
@@ -406,6 +414,34 @@ def cfg5_section(device, steps=200, warmup=10):
             "roofline": decode_roofline(wl5), "recon_from_atoms": recon_section(wl5)}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, max_bytes=DUMP_MAX_BYTES, seed=0):
+    """arrays: {name: tensor / ndarray} -> out_dir/<name>.npy as float32 (float64 tensors and integer codes as float64).
+    Above max_bytes in all, every array keeps the same seeded sample of its rows (first axis), sorted, and
+    out_dir/<name>_rows.npy records which rows those are."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        host[name] = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+    total = sum(a.nbytes for a in host.values())
+    # the row lists of a sample count too (8 bytes per row at most)
+    keep = 1.0 if total <= max_bytes else (max_bytes - sum(8 * len(a) for a in host.values() if a.ndim)) / total
+    written = {}
+    for name, a in host.items():
+        if keep < 1.0 and a.ndim and a.shape[0] > 1:
+            k = max(1, int(a.shape[0] * keep))
+            rows = np.sort(np.random.default_rng(seed).choice(a.shape[0], k, replace=False))
+            a = a[rows]
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+            written[name + "_rows"] = rows.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = a.nbytes
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -413,12 +449,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=None, help="default 1 (cfg5: 10)")
     ap.add_argument("--config", choices=["cfg2", "cfg3", "cfg4", "cfg4share", "cfg5"], default="cfg2",
                     help="BASELINE.json configuration (default cfg2, the one the metric is quoted on)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-f32-leg", action="store_true", help="skip the extra fp32-MFMA timing of the same job")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what takes runs of its own: roofline (dominant-kernel launch times), "
+                         "prepass share, fp32-MFMA leg, cfg5 section (cfg2), recon from atoms (cfg5) and the CPU baseline; "
+                         "the --no-* options below leave parts of it out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0) as DIR/<name>.npy, float32 / float64, 64 MB at most")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full run: skip the CPU oracle timing")
+    ap.add_argument("--no-f32-leg", action="store_true", help="--full run: skip the extra fp32-MFMA timing of the same job")
     ap.add_argument("--streams", type=int, default=None,
                     help="1: the whole job on one HIP stream (kernel traces / counter passes, where a kernel's duration must be "
                          "its own); default: as the product runs it (a large job = two half-jobs on two streams)")
-    ap.add_argument("--no-cfg5", action="store_true", help="cfg2 run: skip the appended decoder-only measurement (BASELINE configuration 5)")
+    ap.add_argument("--no-cfg5", action="store_true", help="--full cfg2 run: skip the appended decoder-only measurement (BASELINE configuration 5)")
     ap.add_argument("--precision", choices=["f16x3", "f16x4", "f32"], default="f16x3",
                     help="contraction mode: f16x3 (default) / f16x4 = fp32 operands split into fp16 hi+lo halves on "
                          "the f16 matrix pipe, 3 or 4 cross products per fp32 product, fp32 accumulation "
@@ -468,10 +510,13 @@ def main():
 
     def step():
         xyz, idx = wl.run(streams=args.streams)
+        gathered = None
         if world > 1:
             from codlad_amd.parallel import gather_coordinates
-            gather_coordinates(xyz, world)
-        return xyz
+            gathered = gather_coordinates(xyz, world)
+        return xyz, idx, gathered
+
+    last = []
 
     def timed_steps(n_warm, n_steps):
         for _ in range(n_warm):
@@ -479,25 +524,34 @@ def main():
         barrier()
         t0 = time.perf_counter()
         for _ in range(n_steps):
-            step()
+            out = step()
         barrier()
         dt = time.perf_counter() - t0
         if world > 1:
             tmax = torch.tensor([dt], dtype=torch.float64, device=device if backend == "nccl" else "cpu")
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             dt = float(tmax)
+        last[:] = [out] if n_steps else []
         return dt
 
     dt = timed_steps(args.warmup, args.steps)
+    if args.dump_outputs and rank == 0 and last:
+        # now: the --full passes below run the job again into the same output buffers
+        xyz, idx, gathered = last[0]
+        arrays = {f"xyz_{g:02d}": x for g, x in enumerate(xyz)}
+        arrays["vq_indices"] = idx
+        if gathered is not None:
+            arrays.update({f"xyz_rank{r}": x for r, x in enumerate(gathered)})
+        dump_outputs(args.dump_outputs, arrays)
     strong = wl.cfg["scaling"] == "strong"
     structs_per_step = wl.n_units_job if strong else wl.n_structures * world
 
     extra = {}
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         extra["prepass_ms"] = wl.timed(wl.prepass, 3) * 1e3     # share of ms_per_step spent before the first DDPM step
         if wl.decode_only:
             extra["recon_from_atoms"] = recon_section(wl)
-    if not wl.decode_only:
+    if args.full and not wl.decode_only:
         kern = wl.time_dominant_kernel()          # back to back, alone on the chip
         insitu = probe_edge_kernels(wl)           # inside the job
         t_msg = insitu["message"]["ms"] / 1e3 if "message" in insitu else kern["message"]
@@ -517,7 +571,9 @@ def main():
     if rank == 0:
         value = structs_per_step * args.steps / dt
         terms = {"f16x3": 3, "f16x4": 4, "f32": 0}[args.precision]
-        if wl.decode_only:
+        if not args.full:
+            roofline = None
+        elif wl.decode_only:
             roofline = decode_roofline(wl)
         else:
             # dominant kernel: layers 1-2 of the encoder message MLP.  Algorithmic 2*(384*128 + 128*128) FLOP per
@@ -575,15 +631,17 @@ def main():
                        "parallelism": (f"units sharded x{world} (LPT), no data-path collective" if strong
                                        else f"replicas x{world}"),
                        "streams": ("two half-jobs on two HIP streams per GPU (codlad_amd.engine.Denoiser.sample, jobs of "
-                                   ">= 8 192 nodes); the roofline's per-launch times come from a separate single-stream pass"
+                                   ">= 8 192 nodes)" + ("; the roofline's per-launch times come from a separate single-stream pass"
+                                                        if args.full else "")
                                    if args.streams is None and not wl.decode_only and wl.job.n_nodes >= wl.den.SPLIT_MIN_NODES
                                    else "one HIP stream")},
-            "roofline": roofline,
         }
+        if roofline is not None:
+            result["roofline"] = roofline
         result.update(extra)
-        if world == 1 and args.config == "cfg2" and not args.no_cfg5:
+        if args.full and world == 1 and args.config == "cfg2" and not args.no_cfg5:
             result["cfg5"] = cfg5_section(device)       # BASELINE configuration 5 (the other 1-GPU configuration) in the same line
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(args.config)
         print(json.dumps(result), flush=True)
     if world > 1:

@@ -75,7 +75,7 @@ def _bench_two_ranks(extra):
 def test_bench_sharded_config_two_ranks():
     """bench.py --config cfg3 --gpus 2 as the driver launches it (torch.distributed.run), both ranks on cuda:0 over
     gloo: one JSON line, strong scaling, all 64 structures accounted for."""
-    r = _bench_two_ranks(["--config", "cfg3"])
+    r = _bench_two_ranks(["--config", "cfg3", "--full"])
     assert r["n_gpus"] == 2 and r["scaling"] == "strong" and r["config"]["structures_per_step"] == 64
     assert r["value"] > 0 and 0 < r["roofline"]["frac"] <= 1.0
 
@@ -84,7 +84,7 @@ def test_bench_sharded_config_two_ranks():
 def test_bench_default_config_two_ranks():
     """The driver's N > 1 command on the default configuration (cfg2, weak scaling: one 400-structure replica per rank,
     weights broadcast, coordinates all-gathered inside the timed region)."""
-    r = _bench_two_ranks([])
+    r = _bench_two_ranks(["--full"])
     assert r["n_gpus"] == 2 and r["scaling"] == "weak" and r["config"]["structures_per_step"] == 800
     assert r["metric"].startswith("sampled all-atom structures/sec") and r["value"] > 0
     assert "cpu_baseline" not in r and "f32_mfma" not in r          # rank-0, N = 1 only
@@ -170,3 +170,31 @@ def test_rccl_backend_runs_the_collectives_on_device_tensors():
     assert res.returncode == 0, res.stdout[-1500:] + res.stderr[-3000:]
     assert "nccl single-rank collectives ok: backend nccl" in res.stdout
     assert "ranks=1 backend=nccl" in res.stdout
+
+
+@pytest.mark.timeout(300)
+def test_bench_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """The plain bench command (no --full) times exactly --steps steps, prints the headline without the extra
+    measurements, and --dump-outputs writes the coordinates and VQ codes of the last timed step."""
+    out = tmp_path / "out"
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0",
+                          "--dump-outputs", str(out)], env=_env(), cwd=ROOT, capture_output=True, text=True, timeout=280)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
+    lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    r = json.loads(lines[0])
+    assert r["steps"] == 1 and r["warmup"] == 0 and r["ms_per_step"] > 0 and r["value"] > 0
+    assert r["unit"] == "structures/s" and r["higher_is_better"] is True and r["dtype"].startswith("f32 as f16x3")
+    for k in ("roofline", "cfg5", "cpu_baseline", "f32_mfma", "prepass_ms"):
+        assert k not in r, k
+    files = sorted(os.listdir(out))
+    assert files == ["vq_indices.npy"] + [f"xyz_{g:02d}.npy" for g in range(4)]          # cfg2: 4 proteins
+    codes = np.load(out / "vq_indices.npy")
+    assert codes.dtype == np.float64 and codes.shape == (r["config"]["nodes_rank0"],)
+    assert codes.min() >= 0 and codes.max() < 4096 and np.array_equal(codes, np.round(codes))
+    n = 0
+    for g in range(4):
+        xyz = np.load(out / f"xyz_{g:02d}.npy")
+        assert xyz.dtype == np.float32 and xyz.ndim == 3 and xyz.shape[2] == 3 and np.isfinite(xyz).all()
+        n += xyz.shape[0]
+    assert n == r["config"]["structures_per_step"] == 400

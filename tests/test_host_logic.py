@@ -411,3 +411,26 @@ def test_package_asks_for_device_side_kernel_arguments_unless_told_otherwise():
             env["HIP_FORCE_DEV_KERNARG"] = given
         out = subprocess.run([sys.executable, "-c", code], cwd=root, env=env, capture_output=True, text=True, check=True)
         assert out.stdout.strip() == want
+
+
+def test_bench_dump_writes_float_arrays_and_a_seeded_sample_above_the_cap(tmp_path):
+    """bench.py --dump-outputs: coordinates stay float32, integer codes become float64 (exact), and above the byte cap
+    every array keeps the same seeded rows, listed beside it, within the cap; the same call gives the same files."""
+    import bench
+    xyz = torch.arange(40 * 6 * 3, dtype=torch.float32).reshape(40, 6, 3)
+    idx = torch.arange(100, dtype=torch.int64) * 37 % 4096
+    written = bench.dump_outputs(str(tmp_path / "all"), {"xyz_00": xyz, "vq_indices": idx})
+    got = np.load(tmp_path / "all" / "xyz_00.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, xyz.numpy())
+    codes = np.load(tmp_path / "all" / "vq_indices.npy")
+    assert codes.dtype == np.float64 and np.array_equal(codes, idx.numpy())
+    assert sorted(written) == ["vq_indices", "xyz_00"]
+    cap = 1000
+    for run in ("a", "b"):
+        written = bench.dump_outputs(str(tmp_path / run), {"xyz_00": xyz, "vq_indices": idx}, max_bytes=cap)
+        assert 0 < sum(written.values()) <= cap
+    for name in ("xyz_00", "xyz_00_rows", "vq_indices", "vq_indices_rows"):
+        assert np.array_equal(np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy"))
+    rows = np.load(tmp_path / "a" / "xyz_00_rows.npy").astype(np.int64)
+    assert 0 < len(rows) < 40 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "xyz_00.npy"), xyz.numpy()[rows])

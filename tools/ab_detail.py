@@ -11,7 +11,7 @@ for rep in range(2):
         env = dict(os.environ)
         if lib:
             env["CODLAD_HIP_LIB"] = os.path.abspath(lib)
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
                               "--no-f32-leg", "--no-cfg5"], env=env, capture_output=True, text=True).stdout
         d = json.loads(out.strip().splitlines()[-1])
         r = d["roofline"]

@@ -5,7 +5,7 @@ set -e
 OUT=$GRAFT_REPO_ROOT/gpurun_out/${1:-prof_decode}
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace" --output-format csv -- python3 bench.py --config cfg5 --no-cpu-baseline --steps 4 --warmup 1 > "$OUT/bench.log" 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace" --output-format csv -- python3 bench.py --full --config cfg5 --no-cpu-baseline --steps 4 --warmup 1 > "$OUT/bench.log" 2>&1
 python3 tools/kernel_stats.py "$OUT/trace" 14 > "$OUT/kernel_stats.txt"
 rm -rf "$OUT/trace"
 cat "$OUT/kernel_stats.txt"
