@@ -715,10 +715,13 @@ DEV void tile_modulate(Tile &t, const float *shift, const float *scale, const fl
 // 2 = fixed variance (FIXED_SMALL / FIXED_LARGE: cf[4] is the step's log variance, `v` is not read), 4 = clip_denoised
 // (pred_xstart clamped into [-1, 1]).  mode 0 = epsilon prediction with the learned-range variance, what test.py samples with.
 // *x0_out (optional) receives pred_xstart, the self-conditioning input of the next step.
+// *pin (optional): residue pinning, the denoised_fn `where(mask, x0_known, x)` fused - the raw pred_xstart is replaced
+// by *pin before the clamp (gaussian_diffusion.py:335-340: denoised_fn first, then clip_denoised).
 #define CODLAD_DDPM_START_X 1
 #define CODLAD_DDPM_FIXED_VAR 2
 #define CODLAD_DDPM_CLIP 4
-DEV float ddpm_step(float xt, float out, float v, const float *cf, float noise, float *x0_out = nullptr) {
+DEV float ddpm_step(float xt, float out, float v, const float *cf, float noise, float *x0_out = nullptr,
+                    const float *pin = nullptr) {
 #pragma clang fp contract(off)
     const int mode = (int)cf[7];
     float logvar = cf[4];
@@ -727,9 +730,41 @@ DEV float ddpm_step(float xt, float out, float v, const float *cf, float noise, 
         logvar = frac * cf[5] + (1.0f - frac) * cf[4];
     }
     float x0 = (mode & CODLAD_DDPM_START_X) ? out : cf[0] * xt - cf[1] * out;
+    if (pin) x0 = *pin;
     if (mode & CODLAD_DDPM_CLIP) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
     const float mean = cf[2] * x0 + cf[3] * xt;
     if (x0_out) *x0_out = x0;
+    return mean + (cf[6] * expf(0.5f * logvar)) * noise;
+}
+
+// ddpm_step split in two around a caller's denoised_fn / cond_fn (codlad_ddpm_pred_xstart / codlad_ddpm_posterior_step).
+// Its expressions, written out again (folding ddpm_step onto these pieces reschedules final_kernel's code): a pin applied
+// between the halves rounds exactly as the fused one.  Keep the three in step with ddpm_step.
+// The raw pred_xstart, before denoised_fn and the clamp (gaussian_diffusion.py:343-349).
+DEV float ddpm_raw_x0(float xt, float out, const float *cf) {
+#pragma clang fp contract(off)
+    return ((int)cf[7] & CODLAD_DDPM_START_X) ? out : cf[0] * xt - cf[1] * out;
+}
+
+DEV float ddpm_log_variance(float v, const float *cf) {
+#pragma clang fp contract(off)
+    float logvar = cf[4];
+    if (!((int)cf[7] & CODLAD_DDPM_FIXED_VAR)) {
+        const float frac = (v + 1.0f) / 2.0f;
+        logvar = frac * cf[5] + (1.0f - frac) * cf[4];
+    }
+    return logvar;
+}
+
+// clamp, posterior mean, optional classifier guidance mean += variance * grad (gaussian_diffusion.py:374-384, 436-446),
+// then the noise term
+DEV float ddpm_posterior(float xt, float x0, float logvar, const float *cf, float noise, float *x0_out,
+                         const float *grad, float variance) {
+#pragma clang fp contract(off)
+    if ((int)cf[7] & CODLAD_DDPM_CLIP) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    float mean = cf[2] * x0 + cf[3] * xt;
+    if (x0_out) *x0_out = x0;
+    if (grad) mean = mean + variance * *grad;
     return mean + (cf[6] * expf(0.5f * logvar)) * noise;
 }
 

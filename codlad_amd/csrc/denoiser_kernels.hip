@@ -342,7 +342,12 @@ DEV float half_wave_allsum(float v) {
     return v;
 }
 
-__global__ __launch_bounds__(256) void final_kernel(FinalArgs a) {
+// PIN: residue pinning fused into the update (codlad_sample_loop_pinned): at a node with pin_mask[n] != 0 the step's
+// raw pred_xstart is replaced by pin_x0[n] before the clamp.  A template parameter, so that final_kernel<false> (the
+// logits mode and the plain loop) is instruction for instruction the kernel it was before pinning existed; only its
+// argument block grows by the two unused pointers.
+template <bool PIN>
+__global__ __launch_bounds__(256) void final_kernel(FinalArgs a, const float *pin_x0, const uint8_t *pin_mask) {
     const int l = threadIdx.x & 31;
     const int n = blockIdx.x * 8 + (threadIdx.x >> 5);
     const bool live = n < a.n_nodes;
@@ -391,7 +396,8 @@ __global__ __launch_bounds__(256) void final_kernel(FinalArgs a) {
         const float eps = l == 0 ? o[0] : (l == 1 ? o[1] : o[2]);
         const float vv = l == 0 ? o[3] : (l == 1 ? o[4] : o[5]);      // (zeros for a 3-row head: fixed-variance samplers)
         const size_t i = (size_t)n * 3 + l;
-        a.x[i] = ddpm_step(a.x[i], eps, vv, a.coef, a.noise[i], a.x_start ? a.x_start + i : nullptr);
+        const float *pin = PIN && pin_mask[n] ? pin_x0 + i : nullptr;
+        a.x[i] = ddpm_step(a.x[i], eps, vv, a.coef, a.noise[i], a.x_start ? a.x_start + i : nullptr, pin);
     }
 }
 
@@ -409,6 +415,31 @@ __global__ void ddpm_kernel(const float *x, const float *out, const float *noise
     const bool fixed = ((int)cf.c[7] & CODLAD_DDPM_FIXED_VAR) != 0;
     const float o = fixed ? out[n * 3 + k] : out[n * 6 + k], v = fixed ? 0.f : out[n * 6 + 3 + k];
     x_out[i] = ddpm_step(x[i], o, v, cf.c, noise[i], x_start ? x_start + i : nullptr);
+}
+
+// The DDPM update split in two around a caller's denoised_fn / cond_fn (codlad_ddpm_pred_xstart /
+// codlad_ddpm_posterior_step): the pieces of ddpm_step, so that a pin applied between them rounds as the fused one.
+__global__ void ddpm_pred_xstart_kernel(const float *x, const float *out, DdpmCoef cf, int n_nodes, float *x0_out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_nodes * 3) return;
+    const int n = i / 3, k = i - 3 * n;
+    const bool fixed = ((int)cf.c[7] & CODLAD_DDPM_FIXED_VAR) != 0;
+    x0_out[i] = ddpm_raw_x0(x[i], fixed ? out[n * 3 + k] : out[n * 6 + k], cf.c);
+}
+
+__global__ void ddpm_posterior_kernel(const float *x, const float *x0, const float *out, const float *noise,
+                                      const float *grad, DdpmCoef cf, float fixed_variance, int n_nodes, float *x_out,
+                                      float *x_start) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_nodes * 3) return;
+    const int n = i / 3, k = i - 3 * n;
+    const bool fixed = ((int)cf.c[7] & CODLAD_DDPM_FIXED_VAR) != 0;
+    const float logvar = ddpm_log_variance(fixed ? 0.f : out[n * 6 + 3 + k], cf.c);
+    // the variance that scales the gradient: exp(model_log_variance) for the learned range, the table value for
+    // fixed variance (gaussian_diffusion.py:318, 320-334)
+    const float variance = fixed ? fixed_variance : expf(logvar);
+    x_out[i] = ddpm_posterior(x[i], x0[i], logvar, cf.c, noise[i], x_start ? x_start + i : nullptr,
+                              grad ? grad + i : nullptr, variance);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -822,7 +853,7 @@ extern "C" int codlad_denoiser_forward(const codlad_denoiser_weights *w, const i
     FinalArgs fa = {};
     fa.hV = ws->hV; fa.mods = mods_t + mods_offset(6); fa.out_w = w->out_w; fa.out_b = w->out_b;
     fa.n_nodes = n_nodes; fa.logits = out; fa.status = ws->status; fa.n_out = w->out_dim;
-    hipLaunchKernelGGL(final_kernel, dim3((n_nodes + 7) / 8), dim3(256), 0, st, fa);
+    hipLaunchKernelGGL(final_kernel<false>, dim3((n_nodes + 7) / 8), dim3(256), 0, st, fa, nullptr, nullptr);
     return codlad_check_launch("codlad_denoiser_forward");
 }
 
@@ -838,17 +869,35 @@ extern "C" int codlad_ddpm_update(const float *x, const float *model_out, const 
     return codlad_check_launch("codlad_ddpm_update");
 }
 
-extern "C" int codlad_sample_loop(const codlad_denoiser_weights *w, const int32_t *node_info,
-                                  int n_nodes, const int32_t *E_idx, const float *h_E0,
-                                  const float *E1, int n_snodes, float *x, float *x_start,
-                                  const float *noise, const float *mods, const float *coef, int T,
-                                  const codlad_workspace *ws, void *stream) {
-    CODLAD_REQUIRE(w && node_info && E_idx && h_E0 && x && noise && mods && coef, "null pointer");
-    CODLAD_REQUIRE(check_ws(ws), "incomplete workspace");
-    CODLAD_REQUIRE(n_nodes > 0 && T > 0, "n_nodes and T must be positive");
-    CODLAD_REQUIRE(!w->self_condition || x_start, "a self-conditioned model needs the x_start buffer");
-    CODLAD_REQUIRE(w->out_dim == 6 || w->out_dim == 3,
-                   "the DDPM loop needs a model with 6 outputs (mean | variance logits) or 3 (fixed-variance samplers)");
+extern "C" int codlad_ddpm_pred_xstart(const float *x, const float *model_out, const float *coef_host, int n_nodes,
+                                      float *pred_xstart, void *stream) {
+    CODLAD_REQUIRE(x && model_out && coef_host && pred_xstart, "null pointer");
+    CODLAD_REQUIRE(n_nodes > 0, "n_nodes must be positive");
+    DdpmCoef cf;
+    for (int k = 0; k < 8; ++k) cf.c[k] = coef_host[k];
+    hipLaunchKernelGGL(ddpm_pred_xstart_kernel, dim3((n_nodes * 3 + 255) / 256), dim3(256), 0, (hipStream_t)stream, x,
+                       model_out, cf, n_nodes, pred_xstart);
+    return codlad_check_launch("codlad_ddpm_pred_xstart");
+}
+
+extern "C" int codlad_ddpm_posterior_step(const float *x, const float *pred_xstart, const float *model_out,
+                                          const float *noise, const float *grad, const float *coef_host,
+                                          float fixed_variance, int n_nodes, float *x_out, float *x_start_out,
+                                          void *stream) {
+    CODLAD_REQUIRE(x && pred_xstart && model_out && noise && coef_host && x_out, "null pointer");
+    CODLAD_REQUIRE(n_nodes > 0, "n_nodes must be positive");
+    DdpmCoef cf;
+    for (int k = 0; k < 8; ++k) cf.c[k] = coef_host[k];
+    hipLaunchKernelGGL(ddpm_posterior_kernel, dim3((n_nodes * 3 + 255) / 256), dim3(256), 0, (hipStream_t)stream, x,
+                       pred_xstart, model_out, noise, grad, cf, fixed_variance, n_nodes, x_out, x_start_out);
+    return codlad_check_launch("codlad_ddpm_posterior_step");
+}
+
+// the loop of codlad_sample_loop / codlad_sample_loop_pinned (pin_x0 == NULL: no pinning, the plain final_kernel)
+static int sample_loop(const codlad_denoiser_weights *w, const int32_t *node_info, int n_nodes, const int32_t *E_idx,
+                       const float *h_E0, const float *E1, int n_snodes, float *x, float *x_start, const float *noise,
+                       const float *mods, const float *coef, int T, const float *pin_x0, const uint8_t *pin_mask,
+                       const codlad_workspace *ws, void *stream) {
     hipStream_t st = (hipStream_t)stream;
     // self-conditioning (gaussian_diffusion.py:530-547): step k reads the pred_xstart step k-1 wrote;
     // the first step gets none, which the model treats as zeros (latent_model.py:211)
@@ -862,10 +911,46 @@ extern "C" int codlad_sample_loop(const codlad_denoiser_weights *w, const int32_
         fa.hV = ws->hV; fa.mods = mods_t + mods_offset(6); fa.out_w = w->out_w; fa.out_b = w->out_b;
         fa.n_nodes = n_nodes; fa.x = x; fa.noise = noise + (size_t)k * n_nodes * 3;
         fa.coef = coef + (size_t)i * 8; fa.x_start = x_start; fa.status = ws->status; fa.n_out = w->out_dim;
-        hipLaunchKernelGGL(final_kernel, dim3((n_nodes + 7) / 8), dim3(256), 0, st, fa);
+        if (pin_x0)
+            hipLaunchKernelGGL(final_kernel<true>, dim3((n_nodes + 7) / 8), dim3(256), 0, st, fa, pin_x0, pin_mask);
+        else
+            hipLaunchKernelGGL(final_kernel<false>, dim3((n_nodes + 7) / 8), dim3(256), 0, st, fa, nullptr, nullptr);
     }
+    return 0;
+}
+
+#define SAMPLE_LOOP_REQUIRE()                                                                                          \
+    CODLAD_REQUIRE(w && node_info && E_idx && h_E0 && x && noise && mods && coef, "null pointer");                     \
+    CODLAD_REQUIRE(check_ws(ws), "incomplete workspace");                                                             \
+    CODLAD_REQUIRE(n_nodes > 0 && T > 0, "n_nodes and T must be positive");                                           \
+    CODLAD_REQUIRE(!w->self_condition || x_start, "a self-conditioned model needs the x_start buffer");               \
+    CODLAD_REQUIRE(w->out_dim == 6 || w->out_dim == 3,                                                                \
+                   "the DDPM loop needs a model with 6 outputs (mean | variance logits) or 3 (fixed-variance samplers)")
+
+extern "C" int codlad_sample_loop(const codlad_denoiser_weights *w, const int32_t *node_info,
+                                  int n_nodes, const int32_t *E_idx, const float *h_E0,
+                                  const float *E1, int n_snodes, float *x, float *x_start,
+                                  const float *noise, const float *mods, const float *coef, int T,
+                                  const codlad_workspace *ws, void *stream) {
+    SAMPLE_LOOP_REQUIRE();
+    sample_loop(w, node_info, n_nodes, E_idx, h_E0, E1, n_snodes, x, x_start, noise, mods, coef, T, nullptr, nullptr, ws,
+                stream);
     return codlad_check_launch("codlad_sample_loop");
 }
+
+extern "C" int codlad_sample_loop_pinned(const codlad_denoiser_weights *w, const int32_t *node_info,
+                                         int n_nodes, const int32_t *E_idx, const float *h_E0,
+                                         const float *E1, int n_snodes, float *x, float *x_start,
+                                         const float *noise, const float *mods, const float *coef, int T,
+                                         const float *pin_x0, const uint8_t *pin_mask,
+                                         const codlad_workspace *ws, void *stream) {
+    SAMPLE_LOOP_REQUIRE();
+    CODLAD_REQUIRE(pin_x0 && pin_mask, "null pointer (pin_x0 / pin_mask)");
+    sample_loop(w, node_info, n_nodes, E_idx, h_E0, E1, n_snodes, x, x_start, noise, mods, coef, T, pin_x0, pin_mask, ws,
+                stream);
+    return codlad_check_launch("codlad_sample_loop_pinned");
+}
+#undef SAMPLE_LOOP_REQUIRE
 
 extern "C" int codlad_status_check(int32_t *status, void *stream) {
     CODLAD_REQUIRE(status, "null pointer");

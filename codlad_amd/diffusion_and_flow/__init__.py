@@ -5,7 +5,11 @@ Same call surface as the reference (`diffusion_and_flow/__init__.py:10-60`): the
 progress)`, `.p_sample_loop_progressive`, `.p_sample`, the schedule tables and `timestep_map`.
 The arithmetic is on the GPU: when `model` is the forward of a codlad_amd `ProteinMPNN_diffusion_new`
 the whole loop is one `codlad_sample_loop` call; any other CUDA callable is stepped with
-`codlad_ddpm_update`.  Training losses are out of scope.
+`codlad_ddpm_update`.  The reference's hooks are honoured: `denoised_fn` rewrites the x_0 prediction before the
+clamp and `cond_fn` adds variance * gradient to the posterior mean (gaussian_diffusion.py:335-349, 374-384); a
+`PinLatents` denoised_fn on the HIP model without cond_fn is fused into the loop (`codlad_sample_loop_pinned`), any
+other callable runs between the two halves of the split step (`codlad_ddpm_pred_xstart` /
+`codlad_ddpm_posterior_step`).  Training losses are out of scope.
 """
 import enum
 
@@ -27,12 +31,46 @@ class ModelVarType(enum.Enum):
     LEARNED_RANGE = enum.auto()
 
 
+class PinLatents:
+    """Residue pinning as a `denoised_fn`: the x_0 prediction of the residues where `mask` is set is replaced by the known
+    latents `x0` at every step, so they end the loop on them (unless clip_denoised clamps them) and the other residues
+    are sampled conditioned on them.  An ordinary callable, `torch.where(mask[..., None], x0, x)`, so it is a valid
+    denoised_fn for the reference's sampler too; given to `p_sample_loop` with the codlad_amd model and no cond_fn it
+    runs fused into the loop.  x0 [N, L, C] floating point (the sampler's normalised latent space), mask [N, L] bool."""
+
+    def __init__(self, x0, mask):
+        if not isinstance(x0, torch.Tensor) or not x0.is_floating_point():
+            raise TypeError(f"PinLatents: x0 must be a floating-point tensor, got "
+                            f"{x0.dtype if isinstance(x0, torch.Tensor) else type(x0).__name__}")
+        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool:
+            raise TypeError(f"PinLatents: mask must be a bool tensor, got "
+                            f"{mask.dtype if isinstance(mask, torch.Tensor) else type(mask).__name__}")
+        if x0.dim() < 2 or tuple(mask.shape) != tuple(x0.shape[:-1]):
+            raise ValueError(f"PinLatents: mask must have the shape of x0 without its channel axis: x0 {tuple(x0.shape)}, "
+                             f"mask {tuple(mask.shape)}")
+        if x0.device != mask.device:
+            raise ValueError(f"PinLatents: x0 ({x0.device}) and mask ({mask.device}) are on different devices")
+        self.x0, self.mask = x0, mask
+
+    def __call__(self, x):
+        if tuple(x.shape) != tuple(self.x0.shape):
+            raise ValueError(f"PinLatents: pred_xstart {tuple(x.shape)} does not match x0 {tuple(self.x0.shape)}")
+        return torch.where(self.mask[..., None], self.x0, x)
+
+
+def _check_hook_output(v, x, what):
+    if not isinstance(v, torch.Tensor) or tuple(v.shape) != tuple(x.shape) or not v.is_floating_point() or not v.is_cuda:
+        desc = f"{v.dtype} {tuple(v.shape)} on {v.device}" if isinstance(v, torch.Tensor) else type(v).__name__
+        raise ValueError(f"{what} must return a floating-point CUDA tensor of the sample's shape {tuple(x.shape)}, got {desc}")
+
+
 class SpacedDiffusion(Tables):
     """Respaced ancestral sampler (reference respace.py:65-114 + gaussian_diffusion.py:404-547) with every branch of
     p_mean_variance that `create_diffusion` can select (gaussian_diffusion.py:303-349): the model predicts the noise
     (EPSILON, the default) or x_0 (START_X, test.py --predict_xstart); the variance is the learned range
     (LEARNED_RANGE; LEARNED takes the same formula in the reference) or fixed (FIXED_SMALL / FIXED_LARGE, with a
-    model whose head has no variance channels); pred_xstart is optionally clipped into [-1, 1] (clip_denoised)."""
+    model whose head has no variance channels); pred_xstart is optionally clipped into [-1, 1] (clip_denoised).
+    denoised_fn / cond_fn as in the reference (see the module docstring)."""
 
     def __init__(self, use_timesteps, betas, model_mean_type=ModelMeanType.EPSILON,
                  model_var_type=ModelVarType.LEARNED_RANGE, loss_type=None, self_condition=False):
@@ -57,6 +95,12 @@ class SpacedDiffusion(Tables):
         return self.step_coefficients(predict_xstart=self.model_mean_type is ModelMeanType.START_X, var_type=var,
                                       clip_denoised=bool(clip_denoised))
 
+    def fixed_variances(self):
+        """[T] fp32 table variance of a fixed-variance sampler (the factor of cond_fn's gradient; zeros otherwise)."""
+        var = {ModelVarType.FIXED_SMALL: "fixed_small", ModelVarType.FIXED_LARGE: "fixed_large"}.get(self.model_var_type,
+                                                                                                      "learned_range")
+        return self.step_variances(var)
+
     # ------------------------------------------------------------------------------------------
     @staticmethod
     def _hip_module(model):
@@ -66,9 +110,9 @@ class SpacedDiffusion(Tables):
 
     @staticmethod
     def _check_args(clip_denoised, denoised_fn, cond_fn):
-        if denoised_fn is not None or cond_fn is not None:
-            raise NotImplementedError("denoised_fn / cond_fn (arbitrary Python callables inside the step) are not used by "
-                                      "the reference's sampling call (test.py:533) and are not built")
+        for name, fn in (("denoised_fn", denoised_fn), ("cond_fn", cond_fn)):
+            if fn is not None and not callable(fn):
+                raise TypeError(f"{name} must be callable or None, got {type(fn).__name__}")
 
     def _draw_noise(self, x, generator=None):
         """T draws of randn_like(x), in loop order, consuming the device RNG stream exactly as the
@@ -83,9 +127,12 @@ class SpacedDiffusion(Tables):
         self._check_args(clip_denoised, denoised_fn, cond_fn)
         model_kwargs = model_kwargs or {}
         mod = self._hip_module(model)
-        if mod is None:
+        pinned = isinstance(denoised_fn, PinLatents) and cond_fn is None
+        if mod is None or (denoised_fn is not None and not pinned) or cond_fn is not None:
+            # any model callable, or a hook that is not the fused pin: step by step (the HIP model's forward per step)
             final = None
             for final in self.p_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
+                                                        denoised_fn=denoised_fn, cond_fn=cond_fn,
                                                         model_kwargs=model_kwargs, device=device,
                                                         step_noise=step_noise):
                 pass
@@ -107,8 +154,14 @@ class SpacedDiffusion(Tables):
             raise NotImplementedError("fused loop on a padded mixed-length batch; pass equal-length "
                                       "structures per call (what the reference's loaders produce)")
         T = self.num_timesteps
+        pin = None
+        if pinned:
+            if tuple(denoised_fn.x0.shape) != tuple(img.shape) or not denoised_fn.x0.is_cuda:
+                raise ValueError(f"PinLatents: x0 must be a CUDA tensor of the sample's shape {tuple(img.shape)}, got "
+                                 f"{tuple(denoised_fn.x0.shape)} on {denoised_fn.x0.device}")
+            pin = (denoised_fn.x0.reshape(-1, img.shape[-1]), denoised_fn.mask.reshape(-1))
         x0 = mod.engine().sample(job, img.reshape(-1, img.shape[-1]), eps.reshape(T, -1, img.shape[-1]), self,
-                                 coef=self.coefficients(clip_denoised))
+                                 coef=self.coefficients(clip_denoised), pin=pin)
         return x0.view(img.shape)
 
     def p_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
@@ -122,8 +175,8 @@ class SpacedDiffusion(Tables):
         for k, i in enumerate(range(self.num_timesteps - 1, -1, -1)):
             t = torch.tensor([i] * shape[0], device=img.device)
             eps = step_noise[k] if step_noise is not None else torch.randn_like(img)
-            out = self.p_sample(model, img, t, clip_denoised=clip_denoised, model_kwargs=model_kwargs, noise=eps,
-                                x_self_cond=x_start if self.self_condition else None)
+            out = self.p_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
+                                model_kwargs=model_kwargs, noise=eps, x_self_cond=x_start if self.self_condition else None)
             yield out
             img = out["sample"]
             x_start = out["pred_xstart"]
@@ -140,8 +193,6 @@ class SpacedDiffusion(Tables):
         if x_self_cond is not None:
             kwargs["x_self_cond"] = x_self_cond
         model_out = model(x, map_t, **kwargs)
-        if noise is None:
-            noise = torch.randn_like(x)
         C = x.shape[-1]
         assert C == 3 and model_out.shape[-1] == (C if self.fixed_variance else 2 * C), \
             "latent_size 3 only; a fixed-variance sampler takes a model without variance channels " \
@@ -149,6 +200,26 @@ class SpacedDiffusion(Tables):
         import ctypes
         import numpy as np
         coef = np.ascontiguousarray(self.coefficients(clip_denoised)[i])
+        if denoised_fn is not None or cond_fn is not None:
+            # split step: raw pred_xstart -> denoised_fn -> clamp / posterior mean (+ variance * cond_fn) / noise, on the
+            # device; cond_fn sees x_t, the original-process timesteps and the model's kwargs (respace.py:99-100, 117-129)
+            from ..engine import Denoiser
+            raw = Denoiser.ddpm_pred_xstart(x, model_out, coef).view(x.shape)
+            pred = raw
+            if denoised_fn is not None:
+                pred = denoised_fn(raw)
+                _check_hook_output(pred, x, "denoised_fn")
+            if noise is None:                           # drawn where the reference draws it (gaussian_diffusion.py:440)
+                noise = torch.randn_like(x)
+            grad = None
+            if cond_fn is not None:
+                grad = cond_fn(x, map_t, **(model_kwargs or {}))
+                _check_hook_output(grad, x, "cond_fn")
+            sample, x_start = Denoiser.ddpm_posterior_step(x, pred, model_out, noise, coef, grad=grad,
+                                                           fixed_variance=float(self.fixed_variances()[i]))
+            return {"sample": sample.view(x.shape), "pred_xstart": x_start.view(x.shape)}
+        if noise is None:
+            noise = torch.randn_like(x)
         xs = x.contiguous().float()
         out = torch.empty_like(xs)
         x_start = torch.empty_like(xs)

@@ -93,3 +93,15 @@ class Tables:
             raise ValueError(f"unknown variance type {var_type!r}")
         c[:, 7] = (1 if predict_xstart else 0) + (2 if var_type.startswith("fixed") else 0) + (4 if clip_denoised else 0)
         return c
+
+    def step_variances(self, var_type="learned_range"):
+        """[T] fp32: the variance a fixed-variance sampler scales cond_fn's gradient with (gaussian_diffusion.py:320-334,
+        382: posterior_variance for fixed_small, posterior_variance[1] then the betas for fixed_large); zeros for the
+        learned range, whose variance is exp(log variance) of the model's output."""
+        if var_type == "fixed_small":
+            return self.posterior_variance.astype(np.float32)
+        if var_type == "fixed_large":
+            return np.append(self.posterior_variance[1], self.betas[1:]).astype(np.float32)
+        if var_type not in ("learned_range", "learned"):
+            raise ValueError(f"unknown variance type {var_type!r}")
+        return np.zeros(self.num_timesteps, dtype=np.float32)

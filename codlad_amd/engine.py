@@ -277,23 +277,28 @@ class Denoiser:
     # 8 700 +9.6 % (each half then takes the small-job node kernel), 5 220 -1.9 %, 3 480 +5.5 %, 1 740 -8 %.
     SPLIT_MIN_NODES = int(os.environ.get("CODLAD_SAMPLE_SPLIT_MIN_NODES", 8192))
 
-    def sample(self, job, x_T, noise, tables, check=True, coef=None, streams=None):
+    def sample(self, job, x_T, noise, tables, check=True, coef=None, streams=None, pin=None):
         """Full ancestral loop.  x_T [n_nodes,3]; noise [T,n_nodes,3] in loop order (first entry
         is used at step T-1); tables = diffusion_and_flow.schedule.Tables.  Returns x_0.
         check: after the loop, synchronise and raise if any step's output was not finite.
         coef: the [T, 8] step table when it is not the default sampler's (SpacedDiffusion.coefficients).
         streams: 1 = the whole job on the current stream; 2 = two half-jobs on two streams; None = 2 from
-        SPLIT_MIN_NODES nodes up (and at least two samples)."""
+        SPLIT_MIN_NODES nodes up (and at least two samples).
+        pin: (x0 [n_nodes,3], mask [n_nodes] bool / uint8 / int32) - residue pinning: at every step the pred_xstart of a
+        masked node is replaced by its x0 before the clamp (codlad_sample_loop_pinned)."""
         _require_cuda(x_T, "x_T")
         _require_cuda(noise, "noise")
         T = tables.num_timesteps
         assert noise.shape == (T, job.n_nodes, 3) and x_T.shape == (job.n_nodes, 3)
+        if pin is not None:
+            pin = self._pin_arrays(pin, job.n_nodes)
         if streams is None:
             streams = 2 if job.n_nodes >= self.SPLIT_MIN_NODES and len(job.sample_struct) >= 2 else 1
         if streams > 1:
             parts = job.parts(streams)
+            pins = None if pin is None else [(pin[0][i], pin[1][i]) for _p, i in parts]
             outs = self.sample_many([p for p, _i in parts], [x_T[i] for _p, i in parts], [noise[:, i] for _p, i in parts],
-                                    tables, check=check, coef=coef)
+                                    tables, check=check, coef=coef, pins=pins)
             x0 = torch.empty(job.n_nodes, 3, dtype=torch.float32, device=self.device)
             for (_p, i), o in zip(parts, outs):
                 x0[i] = o
@@ -311,21 +316,33 @@ class Denoiser:
         st = job.structures
         self._fresh_features(st)
         x_start = torch.empty_like(x) if self.self_condition else None   # pred_xstart, step to step
-        rc = self.lib.codlad_sample_loop(C.byref(self.weights.struct), _lib.ptr(job.node_info),
-                                         job.n_nodes, _lib.ptr(st.E_idx), _lib.ptr(st.h_E0),
-                                         _lib.ptr(st.E1), st.n_snodes, _lib.ptr(x), _lib.ptr(x_start),
-                                         _lib.ptr(noise), _lib.ptr(mods), _lib.ptr(coef), T, C.byref(job.ws),
-                                         _lib.stream_ptr(self.device))
-        _lib.check(rc, "codlad_sample_loop")
+        if pin is None:
+            rc = self.lib.codlad_sample_loop(C.byref(self.weights.struct), _lib.ptr(job.node_info),
+                                             job.n_nodes, _lib.ptr(st.E_idx), _lib.ptr(st.h_E0),
+                                             _lib.ptr(st.E1), st.n_snodes, _lib.ptr(x), _lib.ptr(x_start),
+                                             _lib.ptr(noise), _lib.ptr(mods), _lib.ptr(coef), T, C.byref(job.ws),
+                                             _lib.stream_ptr(self.device))
+            _lib.check(rc, "codlad_sample_loop")
+        else:
+            rc = self.lib.codlad_sample_loop_pinned(C.byref(self.weights.struct), _lib.ptr(job.node_info),
+                                                    job.n_nodes, _lib.ptr(st.E_idx), _lib.ptr(st.h_E0),
+                                                    _lib.ptr(st.E1), st.n_snodes, _lib.ptr(x), _lib.ptr(x_start),
+                                                    _lib.ptr(noise), _lib.ptr(mods), _lib.ptr(coef), T,
+                                                    _lib.ptr(pin[0]), _lib.ptr(pin[1]), C.byref(job.ws),
+                                                    _lib.stream_ptr(self.device))
+            _lib.check(rc, "codlad_sample_loop_pinned")
         if check:
             self.check_status(job)
         return x
 
-    def sample_many(self, jobs, x_Ts, noises, tables, check=True, coef=None):
+    def sample_many(self, jobs, x_Ts, noises, tables, check=True, coef=None, pins=None):
         """Several independent jobs at once, each on its own HIP stream: the node kernel of a 35 000-node job occupies 139 of
         the 256 CUs and every kernel has a tail - with a second job in flight another job's edge kernels run there (two
         half-jobs of BASELINE configuration 2: 1.03 x; more than two parts lose).  Every job carries its
-        own workspace and the library keeps no state between jobs, so the results are those of `sample` job by job."""
+        own workspace and the library keeps no state between jobs, so the results are those of `sample` job by job.
+        pins: None, or one `pin` of `sample` (or None) per job."""
+        pins = [None] * len(jobs) if pins is None else list(pins)
+        assert len(pins) == len(jobs)
         if not hasattr(self, "_streams"):
             self._streams = []
         while len(self._streams) < len(jobs):
@@ -335,16 +352,35 @@ class Denoiser:
             self._fresh_features(job.structures)
         self.step_mods(tables.timestep_map)
         outs = []
-        for job, x_T, noise, st in zip(jobs, x_Ts, noises, self._streams):
+        for job, x_T, noise, pin, st in zip(jobs, x_Ts, noises, pins, self._streams):
+            if pin is not None:
+                pin = self._pin_arrays(pin, job.n_nodes)         # (copies on the caller's stream)
             st.wait_stream(cur)
             with torch.cuda.stream(st):
-                outs.append(self.sample(job, x_T, noise, tables, check=False, coef=coef, streams=1))
+                outs.append(self.sample(job, x_T, noise, tables, check=False, coef=coef, streams=1, pin=pin))
         for st in self._streams[:len(jobs)]:
             cur.wait_stream(st)
         if check:
             for job in jobs:
                 self.check_status(job)
         return outs
+
+    @staticmethod
+    def _pin_arrays(pin, n_nodes):
+        """(x0, mask) -> (x0 fp32 [n_nodes,3] contiguous, mask uint8 [n_nodes]) on the GPU, checked."""
+        x0, mask = pin
+        _require_cuda(x0, "pin x0")
+        _require_cuda(mask, "pin mask")
+        if tuple(x0.shape) != (n_nodes, 3) or tuple(mask.shape) != (n_nodes,):
+            raise ValueError(f"pin: x0 must be [{n_nodes}, 3] and mask [{n_nodes}], got {tuple(x0.shape)} and {tuple(mask.shape)}")
+        if not x0.is_floating_point():
+            raise TypeError(f"pin: x0 must be a floating-point tensor, got {x0.dtype}")
+        if mask.dtype not in (torch.bool, torch.uint8, torch.int32):
+            raise TypeError(f"pin: mask must be bool, uint8 or int32, got {mask.dtype}")
+        x0 = x0.contiguous().float()
+        if mask.dtype != torch.uint8:
+            mask = mask != 0
+        return x0, mask.to(torch.uint8).contiguous()
 
     def ddpm_update(self, x, model_out, noise, tables, i, return_x_start=False):
         _require_cuda(x, "x")
@@ -359,6 +395,60 @@ class Denoiser:
                                          _lib.stream_ptr(self.device))
         _lib.check(rc, "codlad_ddpm_update")
         return (out, x_start) if return_x_start else out
+
+    @staticmethod
+    def ddpm_pred_xstart(x, model_out, coef):
+        """The raw pred_xstart of one step (before denoised_fn and the clamp): x [n,3], model_out [n,6] (or [n,3] with a
+        fixed-variance row), coef = one [8] row of the step table (codlad_ddpm_pred_xstart).  Needs no Denoiser: any
+        model's output is stepped with it (diffusion_and_flow's per-step path)."""
+        _require_cuda(x, "x")
+        x = x.contiguous().float()
+        out = torch.empty_like(x)
+        coef = np.ascontiguousarray(coef, dtype=np.float32)
+        _check_step_operands(x, model_out, coef)
+        rc = _lib.lib().codlad_ddpm_pred_xstart(_lib.ptr(x), _lib.ptr(model_out.contiguous().float()),
+                                                coef.ctypes.data_as(C.c_void_p), x.numel() // 3, _lib.ptr(out),
+                                                _lib.stream_ptr(x.device))
+        _lib.check(rc, "codlad_ddpm_pred_xstart")
+        return out
+
+    @staticmethod
+    def ddpm_posterior_step(x, pred_xstart, model_out, noise, coef, grad=None, fixed_variance=0.0):
+        """The rest of the step given a (processed) pred_xstart: clamp (mode bit 4), posterior mean, + variance * grad
+        (cond_fn), noise -> (sample, clamped pred_xstart) (codlad_ddpm_posterior_step)."""
+        _require_cuda(x, "x")
+        x = x.contiguous().float()
+        out = torch.empty_like(x)
+        x_start = torch.empty_like(x)
+        coef = np.ascontiguousarray(coef, dtype=np.float32)
+        g = None if grad is None else grad.contiguous().float()
+        _check_step_operands(x, model_out, coef, pred_xstart=pred_xstart, noise=noise, grad=g)
+        rc = _lib.lib().codlad_ddpm_posterior_step(_lib.ptr(x), _lib.ptr(pred_xstart.contiguous().float()),
+                                                   _lib.ptr(model_out.contiguous().float()),
+                                                   _lib.ptr(noise.contiguous().float()), _lib.ptr(g),
+                                                   coef.ctypes.data_as(C.c_void_p), C.c_float(fixed_variance),
+                                                   x.numel() // 3, _lib.ptr(out), _lib.ptr(x_start),
+                                                   _lib.stream_ptr(x.device))
+        _lib.check(rc, "codlad_ddpm_posterior_step")
+        return out, x_start
+
+
+def _check_step_operands(x, model_out, coef, **same_as_x):
+    """Shapes of the split step's operands: the kernels index model_out as [n][6] ([n][3] under the fixed-variance mode
+    bit) and every other tensor as [n][3]."""
+    n = x.numel() // 3
+    if x.numel() != 3 * n or n == 0:
+        raise ValueError(f"x must hold [n, 3] latents, got {tuple(x.shape)}")
+    if coef.shape != (8,):
+        raise ValueError(f"coef must be one [8] row of the step table, got {coef.shape}")
+    width = 3 if int(coef[7]) & 2 else 6
+    for name, t in dict(model_out=model_out, **same_as_x).items():
+        if t is None:
+            continue
+        _require_cuda(t, name)
+        want = n * (width if name == "model_out" else 3)
+        if t.numel() != want:
+            raise ValueError(f"{name} holds {t.numel()} values, the step needs {want} ({n} nodes)")
 
 
 class Decoder:

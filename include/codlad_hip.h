@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define CODLAD_ABI_VERSION 13
+#define CODLAD_ABI_VERSION 14
 #define CODLAD_H 128          /* hidden width of the denoiser                          */
 #define CODLAD_KNN 64         /* k_neighbors (reference models/latent_model.py:86)      */
 #define CODLAD_MODS_PER_STEP 6016 /* 3*9*128 (enc) + 3*6*128 (dec) + 2*128 (final)      */
@@ -233,6 +233,27 @@ int codlad_ddpm_update(const float *x, const float *model_out, const float *nois
                        const float *coef_host, int n_nodes, float *x_out, float *x_start_out /* pred_xstart, may be NULL */,
                        void *stream);
 
+/* Row 2 split in two around a caller's denoised_fn / cond_fn (gaussian_diffusion.py:335-349, 374-384, 436-446), so that
+ * arbitrary device callables can run between the halves without a host round trip.  coef_host[8] and its mode bits as
+ * for codlad_ddpm_update; both halves use its expressions, so a pin applied between them rounds like the fused one.
+ *
+ * codlad_ddpm_pred_xstart: pred_xstart [n_nodes][3] = the raw x_0 prediction of the step, before denoised_fn and before
+ *   the clamp: model_out itself under bit 1, else sqrt_recip_acp * x - sqrt_recipm1_acp * eps.  model_out [n_nodes][6],
+ *   or [n_nodes][3] under bit 2. */
+int codlad_ddpm_pred_xstart(const float *x, const float *model_out, const float *coef_host, int n_nodes,
+                            float *pred_xstart, void *stream);
+
+/* codlad_ddpm_posterior_step: the rest of the step, given the (processed) pred_xstart [n_nodes][3]:
+ *   bit 4 clamps pred_xstart into [-1, 1]; mean = post_coef1 * pred_xstart + post_coef2 * x;
+ *   grad [n_nodes][3] (may be NULL = no cond_fn): mean += variance * grad, variance = exp(log variance of the step)
+ *   for the learned range (read from model_out's variance channels), `fixed_variance` under bit 2 (the table value,
+ *   posterior_variance or the fixed-large betas; ignored otherwise);
+ *   x_out = mean + nonzero * exp(0.5 * log variance) * noise.  x_start_out (may be NULL) receives the clamped
+ *   pred_xstart, the self-conditioning input of the next step.  x_out may alias x, x_start_out may alias pred_xstart. */
+int codlad_ddpm_posterior_step(const float *x, const float *pred_xstart, const float *model_out, const float *noise,
+                               const float *grad /* may be NULL */, const float *coef_host, float fixed_variance,
+                               int n_nodes, float *x_out, float *x_start_out /* may be NULL */, void *stream);
+
 /* Rows 2-7 fused: p_sample_loop (gaussian_diffusion.py:451-547, respace.py:124-129).
  * x [n_nodes][3] holds x_T on entry and x_0 on return.  noise [T][n_nodes][3] is consumed in
  * loop order (entry 0 at step T-1).  mods [T][6016] and coef [T][8] (device) are indexed by
@@ -242,6 +263,17 @@ int codlad_sample_loop(const codlad_denoiser_weights *w, const int32_t *node_inf
                        const int32_t *E_idx, const float *h_E0, const float *E1, int n_snodes,
                        float *x, float *x_start, const float *noise, const float *mods, const float *coef,
                        int T, const codlad_workspace *ws, void *stream);
+
+/* codlad_sample_loop with residue pinning: the denoised_fn `x0 -> where(pin_mask, pin_x0, x0)` fused into every step.
+ * pin_x0 [n_nodes][3] holds the known (normalised) latents, pin_mask [n_nodes] uint8 (0 = sampled, else pinned).  At a
+ * pinned node each step's raw pred_xstart is replaced by pin_x0 before the clamp (mode bit 4), so x_start and the
+ * posterior mean see the pinned value; with the last step's post_coef1 = 1, post_coef2 = 0 and no noise a pinned node
+ * ends on pin_x0 exactly (clamped when bit 4 is set).  The other arguments as for codlad_sample_loop. */
+int codlad_sample_loop_pinned(const codlad_denoiser_weights *w, const int32_t *node_info, int n_nodes,
+                              const int32_t *E_idx, const float *h_E0, const float *E1, int n_snodes,
+                              float *x, float *x_start, const float *noise, const float *mods, const float *coef,
+                              int T, const float *pin_x0, const uint8_t *pin_mask, const codlad_workspace *ws,
+                              void *stream);
 
 /* Row 8: get_norm_feature(norm_in=False) + nearest code
  * (utils/dataset_module.py:253; utils/vq_module.py:61-68 / VectorQuantize eval lookup).

@@ -12,6 +12,8 @@ the length mask; mdtraj I/O is replaced by saving coordinates as .npy (and multi
 Data: `--pdb_files ens.pdb ...` (multi-model PDB ensembles -> the reference's load_dataset without mdtraj),
 `--data_process --data_files f.pkl ...` (pickled per-frame dicts, as the reference's --data_process branch reads
 them) or `--synthetic` (no PED/PDB/Atlas files ship with the reference).
+Addition: `--fix_residues SPEC` keeps the VQ-VAE encoder's latents of the chosen residues (residue pinning, a
+`PinLatents` denoised_fn) and samples the rest of each structure conditioned on them.
 """
 import argparse
 import os
@@ -22,7 +24,7 @@ import numpy as np
 import torch
 
 from codlad_amd import metrics, synth
-from codlad_amd.diffusion_and_flow import create_diffusion
+from codlad_amd.diffusion_and_flow import PinLatents, create_diffusion
 from codlad_amd.models.latent_model import MPNN_models
 from codlad_amd.utils.dataset_module import CG_collate, get_norm_feature
 from codlad_amd.utils.model_module import build_vae, get_vae_model, load_decoder_state
@@ -56,9 +58,55 @@ def load_denoiser(args, device, load=True):
     return model.to(device).eval()
 
 
+def parse_fix_residues(spec):
+    """--fix_residues SPEC, e.g. "3-20,41" -> sorted 1-based residue positions (ranges inclusive).  Raises ValueError on
+    an empty, malformed, non-positive or reversed spec."""
+    if spec is None or not spec.strip():
+        raise ValueError("--fix_residues: empty residue spec")
+    pos = set()
+    for part in spec.split(","):
+        part = part.strip()
+        lo, sep, hi = part.partition("-")
+        if not lo.strip().isdigit() or (sep and not hi.strip().isdigit()):
+            raise ValueError(f"--fix_residues: {part!r} is not a position or a range a-b of 1-based positions")
+        a, b = int(lo), int(hi) if sep else int(lo)
+        if a < 1 or b < a:
+            raise ValueError(f"--fix_residues: {part!r} is out of range (positions start at 1, ranges run upwards)")
+        pos.update(range(a, b + 1))
+    return sorted(pos)
+
+
+def fix_residue_mask(positions, L, n_samples, device=None):
+    """[n_samples, L] bool: True at the pinned positions of a structure of L CG residues (flanking caps excluded)."""
+    if positions[-1] > L:
+        raise ValueError(f"--fix_residues: position {positions[-1]} is out of range for a structure of {L} residues")
+    mask = torch.zeros(n_samples, L, dtype=torch.bool, device=device)
+    mask[:, torch.tensor(positions, device=device) - 1] = True
+    return mask
+
+
+def check_fix_residues(args):
+    """Where --fix_residues applies: DDPM latent sampling decoded by a VQ-VAE whose encoder supplies the known latents,
+    on input that carries atoms (--pdb_files, --data_process pickles, --synthetic).  -> the parsed positions or None."""
+    if getattr(args, "fix_residues", None) is None:
+        return None
+    if args.experiment != "latent" or args.model != "diffusion":
+        raise SystemExit("--fix_residues needs --experiment latent --model diffusion (residue pinning is a denoised_fn of "
+                         "the DDPM sampler; the flow-matching ODE path has no such hook)")
+    if args.vae_type not in ("N6", "K3", "K4"):
+        raise SystemExit(f"--fix_residues needs a VQ-VAE (N6 / K3 / K4) to encode the known residues, not {args.vae_type!r}")
+    if not (args.synthetic or getattr(args, "pdb_files", None) or args.data_process):
+        raise SystemExit("--fix_residues needs input with atoms: --pdb_files, --data_process --data_files or --synthetic")
+    try:
+        return parse_fix_residues(args.fix_residues)
+    except ValueError as e:
+        raise SystemExit(str(e))
+
+
 def load_vae(args, device, load=True):
-    """The VQ-VAE; with its e3nn encoder when the run needs it (`--experiment recon` encodes the batch's atoms)."""
-    enc = args.experiment == "recon"
+    """The VQ-VAE; with its e3nn encoder when the run needs it (`--experiment recon` encodes the batch's atoms, so does
+    --fix_residues for the latents it pins)."""
+    enc = args.experiment == "recon" or getattr(args, "fix_residues", None) is not None
     if not load:
         return build_vae(args.vae_type, with_encoder=enc).to(device).eval()
     if args.synthetic_weights:
@@ -120,7 +168,8 @@ def iter_batches(args):
                 out = output_name(f"synthetic_L{L}", c, len(plan))
                 _TOPOLOGY[out] = (names, [synth.PDB_ATOM_ORDER[nm] for nm in names])
                 batch = synth.make_batch(prot, range(a, b))
-                if getattr(args, "experiment", "latent") == "recon":      # the encoder reads the all-atom side of the batch
+                # the encoder reads the all-atom side of the batch (recon; the known latents of --fix_residues)
+                if getattr(args, "experiment", "latent") == "recon" or getattr(args, "fix_residues", None) is not None:
                     batch.update(synth.make_atoms(prot, range(a, b), seed=1000 + i))
                 yield out, batch, prot["info"]
         return
@@ -239,6 +288,7 @@ def main(args):
     if args.cfg_scale > 1.0:
         raise NotImplementedError("cfg_scale > 1 calls model.forward_with_cfg, which the reference model "
                                   "does not define (dead path)")
+    fixed = check_fix_residues(args)
     # only rank 0 reads checkpoints; the other ranks receive its weights (reference: one process, test.py:264-286)
     vae = load_vae(args, device, load=rank == 0)
     model, cvae = None, None
@@ -269,6 +319,10 @@ def main(args):
         from codlad_amd.parallel import shard_units, unit_cost
         costs = [int(b["num_CGs"].shape[0]) * unit_cost(int(b["num_CGs"][0])) for _g, _n, b, _i in units]
         units = [units[u] for u in shard_units(costs, world)[rank]]
+    if fixed is not None:
+        short = min(int(b["num_CGs"][0]) for _g, _n, b, _i in units) if units else None
+        if short is not None and fixed[-1] > short:
+            raise SystemExit(f"--fix_residues: position {fixed[-1]} is out of range (the shortest structure has {short} residues)")
     for g, name, batch, info in units:
         gen = unit_generator(args, g, device)
         batch = {k: (v.to(device) if hasattr(v, "to") else v) for k, v in batch.items()}
@@ -282,7 +336,14 @@ def main(args):
         if args.experiment == "latent":
             z = torch.randn(B * E, L, args.latent_size, device=device, generator=gen)
             if args.model == "diffusion":
-                samples = diffusion.p_sample_loop(model.forward, z.shape, z, clip_denoised=False,
+                pin = None
+                if fixed is not None:
+                    # the VQ-VAE encoder's latents of the batch, normalised as the samples are de-normalised below, pin the
+                    # chosen residues of every ensemble member (a PinLatents denoised_fn: fused into the loop)
+                    known = get_norm_feature(vae.get_latent_wovq(batch)[0], args.vae_type, norm_channel=args.norm,
+                                             norm_single=args.norm_single, norm_in=True, dataname=args.data_type)
+                    pin = PinLatents(known.repeat(E, 1, 1).contiguous(), fix_residue_mask(fixed, L, B * E, device))
+                samples = diffusion.p_sample_loop(model.forward, z.shape, z, clip_denoised=False, denoised_fn=pin,
                                                   model_kwargs=dict(y=None, mask=mask, batch=rep), device=device,
                                                   step_noise=diffusion._draw_noise(z, generator=gen))
             else:                                               # --model fm / icfm / otcfm ...: ODE sampling
@@ -383,4 +444,8 @@ if __name__ == "__main__":
     p.add_argument("--atom_cutoff", type=float, default=9.0)
     p.add_argument("--cg_cutoff", type=float, default=21.0)
     p.add_argument("--edgeorder", type=int, default=2)
+    p.add_argument("--fix_residues", default=None, metavar="SPEC",
+                   help="keep the latents of these residues (1-based CG positions, flanking caps excluded, e.g. 3-20,41) "
+                        "as the VQ-VAE encodes them from the input's atoms and sample the rest conditioned on them "
+                        "(--experiment latent --model diffusion, VQ-VAE N6 / K3 / K4)")
     main(p.parse_args())

@@ -408,7 +408,8 @@ class NoiseFeeder:
         return e
 
 
-def run_loop(ref, model, T, z, eps, mask, batch, self_condition=False, clip_denoised=False, **diffusion_kwargs):
+def run_loop(ref, model, T, z, eps, mask, batch, self_condition=False, clip_denoised=False, denoised_fn=None, cond_fn=None,
+             **diffusion_kwargs):
     import diffusion_and_flow.gaussian_diffusion as gd
     kw = dict(noise_schedule="linear", predict_xstart=False, rescale_learned_sigmas=False, self_condition=self_condition)
     kw.update(diffusion_kwargs)
@@ -419,6 +420,7 @@ def run_loop(ref, model, T, z, eps, mask, batch, self_condition=False, clip_deno
     try:
         traj = []
         for out in d.p_sample_loop_progressive(model.forward, z.shape, z, clip_denoised=clip_denoised,
+                                               denoised_fn=denoised_fn, cond_fn=cond_fn,
                                                model_kwargs=dict(y=None, mask=mask, batch=batch),
                                                device="cpu"):
             traj.append(out["sample"])
@@ -586,6 +588,32 @@ def g16_sampler_branches(ref, model):
         save(f"g16_sampler_{name}", sample=traj[-1], traj=torch.stack(traj))
 
 
+def g17_guidance(ref, model):
+    """Guided sampling: the reference's own loop with a denoised_fn (residue pinning, a generic map) and / or a cond_fn
+    (gaussian_diffusion.py:335-349, 374-384, 436-446; respace.py:99-100, 117-129), the cases and hooks of
+    tests/guidance_cases.py."""
+    from tests import guidance_cases as gc
+    print("g17 guidance (denoised_fn / cond_fn)")
+    models = {"eps": model}
+    sc = ref["MPNN_models"]["mpnn_diffusion"](input_size=3, unconditional=True, diffusion="diffusion", self_condition=True)
+    sc.load_state_dict(synth.denoiser_state_dict(cases.WEIGHT_SEED, self_condition=True), strict=True)
+    models["selfcond"] = sc.eval()
+    three = ref["MPNN_models"]["mpnn_diffusion"](input_size=3, unconditional=True, diffusion="fm", self_condition=False)
+    three.load_state_dict(synth.denoiser_state_dict(cases.WEIGHT_SEED, flow=True), strict=True)
+    models["three"] = three.eval()
+    for name, (L, B, seed, kw, clip, kind, _hooks) in gc.GUIDANCE_CASES.items():
+        prot, batch, _x, _t, mask = cases.denoiser_inputs(L, B, seed)
+        z, eps = cases.loop_noise(gc.T, B, L, seed)
+        denoised_fn, cond_fn = gc.hooks_for(name)
+        kw = dict(kw)
+        traj = run_loop(ref, models[kind], gc.T, z, eps, mask, batch, self_condition=kw.pop("self_condition", False),
+                        clip_denoised=clip, denoised_fn=denoised_fn, cond_fn=cond_fn, **kw)
+        arrays = dict(sample=traj[-1], traj=torch.stack(traj))
+        if cond_fn is not None:
+            arrays["cond_timesteps"] = np.array(cond_fn.timesteps)      # what the reference hands cond_fn: mapped t
+        save(f"g17_guidance_{name}", **arrays)
+
+
 def g15_e3nn_encoder_prior(ref):
     """Row 8f-1, the reference's own lines executed: e3nnPrior.forward (models/vae_model.py:275-294), e3nnEncoder.forward
     (:112-164, with build_atom / build_cg / build_cross_conv_graph :166-204) and TensorProductConvLayer.forward
@@ -673,6 +701,7 @@ def main():
     if want("g14"): g14_e3nn_fixtures(ref)
     if want("g15"): g15_e3nn_encoder_prior(ref)
     if want("g16"): g16_sampler_branches(ref, model)
+    if want("g17"): g17_guidance(ref, model)
 
 
 if __name__ == "__main__":
