@@ -768,6 +768,42 @@ DEV float ddpm_posterior(float xt, float x0, float logvar, const float *cf, floa
     return mean + (cf[6] * expf(0.5f * logvar)) * noise;
 }
 
+// One DDIM update of a scalar (Song et al. 2021, the IDDPM release's ddim_sample / ddim_reverse_sample), every product,
+// sum and quotient rounded separately like the reference's elementwise tensor ops.
+// cf = one row of Tables.ddim_coefficients(): {sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod, sqrt(acp_prev),
+// sqrt(1 - acp_prev - sigma^2), nonzero * sigma, sqrt(1 - acp), -, mode}; for the reverse step (REVERSE) columns 2-3 are
+// sqrt(acp_next), sqrt(1 - acp_next) and column 4 is not read.  mode: bits 1 (START_X) and 4 (clip_denoised) as for
+// ddpm_step - given by the caller, not read from cf[7]; the variance type (bit 2) only decides the model's head width.
+// ddim_step: the raw pred_xstart, the pin (as in ddpm_step), then ddim_update; the split step (codlad_ddpm_pred_xstart,
+// the caller's denoised_fn, codlad_ddim_step) runs the same two expressions around the hook, so the two paths round alike.
+// ddim_update: the clamp, an optional condition_score with the caller's gradient (gaussian_diffusion.py:386-402:
+// eps -= sqrt(1 - acp) * grad, pred_xstart from eps), eps re-derived from pred_xstart (:369-372, also for an
+// epsilon model), then mean = pred_xstart * sqrt(acp_prev) + sqrt(1 - acp_prev - sigma^2) * eps (+ nonzero * sigma * noise
+// forward).  *x0_out (optional) receives the pred_xstart the step used, the self-conditioning input of the next step.
+template <bool REVERSE>
+DEV float ddim_update(float xt, float x0, const float *cf, int mode, float noise, float *x0_out, const float *grad) {
+#pragma clang fp contract(off)
+    if (mode & CODLAD_DDPM_CLIP) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    if (grad) {
+        float e = (cf[0] * xt - x0) / cf[1];
+        e = e - cf[5] * *grad;
+        x0 = cf[0] * xt - cf[1] * e;
+    }
+    if (x0_out) *x0_out = x0;
+    const float eps = (cf[0] * xt - x0) / cf[1];
+    const float mean = x0 * cf[2] + cf[3] * eps;
+    return REVERSE ? mean : mean + cf[4] * noise;
+}
+
+template <bool REVERSE>
+DEV float ddim_step(float xt, float out, const float *cf, int mode, float noise, float *x0_out = nullptr,
+                    const float *pin = nullptr) {
+#pragma clang fp contract(off)
+    float x0 = (mode & CODLAD_DDPM_START_X) ? out : cf[0] * xt - cf[1] * out;
+    if (pin) x0 = *pin;
+    return ddim_update<REVERSE>(xt, x0, cf, mode, noise, x0_out, nullptr);
+}
+
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------

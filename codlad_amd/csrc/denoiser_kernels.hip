@@ -346,8 +346,15 @@ DEV float half_wave_allsum(float v) {
 // raw pred_xstart is replaced by pin_x0[n] before the clamp.  A template parameter, so that final_kernel<false> (the
 // logits mode and the plain loop) is instruction for instruction the kernel it was before pinning existed; only its
 // argument block grows by the two unused pointers.
-template <bool PIN>
-__global__ __launch_bounds__(256) void final_kernel(FinalArgs a, const float *pin_x0, const uint8_t *pin_mask) {
+// STEP: the update of the loop - CODLAD_STEP_DDPM (ddpm_step, mode from the table's column 7), CODLAD_STEP_DDIM or
+// CODLAD_STEP_DDIM_REVERSE (ddim_step with the host's `mode` argument; the reverse step reads no noise).  The DDPM
+// instantiations are instruction for instruction what they were before DDIM existed (they do not read `mode`, which
+// follows the other arguments).
+#define CODLAD_STEP_DDPM 0
+#define CODLAD_STEP_DDIM 1
+#define CODLAD_STEP_DDIM_REVERSE 2
+template <bool PIN, int STEP = CODLAD_STEP_DDPM>
+__global__ __launch_bounds__(256) void final_kernel(FinalArgs a, const float *pin_x0, const uint8_t *pin_mask, int mode) {
     const int l = threadIdx.x & 31;
     const int n = blockIdx.x * 8 + (threadIdx.x >> 5);
     const bool live = n < a.n_nodes;
@@ -397,7 +404,12 @@ __global__ __launch_bounds__(256) void final_kernel(FinalArgs a, const float *pi
         const float vv = l == 0 ? o[3] : (l == 1 ? o[4] : o[5]);      // (zeros for a 3-row head: fixed-variance samplers)
         const size_t i = (size_t)n * 3 + l;
         const float *pin = PIN && pin_mask[n] ? pin_x0 + i : nullptr;
-        a.x[i] = ddpm_step(a.x[i], eps, vv, a.coef, a.noise[i], a.x_start ? a.x_start + i : nullptr, pin);
+        if constexpr (STEP == CODLAD_STEP_DDPM)
+            a.x[i] = ddpm_step(a.x[i], eps, vv, a.coef, a.noise[i], a.x_start ? a.x_start + i : nullptr, pin);
+        else if constexpr (STEP == CODLAD_STEP_DDIM)
+            a.x[i] = ddim_step<false>(a.x[i], eps, a.coef, mode, a.noise[i], a.x_start ? a.x_start + i : nullptr, pin);
+        else
+            a.x[i] = ddim_step<true>(a.x[i], eps, a.coef, mode, 0.f, a.x_start ? a.x_start + i : nullptr, pin);
     }
 }
 
@@ -440,6 +452,17 @@ __global__ void ddpm_posterior_kernel(const float *x, const float *x0, const flo
     const float variance = fixed ? fixed_variance : expf(logvar);
     x_out[i] = ddpm_posterior(x[i], x0[i], logvar, cf.c, noise[i], x_start ? x_start + i : nullptr,
                               grad ? grad + i : nullptr, variance);
+}
+
+// The DDIM update after a caller's denoised_fn / cond_fn (codlad_ddim_step): its first half is ddpm_pred_xstart_kernel,
+// whose raw pred_xstart is ddim_step's; this is ddim_update, so a pin applied between them rounds as the fused one.
+template <bool REVERSE>
+__global__ void ddim_update_kernel(const float *x, const float *x0, const float *noise, const float *grad, DdpmCoef cf,
+                                   int mode, int n_nodes, float *x_out, float *x_start) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_nodes * 3) return;
+    x_out[i] = ddim_update<REVERSE>(x[i], x0[i], cf.c, mode, REVERSE ? 0.f : noise[i], x_start ? x_start + i : nullptr,
+                                    grad ? grad + i : nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -853,7 +876,7 @@ extern "C" int codlad_denoiser_forward(const codlad_denoiser_weights *w, const i
     FinalArgs fa = {};
     fa.hV = ws->hV; fa.mods = mods_t + mods_offset(6); fa.out_w = w->out_w; fa.out_b = w->out_b;
     fa.n_nodes = n_nodes; fa.logits = out; fa.status = ws->status; fa.n_out = w->out_dim;
-    hipLaunchKernelGGL(final_kernel<false>, dim3((n_nodes + 7) / 8), dim3(256), 0, st, fa, nullptr, nullptr);
+    hipLaunchKernelGGL(final_kernel<false>, dim3((n_nodes + 7) / 8), dim3(256), 0, st, fa, nullptr, nullptr, 0);
     return codlad_check_launch("codlad_denoiser_forward");
 }
 
@@ -893,28 +916,45 @@ extern "C" int codlad_ddpm_posterior_step(const float *x, const float *pred_xsta
     return codlad_check_launch("codlad_ddpm_posterior_step");
 }
 
-// the loop of codlad_sample_loop / codlad_sample_loop_pinned (pin_x0 == NULL: no pinning, the plain final_kernel)
+// the loop of codlad_sample_loop / codlad_sample_loop_pinned / codlad_ddim_loop (pin_x0 == NULL: no pinning).
+// step: CODLAD_STEP_* of final_kernel; `mode` is read by the DDIM steps only.  The forward loops run i = T-1 .. 0 and
+// consume noise entry k at step k; the reverse DDIM loop runs i = 0 .. T-1 and reads no noise.
 static int sample_loop(const codlad_denoiser_weights *w, const int32_t *node_info, int n_nodes, const int32_t *E_idx,
                        const float *h_E0, const float *E1, int n_snodes, float *x, float *x_start, const float *noise,
                        const float *mods, const float *coef, int T, const float *pin_x0, const uint8_t *pin_mask,
-                       const codlad_workspace *ws, void *stream) {
+                       const codlad_workspace *ws, void *stream, int step = CODLAD_STEP_DDPM, int mode = 0) {
     hipStream_t st = (hipStream_t)stream;
     // self-conditioning (gaussian_diffusion.py:530-547): step k reads the pred_xstart step k-1 wrote;
     // the first step gets none, which the model treats as zeros (latent_model.py:211)
     const bool sc = w->self_condition != 0;
+    const bool reverse = step == CODLAD_STEP_DDIM_REVERSE;
     for (int k = 0; k < T; ++k) {
-        const int i = T - 1 - k;
+        const int i = reverse ? k : T - 1 - k;
         const float *mods_t = mods + (size_t)i * CODLAD_MODS_PER_STEP;
         enqueue_forward(w, node_info, n_nodes, E_idx, h_E0, E1, (size_t)n_snodes, x, sc && k > 0 ? x_start : nullptr,
                         mods_t, ws, st);
         FinalArgs fa = {};
         fa.hV = ws->hV; fa.mods = mods_t + mods_offset(6); fa.out_w = w->out_w; fa.out_b = w->out_b;
-        fa.n_nodes = n_nodes; fa.x = x; fa.noise = noise + (size_t)k * n_nodes * 3;
+        fa.n_nodes = n_nodes; fa.x = x; fa.noise = reverse ? nullptr : noise + (size_t)k * n_nodes * 3;
         fa.coef = coef + (size_t)i * 8; fa.x_start = x_start; fa.status = ws->status; fa.n_out = w->out_dim;
-        if (pin_x0)
-            hipLaunchKernelGGL(final_kernel<true>, dim3((n_nodes + 7) / 8), dim3(256), 0, st, fa, pin_x0, pin_mask);
-        else
-            hipLaunchKernelGGL(final_kernel<false>, dim3((n_nodes + 7) / 8), dim3(256), 0, st, fa, nullptr, nullptr);
+        const dim3 grid((n_nodes + 7) / 8);
+        if (step == CODLAD_STEP_DDIM) {
+            if (pin_x0)
+                hipLaunchKernelGGL((final_kernel<true, CODLAD_STEP_DDIM>), grid, dim3(256), 0, st, fa, pin_x0, pin_mask, mode);
+            else
+                hipLaunchKernelGGL((final_kernel<false, CODLAD_STEP_DDIM>), grid, dim3(256), 0, st, fa, nullptr, nullptr, mode);
+        } else if (reverse) {
+            if (pin_x0)
+                hipLaunchKernelGGL((final_kernel<true, CODLAD_STEP_DDIM_REVERSE>), grid, dim3(256), 0, st, fa, pin_x0,
+                                   pin_mask, mode);
+            else
+                hipLaunchKernelGGL((final_kernel<false, CODLAD_STEP_DDIM_REVERSE>), grid, dim3(256), 0, st, fa, nullptr,
+                                   nullptr, mode);
+        } else if (pin_x0) {
+            hipLaunchKernelGGL(final_kernel<true>, dim3((n_nodes + 7) / 8), dim3(256), 0, st, fa, pin_x0, pin_mask, 0);
+        } else {
+            hipLaunchKernelGGL(final_kernel<false>, dim3((n_nodes + 7) / 8), dim3(256), 0, st, fa, nullptr, nullptr, 0);
+        }
     }
     return 0;
 }
@@ -951,6 +991,46 @@ extern "C" int codlad_sample_loop_pinned(const codlad_denoiser_weights *w, const
     return codlad_check_launch("codlad_sample_loop_pinned");
 }
 #undef SAMPLE_LOOP_REQUIRE
+
+extern "C" int codlad_ddim_loop(const codlad_denoiser_weights *w, const int32_t *node_info, int n_nodes,
+                                const int32_t *E_idx, const float *h_E0, const float *E1, int n_snodes, float *x,
+                                float *x_start, const float *noise, const float *mods, const float *coef, int T, int mode,
+                                int reverse, const float *pin_x0, const uint8_t *pin_mask, const codlad_workspace *ws,
+                                void *stream) {
+    CODLAD_REQUIRE(w && node_info && E_idx && h_E0 && x && mods && coef, "null pointer");
+    CODLAD_REQUIRE(reverse || noise, "null pointer (noise: only the reverse loop runs without it)");
+    CODLAD_REQUIRE(!pin_x0 == !pin_mask, "null pointer (pin_x0 and pin_mask come together)");
+    CODLAD_REQUIRE(n_nodes > 0 && T > 0, "n_nodes and T must be positive");
+    CODLAD_REQUIRE(mode >= 0 && mode <= (CODLAD_DDPM_START_X | CODLAD_DDPM_FIXED_VAR | CODLAD_DDPM_CLIP),
+                   "unknown mode bits");
+    CODLAD_REQUIRE(w->out_dim == ((mode & CODLAD_DDPM_FIXED_VAR) ? 3 : 6),
+                   "mode and model disagree: a learned-range sampler needs a model with 6 outputs (mean | variance "
+                   "logits), a fixed-variance one (mode bit 2) a model with 3");
+    CODLAD_REQUIRE(!w->self_condition || x_start, "a self-conditioned model needs the x_start buffer");
+    CODLAD_REQUIRE(check_ws(ws), "incomplete workspace");
+    sample_loop(w, node_info, n_nodes, E_idx, h_E0, E1, n_snodes, x, x_start, noise, mods, coef, T, pin_x0, pin_mask, ws,
+                stream, reverse ? CODLAD_STEP_DDIM_REVERSE : CODLAD_STEP_DDIM, mode);
+    return codlad_check_launch("codlad_ddim_loop");
+}
+
+extern "C" int codlad_ddim_step(const float *x, const float *pred_xstart, const float *noise, const float *grad,
+                                const float *coef_host, int reverse, int n_nodes, float *x_out, float *x_start_out,
+                                void *stream) {
+    CODLAD_REQUIRE(x && pred_xstart && coef_host && x_out, "null pointer");
+    CODLAD_REQUIRE(reverse || noise, "null pointer (noise: only the reverse step runs without it)");
+    CODLAD_REQUIRE(n_nodes > 0, "n_nodes must be positive");
+    DdpmCoef cf;
+    for (int k = 0; k < 8; ++k) cf.c[k] = coef_host[k];
+    const int mode = (int)coef_host[7];
+    const dim3 grid((n_nodes * 3 + 255) / 256);
+    if (reverse)
+        hipLaunchKernelGGL(ddim_update_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, x, pred_xstart, nullptr,
+                           grad, cf, mode, n_nodes, x_out, x_start_out);
+    else
+        hipLaunchKernelGGL(ddim_update_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, x, pred_xstart, noise,
+                           grad, cf, mode, n_nodes, x_out, x_start_out);
+    return codlad_check_launch("codlad_ddim_step");
+}
 
 extern "C" int codlad_status_check(int32_t *status, void *stream) {
     CODLAD_REQUIRE(status, "null pointer");

@@ -9,7 +9,10 @@ the whole loop is one `codlad_sample_loop` call; any other CUDA callable is step
 clamp and `cond_fn` adds variance * gradient to the posterior mean (gaussian_diffusion.py:335-349, 374-384); a
 `PinLatents` denoised_fn on the HIP model without cond_fn is fused into the loop (`codlad_sample_loop_pinned`), any
 other callable runs between the two halves of the split step (`codlad_ddpm_pred_xstart` /
-`codlad_ddpm_posterior_step`).  Training losses are out of scope.
+`codlad_ddpm_posterior_step`).  DDIM (the IDDPM release's `ddim_sample`, `ddim_reverse_sample`, `ddim_sample_loop`,
+`ddim_sample_loop_progressive`, with `eta`; `ddim_reverse_sample_loop` returns x_T) follows the same rule: the loop is
+one `codlad_ddim_loop` call for the HIP model with no hook or only a `PinLatents`, any other case steps through the
+model and `codlad_ddpm_pred_xstart` / `codlad_ddim_step`.  Training losses are out of scope.
 """
 import enum
 
@@ -101,6 +104,27 @@ class SpacedDiffusion(Tables):
                                                                                                       "learned_range")
         return self.step_variances(var)
 
+    def ddim_coefs(self, clip_denoised, eta=0.0, reverse=False):
+        """The [T, 8] DDIM table of the kernels for this sampler's branches (schedule.Tables.ddim_coefficients)."""
+        key = (bool(clip_denoised), float(eta), bool(reverse))
+        cache = self.__dict__.setdefault("_ddim_tables", {})
+        if key not in cache:
+            var = {ModelVarType.FIXED_SMALL: "fixed_small",
+                   ModelVarType.FIXED_LARGE: "fixed_large"}.get(self.model_var_type, "learned_range")
+            cache[key] = self.ddim_coefficients(eta=eta, reverse=reverse,
+                                                predict_xstart=self.model_mean_type is ModelMeanType.START_X,
+                                                var_type=var, clip_denoised=bool(clip_denoised))
+        return cache[key]
+
+    @staticmethod
+    def _check_eta(eta, reverse):
+        if not isinstance(eta, (int, float)) or isinstance(eta, bool):
+            raise TypeError(f"eta must be a number, got {type(eta).__name__}")
+        if eta < 0:
+            raise ValueError(f"eta must be >= 0, got {eta}")
+        if reverse and eta != 0:
+            raise ValueError(f"the reverse DDIM step is the deterministic ODE: eta must be 0, got {eta}")
+
     # ------------------------------------------------------------------------------------------
     @staticmethod
     def _hip_module(model):
@@ -143,6 +167,14 @@ class SpacedDiffusion(Tables):
         if not img.is_cuda:
             raise RuntimeError("p_sample_loop (codlad_amd) runs on the MI355X only")
         eps = step_noise if step_noise is not None else self._draw_noise(img)
+        job, pin = self._fused_job(mod, img, model_kwargs, denoised_fn if pinned else None)
+        T = self.num_timesteps
+        x0 = mod.engine().sample(job, img.reshape(-1, img.shape[-1]), eps.reshape(T, -1, img.shape[-1]), self,
+                                 coef=self.coefficients(clip_denoised), pin=pin)
+        return x0.view(img.shape)
+
+    def _fused_job(self, mod, img, model_kwargs, pin_fn):
+        """The engine job of a fused loop on `img` [N, L, C] and its pin arrays (pin_fn: a PinLatents or None)."""
         batch = model_kwargs["batch"]
         n_rep = img.shape[0] // int(batch["num_CGs"].shape[0])
         job, lens = mod.job_for(batch, n_rep)
@@ -153,16 +185,13 @@ class SpacedDiffusion(Tables):
         if len(set(lens)) != 1:
             raise NotImplementedError("fused loop on a padded mixed-length batch; pass equal-length "
                                       "structures per call (what the reference's loaders produce)")
-        T = self.num_timesteps
         pin = None
-        if pinned:
-            if tuple(denoised_fn.x0.shape) != tuple(img.shape) or not denoised_fn.x0.is_cuda:
+        if pin_fn is not None:
+            if tuple(pin_fn.x0.shape) != tuple(img.shape) or not pin_fn.x0.is_cuda:
                 raise ValueError(f"PinLatents: x0 must be a CUDA tensor of the sample's shape {tuple(img.shape)}, got "
-                                 f"{tuple(denoised_fn.x0.shape)} on {denoised_fn.x0.device}")
-            pin = (denoised_fn.x0.reshape(-1, img.shape[-1]), denoised_fn.mask.reshape(-1))
-        x0 = mod.engine().sample(job, img.reshape(-1, img.shape[-1]), eps.reshape(T, -1, img.shape[-1]), self,
-                                 coef=self.coefficients(clip_denoised), pin=pin)
-        return x0.view(img.shape)
+                                 f"{tuple(pin_fn.x0.shape)} on {pin_fn.x0.device}")
+            pin = (pin_fn.x0.reshape(-1, img.shape[-1]), pin_fn.mask.reshape(-1))
+        return job, pin
 
     def p_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
                                   cond_fn=None, model_kwargs=None, device=None, progress=False,
@@ -229,6 +258,166 @@ class SpacedDiffusion(Tables):
                                            _lib.ptr(out), _lib.ptr(x_start), _lib.stream_ptr(x.device))
         _lib.check(rc, "codlad_ddpm_update")
         return {"sample": out, "pred_xstart": x_start}
+
+    # -- DDIM -----------------------------------------------------------------------------------
+    def condition_score(self, cond_fn, p_mean_var, x, t, model_kwargs=None):
+        """gaussian_diffusion.py:386-402 (Song et al. 2020): what p_mean_variance would have returned had the model's
+        score been conditioned by cond_fn - eps from pred_xstart, eps -= sqrt(1 - acp) * grad, pred_xstart from eps, the
+        posterior mean of that.  cond_fn receives the original-process timesteps (respace.py:102-103).  On the device:
+        codlad_ddim_step's condition_score and codlad_ddpm_posterior_step's mean (no clamp, no noise)."""
+        if not callable(cond_fn):
+            raise TypeError(f"cond_fn must be callable, got {type(cond_fn).__name__}")
+        if not x.is_cuda:
+            raise RuntimeError("condition_score (codlad_amd) runs on the MI355X only")
+        from ..engine import Denoiser
+        i = int(t.reshape(-1)[0])
+        map_t = torch.tensor(self.timestep_map, device=t.device, dtype=t.dtype)[t]
+        grad = cond_fn(x, map_t, **(model_kwargs or {}))
+        _check_hook_output(grad, x, "cond_fn")
+        row = self.ddim_coefs(False)[i].copy()
+        row[7] = int(row[7]) & ~4                            # condition_score does not clamp again
+        zeros = torch.zeros_like(x)
+        _, pred = Denoiser.ddim_step(x, p_mean_var["pred_xstart"], zeros, row, grad=grad)
+        post = self.coefficients(False)[i].copy()
+        post[6] = 0.0                                        # the posterior mean alone
+        post[7] = 2                                          # fixed-variance row: model_out is not read for it
+        mean, _ = Denoiser.ddpm_posterior_step(x, pred, zeros, zeros, post)
+        out = dict(p_mean_var)
+        out["pred_xstart"] = pred.view(x.shape)
+        out["mean"] = mean.view(x.shape)
+        return out
+
+    def _ddim_step(self, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta, x_self_cond, noise,
+                   reverse):
+        """One DDIM step on the device: the model, the raw pred_xstart (codlad_ddpm_pred_xstart), denoised_fn, cond_fn's
+        gradient, then codlad_ddim_step (clamp, condition_score, eps, update)."""
+        self._check_args(clip_denoised, denoised_fn, cond_fn)
+        self._check_eta(eta, reverse)
+        if not x.is_cuda:
+            raise RuntimeError("ddim_sample (codlad_amd) runs on the MI355X only")
+        import numpy as np
+        from ..engine import Denoiser
+        i = int(t.reshape(-1)[0])
+        map_t = torch.tensor(self.timestep_map, device=t.device, dtype=t.dtype)[t]   # respace.py:124-129
+        kwargs = dict(model_kwargs or {})
+        if x_self_cond is not None:
+            kwargs["x_self_cond"] = x_self_cond
+        model_out = model(x, map_t, **kwargs)
+        C = x.shape[-1]
+        assert C == 3 and model_out.shape[-1] == (C if self.fixed_variance else 2 * C), \
+            "latent_size 3 only; a fixed-variance sampler takes a model without variance channels " \
+            "(gaussian_diffusion.py:303-306, 321-334)"
+        coef = np.ascontiguousarray(self.ddim_coefs(clip_denoised, eta, reverse)[i])
+        pred = Denoiser.ddpm_pred_xstart(x, model_out, coef).view(x.shape)
+        if denoised_fn is not None:
+            pred = denoised_fn(pred)
+            _check_hook_output(pred, x, "denoised_fn")
+        grad = None
+        if cond_fn is not None:
+            grad = cond_fn(x, map_t, **(model_kwargs or {}))
+            _check_hook_output(grad, x, "cond_fn")
+        if not reverse and noise is None:
+            noise = torch.randn_like(x)                  # drawn where the released ddim_sample draws it, also at eta = 0
+        sample, x_start = Denoiser.ddim_step(x, pred, None if reverse else noise, coef, grad=grad, reverse=reverse)
+        return {"sample": sample.view(x.shape), "pred_xstart": x_start.view(x.shape)}
+
+    def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, eta=0.0,
+                    x_self_cond=None, noise=None):
+        """x_{t-1} from x_t by DDIM: {"sample", "pred_xstart"}.  noise: this step's draw (None: randn_like(x))."""
+        return self._ddim_step(model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta, x_self_cond, noise,
+                               reverse=False)
+
+    def ddim_reverse_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
+                            eta=0.0, x_self_cond=None):
+        """x_{t+1} from x_t by the reverse DDIM ODE (eta must be 0): {"sample", "pred_xstart"}."""
+        return self._ddim_step(model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta, x_self_cond, None,
+                               reverse=True)
+
+    def _ddim_fusable(self, mod, denoised_fn, cond_fn):
+        return mod is not None and cond_fn is None and (denoised_fn is None or isinstance(denoised_fn, PinLatents))
+
+    def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
+                         model_kwargs=None, device=None, progress=False, eta=0.0, step_noise=None):
+        """Returns x_0 with `shape`, sampled by DDIM.  `step_noise` [T, *shape] as for p_sample_loop.  One randn_like(x)
+        is drawn per step at any eta, as the released ddim_sample does, on both paths."""
+        self._check_args(clip_denoised, denoised_fn, cond_fn)
+        self._check_eta(eta, False)
+        model_kwargs = model_kwargs or {}
+        mod = self._hip_module(model)
+        if not self._ddim_fusable(mod, denoised_fn, cond_fn):
+            final = None
+            for final in self.ddim_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
+                                                           denoised_fn=denoised_fn, cond_fn=cond_fn,
+                                                           model_kwargs=model_kwargs, device=device, eta=eta,
+                                                           step_noise=step_noise):
+                pass
+            return final["sample"]
+        if device is None:
+            device = next(mod.parameters()).device
+        img = noise if noise is not None else torch.randn(*shape, device=device)
+        if not img.is_cuda:
+            raise RuntimeError("ddim_sample_loop (codlad_amd) runs on the MI355X only")
+        eps = step_noise if step_noise is not None else self._draw_noise(img)
+        job, pin = self._fused_job(mod, img, model_kwargs, denoised_fn)
+        T = self.num_timesteps
+        x0 = mod.engine().sample(job, img.reshape(-1, img.shape[-1]), eps.reshape(T, -1, img.shape[-1]), self,
+                                 coef=self.ddim_coefs(clip_denoised, eta), pin=pin, kind="ddim")
+        return x0.view(img.shape)
+
+    def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
+                                     model_kwargs=None, device=None, progress=False, eta=0.0, step_noise=None):
+        """Generic DDIM stepping for any CUDA model callable; yields each step's {"sample", "pred_xstart"}."""
+        self._check_args(clip_denoised, denoised_fn, cond_fn)
+        self._check_eta(eta, False)
+        model_kwargs = model_kwargs or {}
+        img = noise if noise is not None else torch.randn(*shape, device=device)
+        x_start = None
+        for k, i in enumerate(range(self.num_timesteps - 1, -1, -1)):
+            t = torch.tensor([i] * shape[0], device=img.device)
+            out = self.ddim_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
+                                   model_kwargs=model_kwargs, eta=eta,
+                                   x_self_cond=x_start if self.self_condition else None,
+                                   noise=step_noise[k] if step_noise is not None else None)
+            yield out
+            img = out["sample"]
+            x_start = out["pred_xstart"]
+
+    def ddim_reverse_sample_loop(self, model, x, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
+                                 device=None, progress=False, eta=0.0):
+        """DDIM inversion: x_0 [N, L, C] -> x_T along the deterministic ODE (eta must be 0), steps i = 0 .. T-1.  The
+        HIP model with no hook or only a PinLatents runs fused (codlad_ddim_loop, reverse); anything else step by step."""
+        self._check_args(clip_denoised, denoised_fn, cond_fn)
+        self._check_eta(eta, True)
+        model_kwargs = model_kwargs or {}
+        mod = self._hip_module(model)
+        if not self._ddim_fusable(mod, denoised_fn, cond_fn):
+            final = None
+            for final in self.ddim_reverse_sample_loop_progressive(model, x, clip_denoised=clip_denoised,
+                                                                   denoised_fn=denoised_fn, cond_fn=cond_fn,
+                                                                   model_kwargs=model_kwargs, device=device, eta=eta):
+                pass
+            return final["sample"]
+        if not x.is_cuda:
+            raise RuntimeError("ddim_reverse_sample_loop (codlad_amd) runs on the MI355X only")
+        job, pin = self._fused_job(mod, x, model_kwargs, denoised_fn)
+        xT = mod.engine().sample(job, x.reshape(-1, x.shape[-1]), None, self, coef=self.ddim_coefs(clip_denoised, 0.0, True),
+                                 pin=pin, kind="ddim_reverse")
+        return xT.view(x.shape)
+
+    def ddim_reverse_sample_loop_progressive(self, model, x, clip_denoised=True, denoised_fn=None, cond_fn=None,
+                                             model_kwargs=None, device=None, progress=False, eta=0.0):
+        """Generic reverse DDIM stepping; yields each step's {"sample", "pred_xstart"} (the last sample is x_T)."""
+        self._check_args(clip_denoised, denoised_fn, cond_fn)
+        self._check_eta(eta, True)
+        img, x_start = x, None
+        for i in range(self.num_timesteps):
+            t = torch.tensor([i] * x.shape[0], device=img.device)
+            out = self.ddim_reverse_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
+                                           cond_fn=cond_fn, model_kwargs=model_kwargs, eta=eta,
+                                           x_self_cond=x_start if self.self_condition else None)
+            yield out
+            img = out["sample"]
+            x_start = out["pred_xstart"]
 
 
 def create_diffusion(timestep_respacing, noise_schedule="linear", use_kl=False, rescale_learned_sigmas=False,

@@ -1,4 +1,4 @@
-"""DDPM schedule tables for the sampler (host side, float64 numpy).
+"""DDPM / DDIM schedule tables for the sampler (host side, float64 numpy).
 
 Same quantities as the reference's GaussianDiffusion / SpacedDiffusion constructors
 (reference diffusion_and_flow/gaussian_diffusion.py:104-128,159-209; respace.py:12-62,73-87),
@@ -65,6 +65,7 @@ class Tables:
         alphas = 1.0 - betas
         self.alphas_cumprod = acp = np.cumprod(alphas, axis=0)
         self.alphas_cumprod_prev = prev = np.append(1.0, acp[:-1])
+        self.alphas_cumprod_next = np.append(acp[1:], 0.0)         # read by the reverse DDIM step only
         self.sqrt_recip_alphas_cumprod = np.sqrt(1.0 / acp)
         self.sqrt_recipm1_alphas_cumprod = np.sqrt(1.0 / acp - 1)
         self.posterior_variance = pv = betas * (1.0 - prev) / (1.0 - acp)
@@ -105,3 +106,41 @@ class Tables:
         if var_type not in ("learned_range", "learned"):
             raise ValueError(f"unknown variance type {var_type!r}")
         return np.zeros(self.num_timesteps, dtype=np.float32)
+
+    def ddim_coefficients(self, eta=0.0, reverse=False, predict_xstart=False, var_type="learned_range",
+                          clip_denoised=False):
+        """[T, 8] fp32 rows for codlad_ddim_loop / codlad_ddim_step: every schedule factor of the IDDPM release's
+        ddim_sample (ddim_reverse_sample with reverse=True) computed as it computes them - fp32 torch ops on the values
+        _extract_into_tensor yields (`.float()` of the float64 tables), in the formula's order - so that the kernels only
+        multiply and add: {sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod, sqrt(acp_prev), sqrt(1 - acp_prev -
+        sigma^2), nonzero * sigma, sqrt(1 - acp) (condition_score), 0, mode}, sigma = eta * sqrt((1 - acp_prev) / (1 -
+        acp)) * sqrt(1 - acp / acp_prev); reverse: {.., sqrt(acp_next), sqrt(1 - acp_next), 0, ..}.  Column 7 is the mode
+        word of step_coefficients (var_type only decides whether the model has variance channels: DDIM reads none)."""
+        import torch
+        eta = float(eta)
+        if eta < 0:
+            raise ValueError(f"eta must be >= 0, got {eta}")
+        if reverse and eta != 0.0:
+            raise ValueError(f"the reverse DDIM step is the deterministic ODE: eta must be 0, got {eta}")
+        if var_type not in ("fixed_small", "fixed_large", "learned_range", "learned"):
+            raise ValueError(f"unknown variance type {var_type!r}")
+        T = self.num_timesteps
+        f32 = lambda a: torch.from_numpy(np.asarray(a, dtype=np.float64)).float()   # noqa: E731  (_extract_into_tensor)
+        alpha_bar = f32(self.alphas_cumprod)
+        c = torch.zeros(T, 8, dtype=torch.float32)
+        c[:, 0] = f32(self.sqrt_recip_alphas_cumprod)
+        c[:, 1] = f32(self.sqrt_recipm1_alphas_cumprod)
+        if reverse:
+            alpha_bar_next = f32(self.alphas_cumprod_next)
+            c[:, 2] = torch.sqrt(alpha_bar_next)
+            c[:, 3] = torch.sqrt(1 - alpha_bar_next)
+        else:
+            alpha_bar_prev = f32(self.alphas_cumprod_prev)
+            sigma = eta * torch.sqrt((1 - alpha_bar_prev) / (1 - alpha_bar)) * torch.sqrt(1 - alpha_bar / alpha_bar_prev)
+            c[:, 2] = torch.sqrt(alpha_bar_prev)
+            c[:, 3] = torch.sqrt(1 - alpha_bar_prev - sigma ** 2)
+            nonzero_mask = (torch.arange(T) != 0).float()                 # no noise when t == 0
+            c[:, 4] = nonzero_mask * sigma
+        c[:, 5] = (1 - alpha_bar).sqrt()
+        c[:, 7] = (1 if predict_xstart else 0) + (2 if var_type.startswith("fixed") else 0) + (4 if clip_denoised else 0)
+        return c.numpy()

@@ -277,7 +277,9 @@ class Denoiser:
     # 8 700 +9.6 % (each half then takes the small-job node kernel), 5 220 -1.9 %, 3 480 +5.5 %, 1 740 -8 %.
     SPLIT_MIN_NODES = int(os.environ.get("CODLAD_SAMPLE_SPLIT_MIN_NODES", 8192))
 
-    def sample(self, job, x_T, noise, tables, check=True, coef=None, streams=None, pin=None):
+    SAMPLE_KINDS = ("ddpm", "ddim", "ddim_reverse")
+
+    def sample(self, job, x_T, noise, tables, check=True, coef=None, streams=None, pin=None, kind="ddpm"):
         """Full ancestral loop.  x_T [n_nodes,3]; noise [T,n_nodes,3] in loop order (first entry
         is used at step T-1); tables = diffusion_and_flow.schedule.Tables.  Returns x_0.
         check: after the loop, synchronise and raise if any step's output was not finite.
@@ -285,11 +287,21 @@ class Denoiser:
         streams: 1 = the whole job on the current stream; 2 = two half-jobs on two streams; None = 2 from
         SPLIT_MIN_NODES nodes up (and at least two samples).
         pin: (x0 [n_nodes,3], mask [n_nodes] bool / uint8 / int32) - residue pinning: at every step the pred_xstart of a
-        masked node is replaced by its x0 before the clamp (codlad_sample_loop_pinned)."""
-        _require_cuda(x_T, "x_T")
-        _require_cuda(noise, "noise")
+        masked node is replaced by its x0 before the clamp (codlad_sample_loop_pinned).
+        kind: "ddpm" (the ancestral loop above), "ddim" (the DDIM loop, codlad_ddim_loop; coef = a Tables.ddim_coefficients
+        table, default eta = 0) or "ddim_reverse" (DDIM inversion: x_T holds x_0, the result is x_T; noise must be None)."""
+        if kind not in self.SAMPLE_KINDS:
+            raise ValueError(f"kind must be one of {self.SAMPLE_KINDS}, got {kind!r}")
+        reverse = kind == "ddim_reverse"
         T = tables.num_timesteps
-        assert noise.shape == (T, job.n_nodes, 3) and x_T.shape == (job.n_nodes, 3)
+        _require_cuda(x_T, "x_T")
+        if reverse:
+            if noise is not None:
+                raise ValueError("the reverse DDIM loop is deterministic: noise must be None")
+        else:
+            _require_cuda(noise, "noise")
+            assert noise.shape == (T, job.n_nodes, 3)
+        assert x_T.shape == (job.n_nodes, 3)
         if pin is not None:
             pin = self._pin_arrays(pin, job.n_nodes)
         if streams is None:
@@ -297,26 +309,38 @@ class Denoiser:
         if streams > 1:
             parts = job.parts(streams)
             pins = None if pin is None else [(pin[0][i], pin[1][i]) for _p, i in parts]
-            outs = self.sample_many([p for p, _i in parts], [x_T[i] for _p, i in parts], [noise[:, i] for _p, i in parts],
-                                    tables, check=check, coef=coef, pins=pins)
+            noises = [None if reverse else noise[:, i] for _p, i in parts]
+            outs = self.sample_many([p for p, _i in parts], [x_T[i] for _p, i in parts], noises,
+                                    tables, check=check, coef=coef, pins=pins, kind=kind)
             x0 = torch.empty(job.n_nodes, 3, dtype=torch.float32, device=self.device)
             for (_p, i), o in zip(parts, outs):
                 x0[i] = o
             return x0
-        coef = tables.step_coefficients() if coef is None else coef
+        if coef is None:
+            coef = tables.step_coefficients() if kind == "ddpm" else tables.ddim_coefficients(reverse=reverse)
         fixed_var = bool(int(coef[0, 7]) & 2)
         if self.weights.out_dim != (3 if fixed_var else 6):
-            raise ValueError("the DDPM loop needs a model with 6 outputs (mean | variance logits), or 3 with a fixed-variance "
-                             "sampler (create_diffusion(learn_sigma=False)); a flow-matching model is sampled with "
-                             "codlad_amd.diffusion_and_flow.ode.odeint")
+            raise ValueError(f"the {kind.upper()} loop needs a model with 6 outputs (mean | variance logits), or 3 with a "
+                             "fixed-variance sampler (create_diffusion(learn_sigma=False)); a flow-matching model is sampled "
+                             "with codlad_amd.diffusion_and_flow.ode.odeint")
         x = x_T.detach().clone().contiguous().float()
-        noise = noise.contiguous().float()
+        noise = None if reverse else noise.contiguous().float()
         mods = self.step_mods(tables.timestep_map)
+        mode = int(coef[0, 7])                                  # the host's mode word (codlad_ddim_loop checks it)
         coef = torch.from_numpy(coef).to(self.device)
         st = job.structures
         self._fresh_features(st)
         x_start = torch.empty_like(x) if self.self_condition else None   # pred_xstart, step to step
-        if pin is None:
+        if kind != "ddpm":
+            rc = self.lib.codlad_ddim_loop(C.byref(self.weights.struct), _lib.ptr(job.node_info), job.n_nodes,
+                                           _lib.ptr(st.E_idx), _lib.ptr(st.h_E0), _lib.ptr(st.E1), st.n_snodes,
+                                           _lib.ptr(x), _lib.ptr(x_start), _lib.ptr(noise), _lib.ptr(mods),
+                                           _lib.ptr(coef), T, mode, int(reverse),
+                                           _lib.ptr(None if pin is None else pin[0]),
+                                           _lib.ptr(None if pin is None else pin[1]), C.byref(job.ws),
+                                           _lib.stream_ptr(self.device))
+            _lib.check(rc, "codlad_ddim_loop")
+        elif pin is None:
             rc = self.lib.codlad_sample_loop(C.byref(self.weights.struct), _lib.ptr(job.node_info),
                                              job.n_nodes, _lib.ptr(st.E_idx), _lib.ptr(st.h_E0),
                                              _lib.ptr(st.E1), st.n_snodes, _lib.ptr(x), _lib.ptr(x_start),
@@ -335,12 +359,13 @@ class Denoiser:
             self.check_status(job)
         return x
 
-    def sample_many(self, jobs, x_Ts, noises, tables, check=True, coef=None, pins=None):
+    def sample_many(self, jobs, x_Ts, noises, tables, check=True, coef=None, pins=None, kind="ddpm"):
         """Several independent jobs at once, each on its own HIP stream: the node kernel of a 35 000-node job occupies 139 of
         the 256 CUs and every kernel has a tail - with a second job in flight another job's edge kernels run there (two
         half-jobs of BASELINE configuration 2: 1.03 x; more than two parts lose).  Every job carries its
         own workspace and the library keeps no state between jobs, so the results are those of `sample` job by job.
-        pins: None, or one `pin` of `sample` (or None) per job."""
+        pins: None, or one `pin` of `sample` (or None) per job.  kind as for `sample` (noises: None per job for
+        "ddim_reverse")."""
         pins = [None] * len(jobs) if pins is None else list(pins)
         assert len(pins) == len(jobs)
         if not hasattr(self, "_streams"):
@@ -357,7 +382,7 @@ class Denoiser:
                 pin = self._pin_arrays(pin, job.n_nodes)         # (copies on the caller's stream)
             st.wait_stream(cur)
             with torch.cuda.stream(st):
-                outs.append(self.sample(job, x_T, noise, tables, check=False, coef=coef, streams=1, pin=pin))
+                outs.append(self.sample(job, x_T, noise, tables, check=False, coef=coef, streams=1, pin=pin, kind=kind))
         for st in self._streams[:len(jobs)]:
             cur.wait_stream(st)
         if check:
@@ -430,6 +455,27 @@ class Denoiser:
                                                    x.numel() // 3, _lib.ptr(out), _lib.ptr(x_start),
                                                    _lib.stream_ptr(x.device))
         _lib.check(rc, "codlad_ddpm_posterior_step")
+        return out, x_start
+
+    @staticmethod
+    def ddim_step(x, pred_xstart, noise, coef, grad=None, reverse=False):
+        """One DDIM update given a (processed) pred_xstart: clamp (mode bit 4), condition_score with grad (cond_fn), eps
+        from pred_xstart, then the forward update with noise or the reverse one (noise None) -> (sample, the pred_xstart
+        the step used) (codlad_ddim_step).  coef = one [8] row of Tables.ddim_coefficients."""
+        _require_cuda(x, "x")
+        x = x.contiguous().float()
+        out = torch.empty_like(x)
+        x_start = torch.empty_like(x)
+        coef = np.ascontiguousarray(coef, dtype=np.float32)
+        if reverse != (noise is None):
+            raise ValueError("the forward DDIM step takes noise, the reverse one none")
+        nz = None if noise is None else noise.contiguous().float()
+        g = None if grad is None else grad.contiguous().float()
+        _check_step_operands(x, None, coef, pred_xstart=pred_xstart, noise=nz, grad=g)
+        rc = _lib.lib().codlad_ddim_step(_lib.ptr(x), _lib.ptr(pred_xstart.contiguous().float()), _lib.ptr(nz),
+                                         _lib.ptr(g), coef.ctypes.data_as(C.c_void_p), int(bool(reverse)),
+                                         x.numel() // 3, _lib.ptr(out), _lib.ptr(x_start), _lib.stream_ptr(x.device))
+        _lib.check(rc, "codlad_ddim_step")
         return out, x_start
 
 

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define CODLAD_ABI_VERSION 14
+#define CODLAD_ABI_VERSION 15
 #define CODLAD_H 128          /* hidden width of the denoiser                          */
 #define CODLAD_KNN 64         /* k_neighbors (reference models/latent_model.py:86)      */
 #define CODLAD_MODS_PER_STEP 6016 /* 3*9*128 (enc) + 3*6*128 (dec) + 2*128 (final)      */
@@ -274,6 +274,37 @@ int codlad_sample_loop_pinned(const codlad_denoiser_weights *w, const int32_t *n
                               float *x, float *x_start, const float *noise, const float *mods, const float *coef,
                               int T, const float *pin_x0, const uint8_t *pin_mask, const codlad_workspace *ws,
                               void *stream);
+
+/* DDIM (Song et al. 2021; the IDDPM release's ddim_sample_loop / ddim_reverse_sample_loop over the same respaced tables).
+ * coef [T][8] (device) and coef_host[8] are rows of Tables.ddim_coefficients, every schedule factor in fp32 as the
+ * reference extracts it: {sqrt_recip_acp, sqrt_recipm1_acp, sqrt(acp_prev), sqrt(1 - acp_prev - sigma^2),
+ * nonzero * sigma, sqrt(1 - acp), unused, mode}, sigma = eta * sqrt((1 - acp_prev) / (1 - acp)) * sqrt(1 - acp / acp_prev);
+ * the reverse rows hold sqrt(acp_next), sqrt(1 - acp_next) and 0 in columns 2-4.  mode bits as for codlad_ddpm_update:
+ * 1 = x_0 prediction, 2 = fixed variance (DDIM reads no variance; the bit says the model has 3 outputs, not 6),
+ * 4 = clip_denoised.  A step: pred_xstart = raw x_0 prediction -> pin -> clamp (bit 4); eps = (sqrt_recip_acp * x -
+ * pred_xstart) / sqrt_recipm1_acp; x = pred_xstart * col2 + col3 * eps (+ col4 * noise, forward only).
+ *
+ * codlad_ddim_loop: the whole loop fused, as codlad_sample_loop.  reverse = 0: x holds x_T on entry and x_0 on return,
+ *   i = T-1 .. 0, noise [T][n_nodes][3] consumed in loop order.  reverse != 0: x holds x_0 on entry and x_T on return
+ *   (DDIM inversion, eta = 0), i = 0 .. T-1, noise is not read and may be NULL.  mode is the host's: it must agree with
+ *   the model (6 outputs without bit 2, 3 with it); column 7 of coef is not read.  pin_x0 / pin_mask (both NULL, or
+ *   both given) as for codlad_sample_loop_pinned.  x_start [n_nodes][3] carries pred_xstart step to step (required for a
+ *   self-conditioned model; step k reads step k-1's, the first step none). */
+int codlad_ddim_loop(const codlad_denoiser_weights *w, const int32_t *node_info, int n_nodes, const int32_t *E_idx,
+                     const float *h_E0, const float *E1, int n_snodes, float *x, float *x_start,
+                     const float *noise /* NULL iff reverse */, const float *mods, const float *coef, int T, int mode,
+                     int reverse, const float *pin_x0 /* may be NULL */, const uint8_t *pin_mask /* may be NULL */,
+                     const codlad_workspace *ws, void *stream);
+
+/* codlad_ddim_step: one DDIM update after a caller's denoised_fn / cond_fn, given the processed pred_xstart
+ *   [n_nodes][3] (codlad_ddpm_pred_xstart gives the raw one; the two round like one fused step): bit 4 of
+ *   coef_host[7] clamps it; grad [n_nodes][3] (may be NULL = no cond_fn) applies condition_score
+ *   (eps -= sqrt(1 - acp) * grad, pred_xstart from eps); then the update above, forward (reverse = 0, with noise) or
+ *   reverse (noise not read, may be NULL).  x_start_out (may be NULL) receives the pred_xstart the step used.
+ *   x_out may alias x, x_start_out may alias pred_xstart. */
+int codlad_ddim_step(const float *x, const float *pred_xstart, const float *noise /* NULL iff reverse */,
+                     const float *grad /* may be NULL */, const float *coef_host, int reverse, int n_nodes, float *x_out,
+                     float *x_start_out /* may be NULL */, void *stream);
 
 /* Row 8: get_norm_feature(norm_in=False) + nearest code
  * (utils/dataset_module.py:253; utils/vq_module.py:61-68 / VectorQuantize eval lookup).

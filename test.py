@@ -14,6 +14,7 @@ Data: `--pdb_files ens.pdb ...` (multi-model PDB ensembles -> the reference's lo
 them) or `--synthetic` (no PED/PDB/Atlas files ship with the reference).
 Addition: `--fix_residues SPEC` keeps the VQ-VAE encoder's latents of the chosen residues (residue pinning, a
 `PinLatents` denoised_fn) and samples the rest of each structure conditioned on them.
+Addition: `--sampler ddim [--eta E]` samples the latents with DDIM (ddim_sample_loop) instead of the ancestral DDPM loop.
 """
 import argparse
 import os
@@ -101,6 +102,25 @@ def check_fix_residues(args):
         return parse_fix_residues(args.fix_residues)
     except ValueError as e:
         raise SystemExit(str(e))
+
+
+def check_sampler(args):
+    """--sampler / --eta: DDIM applies to latent sampling with the diffusion model; a nonzero eta is a DDIM setting."""
+    sampler, eta = getattr(args, "sampler", "ddpm"), getattr(args, "eta", 0.0)
+    if sampler not in ("ddpm", "ddim"):
+        raise SystemExit(f"--sampler must be ddpm or ddim, not {sampler!r}")
+    if eta < 0:
+        raise SystemExit(f"--eta must be >= 0, got {eta}")
+    if sampler == "ddpm":
+        if eta != 0:
+            raise SystemExit("--eta applies to --sampler ddim only (the DDPM sampler has no eta)")
+        return
+    if args.experiment != "latent":
+        raise SystemExit(f"--sampler ddim samples latents: it needs --experiment latent, not {args.experiment!r} "
+                         "(recon encodes the input, genzprot samples the conditional prior)")
+    if args.model != "diffusion":
+        raise SystemExit(f"--sampler ddim needs --model diffusion: {args.model!r} is a flow-matching model, sampled by "
+                         "its ODE solver")
 
 
 def load_vae(args, device, load=True):
@@ -262,6 +282,7 @@ def run_sampling(model, args, x, mask=None, batch=None):
 
 
 def main(args):
+    check_sampler(args)
     if not torch.cuda.is_available():
         raise SystemExit("test.py (codlad_amd) needs an MI355X: there is no CPU path")
     # one process per GPU under torch.distributed.run: batches (independent units) are dealt to the
@@ -343,9 +364,14 @@ def main(args):
                     known = get_norm_feature(vae.get_latent_wovq(batch)[0], args.vae_type, norm_channel=args.norm,
                                              norm_single=args.norm_single, norm_in=True, dataname=args.data_type)
                     pin = PinLatents(known.repeat(E, 1, 1).contiguous(), fix_residue_mask(fixed, L, B * E, device))
-                samples = diffusion.p_sample_loop(model.forward, z.shape, z, clip_denoised=False, denoised_fn=pin,
-                                                  model_kwargs=dict(y=None, mask=mask, batch=rep), device=device,
-                                                  step_noise=diffusion._draw_noise(z, generator=gen))
+                if args.sampler == "ddim":
+                    samples = diffusion.ddim_sample_loop(model.forward, z.shape, z, clip_denoised=False, denoised_fn=pin,
+                                                         model_kwargs=dict(y=None, mask=mask, batch=rep), device=device,
+                                                         eta=args.eta, step_noise=diffusion._draw_noise(z, generator=gen))
+                else:
+                    samples = diffusion.p_sample_loop(model.forward, z.shape, z, clip_denoised=False, denoised_fn=pin,
+                                                      model_kwargs=dict(y=None, mask=mask, batch=rep), device=device,
+                                                      step_noise=diffusion._draw_noise(z, generator=gen))
             else:                                               # --model fm / icfm / otcfm ...: ODE sampling
                 samples = run_sampling(model, args, z, mask=mask, batch=rep)
             samples = get_norm_feature(samples, args.vae_type, norm_channel=args.norm, norm_single=args.norm_single,
@@ -448,4 +474,9 @@ if __name__ == "__main__":
                    help="keep the latents of these residues (1-based CG positions, flanking caps excluded, e.g. 3-20,41) "
                         "as the VQ-VAE encodes them from the input's atoms and sample the rest conditioned on them "
                         "(--experiment latent --model diffusion, VQ-VAE N6 / K3 / K4)")
+    p.add_argument("--sampler", default="ddpm", choices=["ddpm", "ddim"],
+                   help="latent sampler of --model diffusion: the ancestral DDPM loop (default) or DDIM over the same "
+                        "--num_sampling_steps respacing")
+    p.add_argument("--eta", type=float, default=0.0,
+                   help="DDIM noise scale (0 = the deterministic sampler, 1 = the DDPM posterior variance); --sampler ddim only")
     main(p.parse_args())

@@ -588,12 +588,9 @@ def g16_sampler_branches(ref, model):
         save(f"g16_sampler_{name}", sample=traj[-1], traj=torch.stack(traj))
 
 
-def g17_guidance(ref, model):
-    """Guided sampling: the reference's own loop with a denoised_fn (residue pinning, a generic map) and / or a cond_fn
-    (gaussian_diffusion.py:335-349, 374-384, 436-446; respace.py:99-100, 117-129), the cases and hooks of
-    tests/guidance_cases.py."""
-    from tests import guidance_cases as gc
-    print("g17 guidance (denoised_fn / cond_fn)")
+def guidance_models(ref, model):
+    """The reference denoisers of the g17 / g18 cases: "eps" (6 outputs), "selfcond" (built with self_condition),
+    "three" (the 3-output head a fixed-variance sampler takes), all with the seeded weights of cases.WEIGHT_SEED."""
     models = {"eps": model}
     sc = ref["MPNN_models"]["mpnn_diffusion"](input_size=3, unconditional=True, diffusion="diffusion", self_condition=True)
     sc.load_state_dict(synth.denoiser_state_dict(cases.WEIGHT_SEED, self_condition=True), strict=True)
@@ -601,6 +598,16 @@ def g17_guidance(ref, model):
     three = ref["MPNN_models"]["mpnn_diffusion"](input_size=3, unconditional=True, diffusion="fm", self_condition=False)
     three.load_state_dict(synth.denoiser_state_dict(cases.WEIGHT_SEED, flow=True), strict=True)
     models["three"] = three.eval()
+    return models
+
+
+def g17_guidance(ref, model):
+    """Guided sampling: the reference's own loop with a denoised_fn (residue pinning, a generic map) and / or a cond_fn
+    (gaussian_diffusion.py:335-349, 374-384, 436-446; respace.py:99-100, 117-129), the cases and hooks of
+    tests/guidance_cases.py."""
+    from tests import guidance_cases as gc
+    print("g17 guidance (denoised_fn / cond_fn)")
+    models = guidance_models(ref, model)
     for name, (L, B, seed, kw, clip, kind, _hooks) in gc.GUIDANCE_CASES.items():
         prot, batch, _x, _t, mask = cases.denoiser_inputs(L, B, seed)
         z, eps = cases.loop_noise(gc.T, B, L, seed)
@@ -612,6 +619,86 @@ def g17_guidance(ref, model):
         if cond_fn is not None:
             arrays["cond_timesteps"] = np.array(cond_fn.timesteps)      # what the reference hands cond_fn: mapped t
         save(f"g17_guidance_{name}", **arrays)
+
+
+def run_ddim_loop(ref, model, z, eps, mask, batch, reverse=False, eta=0.0, self_condition=False, clip_denoised=False,
+                  denoised_fn=None, cond_fn=None, respacing="10", **diffusion_kwargs):
+    """DDIM sampling (reverse=False, from x_T = z) or inversion (reverse=True, from x_0 = z) with the reference's own
+    SpacedDiffusion for everything but the update: p_mean_variance through its respacing wrapper (model, clamp,
+    denoised_fn), condition_score (cond_fn sees the mapped t), _predict_eps_from_xstart and the fp32 schedule values
+    (_extract_into_tensor).  The reference has no DDIM step: the sigma / mean / sample lines below are RESTATED from the
+    IDDPM release's ddim_sample / ddim_reverse_sample.  Self-conditioning as the reference's p_sample_loop_progressive
+    (gaussian_diffusion.py:530-547).  -> per-step samples, per-step pred_xstart, per-step coefficient rows [6]."""
+    import diffusion_and_flow.gaussian_diffusion as gd
+    ext = gd._extract_into_tensor
+    kw = dict(noise_schedule="linear", predict_xstart=False, rescale_learned_sigmas=False, self_condition=self_condition)
+    kw.update(diffusion_kwargs)
+    d = ref["create_diffusion"](respacing, **kw)
+    T = d.num_timesteps
+    feeder = NoiseFeeder(eps)
+    orig = gd.th.randn_like
+    gd.th.randn_like = feeder
+    model_kwargs = dict(y=None, mask=mask, batch=batch)
+    traj, preds, coefs = [], [], []
+    try:
+        img, x_start = z, None
+        for i in (range(T) if reverse else range(T - 1, -1, -1)):
+            t = torch.tensor([i] * z.shape[0])
+            out = d.p_mean_variance(model.forward, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
+                                    model_kwargs=model_kwargs, x_self_cond=x_start if self_condition else None)
+            if cond_fn is not None:
+                out = d.condition_score(cond_fn, out, img, t, model_kwargs=model_kwargs)
+            e = d._predict_eps_from_xstart(img, t, out["pred_xstart"])
+            alpha_bar = ext(d.alphas_cumprod, t, img.shape)
+            row = [ext(d.sqrt_recip_alphas_cumprod, t, img.shape), ext(d.sqrt_recipm1_alphas_cumprod, t, img.shape)]
+            # ---- restated: the IDDPM release's ddim_reverse_sample / ddim_sample (eta, Equation 12) ----
+            if reverse:
+                alpha_bar_next = ext(d.alphas_cumprod_next, t, img.shape)
+                sample = out["pred_xstart"] * torch.sqrt(alpha_bar_next) + torch.sqrt(1 - alpha_bar_next) * e
+                row += [torch.sqrt(alpha_bar_next), torch.sqrt(1 - alpha_bar_next), torch.zeros_like(alpha_bar)]
+            else:
+                alpha_bar_prev = ext(d.alphas_cumprod_prev, t, img.shape)
+                sigma = eta * torch.sqrt((1 - alpha_bar_prev) / (1 - alpha_bar)) * torch.sqrt(1 - alpha_bar / alpha_bar_prev)
+                noise = gd.th.randn_like(img)
+                mean_pred = out["pred_xstart"] * torch.sqrt(alpha_bar_prev) + torch.sqrt(1 - alpha_bar_prev - sigma ** 2) * e
+                nonzero_mask = (t != 0).float().view(-1, *([1] * (len(img.shape) - 1)))
+                sample = mean_pred + nonzero_mask * sigma * noise
+                row += [torch.sqrt(alpha_bar_prev), torch.sqrt(1 - alpha_bar_prev - sigma ** 2), nonzero_mask * sigma]
+            # ---- end of the restated lines ----
+            row.append((1 - alpha_bar).sqrt())                   # condition_score's factor (gaussian_diffusion.py:397)
+            coefs.append(torch.stack([r.reshape(-1)[0] for r in row]))
+            traj.append(sample)
+            preds.append(out["pred_xstart"])
+            img, x_start = sample, out["pred_xstart"]
+    finally:
+        gd.th.randn_like = orig
+    assert feeder.k == (0 if reverse else T)
+    return traj, preds, coefs, d.timestep_map
+
+
+def g18_ddim(ref, model):
+    """DDIM sampling and inversion (tests/ddim_cases.py): the reference's p_mean_variance / condition_score /
+    _predict_eps_from_xstart and schedule values, the DDIM update restated (run_ddim_loop)."""
+    from tests import ddim_cases as dc
+    print("g18 DDIM sampling / inversion")
+    models = guidance_models(ref, model)
+    for name, (reverse, L, B, seed, respacing, kw, eta, clip, kind, _hooks) in dc.DDIM_CASES.items():
+        prot, batch, _x, _t, mask = cases.denoiser_inputs(L, B, seed)
+        z, eps = cases.loop_noise(dc.T, B, L, seed)
+        denoised_fn, cond_fn = dc.hooks_for(name)
+        kw = dict(kw)
+        traj, preds, coefs, tmap = run_ddim_loop(ref, models[kind], z, eps, mask, batch, reverse=reverse, eta=eta,
+                                                 self_condition=kw.pop("self_condition", False), clip_denoised=clip,
+                                                 denoised_fn=denoised_fn, cond_fn=cond_fn, respacing=respacing, **kw)
+        steps = list(range(dc.T)) if reverse else list(range(dc.T - 1, -1, -1))
+        coef = torch.zeros(dc.T, 6)
+        for i, row in zip(steps, coefs):
+            coef[i] = row                                       # indexed by respaced step, as the kernels' tables
+        arrays = dict(sample=traj[-1], traj=torch.stack(traj), pred_xstart=torch.stack(preds), coef=coef,
+                      timestep_map=np.array(tmap))
+        if cond_fn is not None:
+            arrays["cond_timesteps"] = np.array(cond_fn.timesteps)      # what the reference hands cond_fn: mapped t
+        save(f"g18_ddim_{name}", **arrays)
 
 
 def g15_e3nn_encoder_prior(ref):
@@ -702,6 +789,7 @@ def main():
     if want("g15"): g15_e3nn_encoder_prior(ref)
     if want("g16"): g16_sampler_branches(ref, model)
     if want("g17"): g17_guidance(ref, model)
+    if want("g18"): g18_ddim(ref, model)
 
 
 if __name__ == "__main__":
