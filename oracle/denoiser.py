@@ -27,36 +27,40 @@ def gather_edges(edges, E_idx):
     return torch.gather(edges, 2, E_idx.unsqueeze(-1).expand(-1, -1, -1, edges.shape[-1]))
 
 
-def timestep_embedding(t, dim=256, max_period=10000):
-    """latent_model.py:51-70."""
+def timestep_embedding(t, dim=256, max_period=10000, dtype=torch.float32):
+    """latent_model.py:51-70.  `dtype`: the reference's fp32, or float64 for a float64 forward."""
     half = dim // 2
-    freqs = torch.exp(-math.log(max_period) * torch.arange(half, dtype=torch.float32) / half)
-    args = t[:, None].float() * freqs[None]
+    freqs = torch.exp(-math.log(max_period) * torch.arange(half, dtype=dtype) / half)
+    args = t[:, None].to(dtype) * freqs[None]
     return torch.cat([torch.cos(args), torch.sin(args)], dim=-1)
 
 
 def t_embed(sd, t):
     """latent_model.py:72-75: Linear -> SiLU -> Linear."""
-    h = _lin(sd, "t_embedder.mlp.0", timestep_embedding(t))
+    w = sd["t_embedder.mlp.0.weight"]
+    h = _lin(sd, "t_embedder.mlp.0", timestep_embedding(t, dtype=w.dtype))
     return _lin(sd, "t_embedder.mlp.2", F.silu(h))
 
 
 # ----------------------------------------------------------------------------------------------
 # CA features
 # ----------------------------------------------------------------------------------------------
-def knn(X, mask, top_k=64, eps=1e-6):
-    """protein_mpnn_utils.py:447-459."""
+def _knn_distances(X, mask, eps=1e-6):
     mask_2D = mask[:, None, :] * mask[:, :, None]
     dX = X[:, None, :, :] - X[:, :, None, :]
     D = mask_2D * torch.sqrt(torch.sum(dX ** 2, 3) + eps)
     D_max, _ = torch.max(D, -1, keepdim=True)
-    D_adjust = D + (1.0 - mask_2D) * D_max
-    return torch.topk(D_adjust, min(top_k, X.shape[1]), dim=-1, largest=False)
+    return D + (1.0 - mask_2D) * D_max
+
+
+def knn(X, mask, top_k=64, eps=1e-6):
+    """protein_mpnn_utils.py:447-459."""
+    return torch.topk(_knn_distances(X, mask, eps), min(top_k, X.shape[1]), dim=-1, largest=False)
 
 
 def _rbf(D):
     """protein_mpnn_utils.py:461-470: 16 Gaussians, centres linspace(2, 22), width 1.25."""
-    mu = torch.linspace(2.0, 22.0, 16).view(1, 1, 1, -1)
+    mu = torch.linspace(2.0, 22.0, 16, dtype=D.dtype).view(1, 1, 1, -1)
     return torch.exp(-((D.unsqueeze(-1) - mu) / ((22.0 - 2.0) / 16)) ** 2)
 
 
@@ -99,10 +103,23 @@ def orientation_features(X, E_idx):
     return torch.cat((dU, _quaternions(R)), dim=-1)
 
 
-def ca_features(sd, Ca, mask, top_k=64):
-    """protein_mpnn_utils.py:478-523 -> E [N,L,K,128] (before W_e), E_idx [N,L,K]."""
-    maskf = mask.float()
-    D_nb, E_idx = knn(Ca, maskf, top_k)
+def embed_edges(sd, E_raw):
+    """protein_mpnn_utils.py:519-521: raw edge features [..., 167] (16 positional | 9 x 16 RBF | 3 direction |
+    4 quaternion) -> edge_embedding -> norm_edges."""
+    E = F.linear(E_raw, sd["features.edge_embedding.weight"])
+    return F.layer_norm(E, (E.shape[-1],), sd["features.norm_edges.weight"], sd["features.norm_edges.bias"], 1e-5)
+
+
+def ca_features(sd, Ca, mask, top_k=64, E_idx=None, taps=None):
+    """protein_mpnn_utils.py:478-523 -> E [N,L,K,128] (before W_e), E_idx [N,L,K].  `E_idx` given: the features of
+    those neighbours in that order instead of the k-NN selection's (for tests that compare edge by edge with
+    another evaluation, whose tied distances may have come out in another order); `taps` receives "E_raw", the
+    raw features that `embed_edges` takes."""
+    maskf = mask.to(Ca.dtype)
+    if E_idx is None:
+        D_nb, E_idx = knn(Ca, maskf, top_k)
+    else:
+        D_nb = torch.gather(_knn_distances(Ca, maskf), 2, E_idx)
     Ca_0 = torch.zeros_like(Ca)
     Ca_2 = torch.zeros_like(Ca)
     Ca_0[:, 1:, :] = Ca[:, :-1, :]
@@ -118,12 +135,11 @@ def ca_features(sd, Ca, mask, top_k=64):
     offset = (ridx[:, None] - ridx[None, :])[None, :, :, None].expand(Ca.shape[0], -1, -1, -1)
     offset = gather_edges(offset, E_idx)[..., 0]
     d = torch.clip(offset + 32, 0, 64)  # same chain everywhere (latent_model.py:201)
-    E_pos = _lin(sd, "features.embeddings.linear", F.one_hot(d, 66).float())
+    E_pos = _lin(sd, "features.embeddings.linear", F.one_hot(d, 66).to(Ca.dtype))
     E = torch.cat((E_pos, rbf, O_feat), -1)
-    E = F.linear(E, sd["features.edge_embedding.weight"])
-    E = F.layer_norm(E, (E.shape[-1],), sd["features.norm_edges.weight"],
-                     sd["features.norm_edges.bias"], 1e-5)
-    return E, E_idx
+    if taps is not None:
+        taps["E_raw"] = E
+    return embed_edges(sd, E), E_idx
 
 
 # ----------------------------------------------------------------------------------------------
@@ -146,10 +162,14 @@ def _ffn(sd, p, x):
     return _lin(sd, f"{p}.dense.W_out", F.gelu(_lin(sd, f"{p}.dense.W_in", x)))
 
 
-def enc_layer(sd, p, h_V, h_E, E_idx, mask_V, mask_attend, c, scale=30.0):
+def _adaln(sd, p, c, mod):
+    """The adaLN vectors of head `p`: its Linear on SiLU(c), or `mod` [N, n] given in their place."""
+    return _lin(sd, f"{p}.adaLN_modulation.1", F.silu(c)) if mod is None else mod
+
+
+def enc_layer(sd, p, h_V, h_E, E_idx, mask_V, mask_attend, c, scale=30.0, mod=None):
     """protein_mpnn_utils.py:236-271."""
-    sh1, sc1, g1, sh2, sc2, g2, sh3, sc3, g3 = _lin(sd, f"{p}.adaLN_modulation.1",
-                                                    F.silu(c)).chunk(9, dim=1)
+    sh1, sc1, g1, sh2, sc2, g2, sh3, sc3, g3 = _adaln(sd, p, c, mod).chunk(9, dim=1)
     K = E_idx.shape[-1]
     h_EV = torch.cat([h_V.unsqueeze(-2).expand(-1, -1, K, -1), h_E, gather_nodes(h_V, E_idx)], -1)
     msg = _mlp3(sd, p, ("W1", "W2", "W3"), h_EV)
@@ -166,10 +186,10 @@ def enc_layer(sd, p, h_V, h_E, E_idx, mask_V, mask_attend, c, scale=30.0):
     return h_V, h_E
 
 
-def dec_layer(sd, p, h_V, h_ESV, mask_V, c, scale=30.0):
+def dec_layer(sd, p, h_V, h_ESV, mask_V, c, scale=30.0, mod=None):
     """protein_mpnn_utils.py:296-318 with mask_attend=None (latent_model.py:262): the sum runs
     over all K neighbours, padded ones included."""
-    sh1, sc1, g1, sh2, sc2, g2 = _lin(sd, f"{p}.adaLN_modulation.1", F.silu(c)).chunk(6, dim=1)
+    sh1, sc1, g1, sh2, sc2, g2 = _adaln(sd, p, c, mod).chunk(6, dim=1)
     K = h_ESV.shape[-2]
     h_EV = torch.cat([h_V.unsqueeze(-2).expand(-1, -1, K, -1), h_ESV], -1)
     msg = _mlp3(sd, p, ("W1", "W2", "W3"), h_EV)
@@ -180,32 +200,58 @@ def dec_layer(sd, p, h_V, h_ESV, mask_V, c, scale=30.0):
     return mask_V.unsqueeze(-1) * h_V
 
 
-def final_layer(sd, h_V, c):
+def final_layer(sd, h_V, c, mod=None):
     """latent_model.py:31-35."""
-    shift, scale = _lin(sd, "W_out.adaLN_modulation.1", F.silu(c)).chunk(2, dim=1)
+    shift, scale = _adaln(sd, "W_out", c, mod).chunk(2, dim=1)
     return _lin(sd, "W_out.linear", _mod(_ln(h_V), shift, scale))
 
 
-def forward(sd, x, t, cg_xyz, cg_z, mask, features=None, taps=None, x_self_cond=None):
+MOD_HEADS = tuple(f"encoder_layers.{l}" for l in range(3)) + tuple(f"decoder_layers.{l}" for l in range(3)) + ("W_out",)
+MOD_WIDTHS = (9 * 128,) * 3 + (6 * 128,) * 3 + (2 * 128,)       # 6016 in all
+
+
+def step_mods(sd, t):
+    """[N, 6016]: the adaLN vectors of a step, heads in MOD_HEADS order (what `forward(mods=)` takes)."""
+    sc = F.silu(t_embed(sd, t))
+    return torch.cat([_lin(sd, f"{h}.adaLN_modulation.1", sc) for h in MOD_HEADS], dim=1)
+
+
+def forward(sd, x, t, cg_xyz, cg_z, mask, features=None, taps=None, x_self_cond=None, h_E0=None, mods=None):
     """latent_model.py:175-268 for `mpnn_diffusion` (decoder_mask=False, use_seq_in_encoder=True).
 
     x [N,L,3]; t [N] (already mapped through timestep_map); cg_xyz [N,L,3]; cg_z [N,L] int64;
     mask [N,L] bool.  `features` = (E, E_idx) lets a caller hoist the step-invariant CA
     features; the reference recomputes them every call.  Returns [N,L,6].
+
+    Everything follows the dtype of the weights and inputs: a state dict, x and cg_xyz cast to float64 give a
+    float64 forward.  Two more substitutions, for tests that compare what comes AFTER an intermediate value:
+    `h_E0` = (edge state after W_e [N,L,K,128], E_idx) in place of the CA features and W_e; `mods` = the adaLN
+    vectors of the step ([6016] or [N,6016], MOD_HEADS order) in place of t_embed and the seven adaLN heads
+    (t is then not read).
     """
-    c = t_embed(sd, t)
+    if mods is None:
+        c = t_embed(sd, t)
+        mod = (None,) * len(MOD_HEADS)
+    else:
+        c = None
+        mod = mods.reshape(-1, sum(MOD_WIDTHS)).expand(x.shape[0], -1).split(MOD_WIDTHS, dim=1)
     maski = mask.int()
-    E, E_idx = ca_features(sd, cg_xyz, maski) if features is None else features
+    if h_E0 is None:
+        E, E_idx = ca_features(sd, cg_xyz, maski) if features is None else features
+    else:
+        assert features is None
+        h_E, E_idx = h_E0
     if sd["x_in.weight"].shape[1] == 2 * x.shape[-1]:     # self_condition model, latent_model.py:210-212
         x = torch.cat((torch.zeros_like(x) if x_self_cond is None else x_self_cond, x), dim=-1)
     h_V = _lin(sd, "x_in", x)
-    h_E = _lin(sd, "W_e", E)
+    if h_E0 is None:
+        h_E = _lin(sd, "W_e", E)
     if taps is not None:
         taps["E_idx"], taps["h_E0"] = E_idx, h_E
     mask_attend = gather_nodes(maski.unsqueeze(-1), E_idx).squeeze(-1)
     mask_attend = maski.unsqueeze(-1) * mask_attend
     for l in range(3):
-        h_V, h_E = enc_layer(sd, f"encoder_layers.{l}", h_V, h_E, E_idx, maski, mask_attend, c)
+        h_V, h_E = enc_layer(sd, f"encoder_layers.{l}", h_V, h_E, E_idx, maski, mask_attend, c, mod=mod[l])
         if taps is not None:
             taps[f"enc{l}_hV"], taps[f"enc{l}_hE"] = h_V, h_E
     h_S = F.embedding(cg_z, sd["W_s.weight"])
@@ -213,10 +259,10 @@ def forward(sd, x, t, cg_xyz, cg_z, mask, features=None, taps=None, x_self_cond=
     h_EXV_enc = torch.cat([h_ES, gather_nodes(h_V, E_idx)], -1)
     for l in range(3):
         h_ESV = torch.cat([h_ES, gather_nodes(h_V, E_idx)], -1) + h_EXV_enc
-        h_V = dec_layer(sd, f"decoder_layers.{l}", h_V, h_ESV, maski, c)
+        h_V = dec_layer(sd, f"decoder_layers.{l}", h_V, h_ESV, maski, c, mod=mod[3 + l])
         if taps is not None:
             taps[f"dec{l}_hV"] = h_V
-    return final_layer(sd, h_V, c)
+    return final_layer(sd, h_V, c, mod=mod[6])
 
 
 def batch_to_dense(batch):

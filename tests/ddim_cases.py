@@ -28,11 +28,35 @@ DDIM_CASES = {
     "rev_pin_L46": (True, 46, 2, 114, "10", dict(), 0.0, False, "eps", "pin"),
     "rev_cond_L46": (True, 46, 2, 115, "10", dict(), 0.0, False, "eps", "cond"),
 }
-# GPU tolerance of a case's trajectory against the reference's where it is not the default 2e-5 (with the measured reason)
-# fwd_fixed_small_L46 / fwd_ddim10_L46: the denoiser FORWARD (f16x3, unchanged by DDIM) differs from the reference's by
-# 4.9e-4 / 1.8e-3 of the output's max at two nodes of these inputs at their first step (2.4e-6 on fwd_L46's); the
-# deterministic DDIM step carries that into the trajectory: 4.7e-4 / 3.5e-4 measured on both paths.
+# GPU tolerance of a case's trajectory against the reference's where it is not the default 2e-5, with the cause.
+#
+# Both exceptions come from ONE pair of edges each, between two neighbouring residues of frame 1 whose local frames are
+# partly zeroed (a CA step outside the 3.6-4.0 A window): R = O_i^T O_j is then symmetric with trace -1 in exact
+# arithmetic, so all three sign arguments s_k are exactly 0 and 1 + trace(R) is pure rounding noise.  The reference's
+# quaternion is normalize(0, 0, 0, sqrt(relu(1 + trace R)) / 2): (0, 0, 0, 1) if the noise came out positive, the zero
+# quaternion if not - a jump of 0.2 of h_E0's maximum in that edge's row.  tests/conditioning.py calls all four edges
+# ill-conditioned (|1 + trace R| < 1e-3).  Established on the CPU and on MI355X (all three contraction modes alike):
+#
+# fwd_fixed_small_L46 (seed 105, t 999): edges 29 <-> 30 of frame 1.  float64: 1 + trace R = 0, zero quaternion; the
+#   device: the same (its rows are within 1.4e-5 of float64 on every ill-conditioned edge); the REFERENCE's fp32 gets a
+#   positive noise value and (0, 0, 0, 1): its h_E0 rows are 0.20 / 0.23 of the maximum from float64 there and its
+#   forward 4.9e-4 / 3.9e-4 of the output's maximum from the float64 forward at nodes 76 / 75 (4.9e-5 next, median
+#   2.8e-6).  The golden carries the reference's rounding, not an error of the kernels.
+# fwd_ddim10_L46 (seed 106, t 900): edges 12 <-> 13 of frame 1.  float64: 1 + trace R = 2.2e-16, (0, 0, 0, 1), and so the
+#   reference's fp32 (its forward is within 1.3e-5 of float64 at every node); the device's fp32 evaluation of the same
+#   formula gets a value <= 0 and the zero quaternion: its two rows equal the float64 rows recomputed with the zero
+#   quaternion to 2.6e-7 of the maximum, and the float64 forward from the device's features differs from the plain
+#   float64 forward by 1.8e-3 / 1.0e-3 at nodes 59 / 58 (6.5e-5 next, median 4e-8) - the whole of the deviation.
+#   These are the edges of FEATURE_DISCONTINUITY_EDGES below, which test_features_prepass_edge_by_edge admits as "the
+#   reference's discontinuity taken the other way" and nothing else.
+#
+# Everything after the features meets the tight per-node bound against float64 on both inputs, in every mode and with
+# the large-job kernels (tests/test_fp64_parity.py: at most 2.6 x the fp32 oracle's own error, bound 4 / 16).  The
+# deterministic DDIM step carries the first-step difference into the trajectory: 4.7e-4 / 3.5e-4 measured on both paths.
 DDIM_TOL = {"fwd_fixed_small_L46": 1e-3, "fwd_ddim10_L46": 1e-3}
+# geometry -> (frame, node, neighbour) of the edges where the device takes a discontinuity of the reference's quaternion
+# the other way than float64 does (see above); an edge that is not listed here must meet the ordinary per-edge bounds
+FEATURE_DISCONTINUITY_EDGES = {"fwd_ddim10_L46": ((1, 12, 13), (1, 13, 12))}
 
 
 def hooks_for(name, device="cpu"):

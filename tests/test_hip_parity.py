@@ -14,6 +14,8 @@ from oracle import denoiser as oden
 from oracle import sampler as osam
 from oracle import vae_decode as odec
 from tests import cases
+from tests import conditioning as cond
+from tests import ddim_cases
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -135,6 +137,26 @@ def test_features_prepass(den, sd, name):
     assert rel_err(got, hE0) < 3e-4
     err = (got - hE0).abs().amax(-1)                    # per edge
     assert float(err[:, :, 1:].median()) < 2e-6         # typical edge: fp32 rounding only
+
+
+@pytest.mark.parametrize("name", list(cond.feature_geometries()))
+def test_features_prepass_edge_by_edge(den, sd, name):
+    """Every edge row of the device's h_E0 against the FLOAT64 oracle's row of the same neighbour - the maximum over
+    edges, not the median - on the four DENOISER_CASES and the geometries of the two DDIM cases with a wider trajectory
+    bound.  Which edges are ill-conditioned is decided from the reference's own formulas (tests/conditioning.py, at most
+    10 % of a case); the bounds and the one admitted exception are those of cond.check_edge_rows."""
+    L, B, seed = cond.feature_geometries()[name]
+    prot, batch, x, t, mask = cases.denoiser_inputs(L, B, seed)
+    st = structures_of(den, prot)
+    torch.cuda.synchronize()
+    cg_z, cg_xyz, m = oden.batch_to_dense(batch)
+    K = min(64, L)
+    got_idx = st.E_idx.cpu().view(B, L, 64)[:, :, :K].long()
+    assert torch.equal(got_idx.sort(-1).values, oden.knn(cg_xyz, m.float())[1].sort(-1).values)     # same neighbour sets
+    got = engine.edge_rows(st.h_E0, split=den.split_edge_state).cpu().view(B, L, 64, 128)[:, :, :K]
+    fig = cond.check_edge_rows(sd, cg_xyz, m, got, got_idx, f"{name} {den.weights.precision}",
+                               ddim_cases.FEATURE_DISCONTINUITY_EDGES.get(name, ()))
+    print(fig["message"], "; worst ill-conditioned edge %.2e" % fig["worst_ill"], "; other way:", fig["other_way"])
 
 
 def test_step_mods(den, sd):
