@@ -10,7 +10,7 @@ import os
 import torch  # noqa: F401  (must precede the dlopen below)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 15   # CODLAD_ABI_VERSION of include/codlad_hip.h this binding was written against
+ABI_VERSION = 16   # CODLAD_ABI_VERSION of include/codlad_hip.h this binding was written against
 # CODLAD_HIP_LIB: an alternative build of the same ABI (A/B measurements, tools/ablate_edge.py)
 LIB_PATH = os.environ.get("CODLAD_HIP_LIB") or os.path.join(_HERE, "libcodlad_hip.so")
 
@@ -52,7 +52,7 @@ class DenoiserWeights(C.Structure):
 
 
 class Workspace(C.Structure):
-    _fields_ = [(n, P) for n in ("hV", "hVenc", "S", "PQ", "hE", "status", "tile_list")] + [("n_tiles", C.c_int32)]
+    _fields_ = [(n, P) for n in ("hV", "hVenc", "S", "PQ", "hE", "status", "tile_list")] + [("n_tiles", C.c_int32), ("xcd_bounds", P)]
 
 
 class DecoderWeights(C.Structure):
@@ -107,6 +107,7 @@ _SIGS = {
                                           C.POINTER(Workspace), P]),
     "codlad_status_check": (C.c_int, [P, P]),
     "codlad_set_option": (C.c_int, [C.c_int, C.c_int]),
+    "codlad_edge_plan_host": (C.c_int, [P, C.c_int, C.c_int, C.c_int, C.c_int, P, P]),
     "codlad_ddpm_update": (C.c_int, [P, P, P, P, C.c_int, P, P, P]),
     "codlad_ddpm_pred_xstart": (C.c_int, [P, P, P, C.c_int, P, P]),
     "codlad_ddpm_posterior_step": (C.c_int, [P, P, P, P, P, P, C.c_float, C.c_int, P, P, P]),
@@ -160,6 +161,19 @@ def lib():
 
 
 OPT_NODEQ_MAX_TILES, OPT_EDGE_TILE_MAX_NODES, OPT_DEC_EDGE_VARIANT, OPT_TP_CONV_VARIANT, OPT_EDGE_UPD_VARIANT, OPT_EDGE_CUS, OPT_EDGE_WIDE_MAX_TILES, OPT_NODE_QUAD_MAX_TILES = 0, 1, 3, 4, 5, 6, 7, 2   # CODLAD_OPT_* of include/codlad_hip.h
+OPT_EDGE_PAIR = 8
+EDGE_GRID = (256, 8)    # persistent grid of the per-node edge kernels on MI355X: one 8-wave workgroup per CU
+
+
+def edge_plan(K, pair=True, grid=EDGE_GRID):
+    """codlad_edge_plan_host: K = the nodes' neighbour counts (node_info[:, 2], host) -> (bounds int32 [9], stats int64 [20]):
+    the XCD chunk bounds of the per-node edge kernels and the tile accounting of their walk (include/codlad_hip.h)."""
+    import numpy as np
+    K = np.ascontiguousarray(K, dtype=np.int32)
+    bounds, stats = np.zeros(9, dtype=np.int32), np.zeros(20, dtype=np.int64)
+    check(lib().codlad_edge_plan_host(K.ctypes.data_as(P), K.shape[0], grid[0], grid[1], int(bool(pair)),
+                                      bounds.ctypes.data_as(P), stats.ctypes.data_as(P)), "codlad_edge_plan_host")
+    return bounds, stats
 
 
 def set_option(option, value):

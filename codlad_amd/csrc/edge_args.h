@@ -35,6 +35,9 @@ struct EdgeArgs {
     // b2 / b3 point at biases pre-scaled to match.
     GeluK gelu_a, gelu_b;
     float res_scale, ln_eps;
+    // per-node kernels of large jobs (msg_kernel_h, upd_kernel_h; every other kernel ignores both):
+    const int32_t *xcd_bounds;   // [9] node bounds of the eight XCD chunks, balanced by tile cost (null: uniform chunks)
+    int pair;                    // 1: two nodes with short last tiles share one 32-edge tile (edge_pair_ok below)
 };
 
 // small jobs: the work dealt out per non-empty 32-edge tile {node, half} (edge_tile_kernels.hip, edge_wide_kernels.hip)
@@ -64,16 +67,42 @@ __host__ __device__ inline int xcd_chunk_nodes(int n_nodes) {
     return g * ((tiles + 7) / 8);
 }
 
+// Paired last tiles (CODLAD_OPT_EDGE_PAIR).  A node's last 32-edge tile holds K - 32 (K > 32) or K (K <= 32) valid columns;
+// when that is at most 16 the node is ELIGIBLE, and the last tiles of two eligible nodes fit in one tile: columns 0..15
+// belong to the first node, 16..31 to the second.  A wave pairs node n with the next node of its own walk, n + stride,
+// when n has two tiles (its first tile gives the time to learn the next node's K before the decision is due) and both
+// are eligible.  Columns are independent of each other in every contraction, GELU and LayerNorm, so the results are
+// bit for bit those of the unpaired walk.  A node's cost in HALF tiles, as the chunk balance below counts it: an
+// eligible two-tile node 3, any other two-tile node 4, a one-tile node 2.
+__host__ __device__ inline bool edge_node_eligible(int K) { return K <= 16 || (K > 32 && K <= 48); }
+__host__ __device__ inline bool edge_pair_ok(int K, int K_next) {
+    return K > 32 && K <= 48 && edge_node_eligible(K_next);
+}
+__host__ __device__ inline int edge_node_cost2(int K) { return K <= 32 ? 2 : (K <= 48 ? 3 : 4); }
+constexpr int XCD_BOUND_GRANULE = 32;     // the balanced chunk bounds are multiples of this many nodes
+
 struct NodeSpan {
     int first, end, stride;
 };
-// nodes first, first + stride, ... < end for wave `wave` of this workgroup
-DEV NodeSpan wave_node_span(int n_nodes, int nwaves, int wave) {
-    const int nb = gridDim.x, b = blockIdx.x;
+// nodes first, first + stride, ... < end for wave `wave` of workgroup b of nb.  bounds (host or device memory, may be
+// null): the nine chunk bounds of EdgeArgs::xcd_bounds.
+__host__ __device__ inline NodeSpan node_span_of(int n_nodes, int nwaves, int wave, int nb, int b, const int32_t *bounds) {
     if (nb % 8) return {b * nwaves + wave, n_nodes, nb * nwaves};
-    const int chunk = xcd_chunk_nodes(n_nodes);
-    const int lo = (b % 8) * chunk, hi = lo + chunk < n_nodes ? lo + chunk : n_nodes;
+    int lo, hi;
+    if (bounds) {
+        lo = bounds[b % 8];
+        hi = bounds[b % 8 + 1];
+    } else {
+        const int chunk = xcd_chunk_nodes(n_nodes);
+        lo = (b % 8) * chunk;
+        hi = lo + chunk;
+    }
+    if (lo > n_nodes) lo = n_nodes;
+    if (hi > n_nodes) hi = n_nodes;
     return {lo + (b / 8) * nwaves + wave, hi, (nb / 8) * nwaves};
+}
+DEV NodeSpan wave_node_span(int n_nodes, int nwaves, int wave, const int32_t *bounds = nullptr) {
+    return node_span_of(n_nodes, nwaves, wave, gridDim.x, blockIdx.x, bounds);
 }
 
 // Small wave-uniform vectors (the centre node's P row, biases, modulation) are NOT read with

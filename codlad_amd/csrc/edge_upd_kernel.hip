@@ -19,7 +19,7 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void upd_kernel_h(EdgeArgs
     extern __shared__ __align__(16) u32x4 wl[];
     constexpr int NT = NWAVES * 64;
     constexpr int W1_U4 = UPD_W1_KS * 512;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     u32x4 *consts = wl + 2 * LDS_BLOCK_U4 + W1_U4;
     {
         const u32x4 *g1 = reinterpret_cast<const u32x4 *>(a.W1h);
@@ -48,26 +48,53 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void upd_kernel_h(EdgeArgs
     const float *c_base = reinterpret_cast<const float *>(consts);
     float *Pslot = reinterpret_cast<float *>(consts + EDGE_CONST_U4 + wave * 32);
     const int h = lane >> 5, c = lane & 31;
-    const NodeSpan span = wave_node_span(a.n_nodes, NWAVES, wave);
-    for (int n = span.first; n < span.end; n += span.stride) {
+    const NodeSpan span = wave_node_span(a.n_nodes, NWAVES, wave, a.xcd_bounds);
+    // Paired last tiles (edge_args.h): the first node of a pair runs its first tile only and waits in pend_* (wave-uniform);
+    // the wave's next node then runs its last tile with the waiting node in columns 0..15 and itself in 16..31.
+    int pend_n = -1, pend_src = 0, pend_base = 0, pend_K = 0;
+    for (int nv = span.first; nv < span.end; nv += span.stride) {
+        // node and table entry are wave-uniform: kept in scalar registers, the per-lane choice between this node and the
+        // waiting one is then one select where an address is formed
+        const int n = __builtin_amdgcn_readfirstlane(nv);
         const int4 info = a.node_info[n];
-        const int src = info.x, base = info.y, K = info.z;
-        const float *rows = a.hE_in + (size_t)(a.in_by_src ? src : n) * EDGE_BLOCK;
-        float *out_rows = a.hE_out + (size_t)n * EDGE_BLOCK;
-        const bool validA = c < K, validB = 32 + c < K;
-        const int colA = validA ? c : 0, colB = validB ? 32 + c : 0;
-        const int jA = a.E_idx[(size_t)src * 64 + colA], jB = a.E_idx[(size_t)src * 64 + colB];
+        const int src = __builtin_amdgcn_readfirstlane(info.x), base = __builtin_amdgcn_readfirstlane(info.y);
+        const int K = __builtin_amdgcn_readfirstlane(info.z);
+        const int Ku = K, lh = Ku > 32;     // lh: the half that holds this node's last tile
+        const bool paired = pend_n >= 0;
+        bool open_pair = false;
+        if (a.pair && !paired && Ku > 32 && Ku <= 48 && n + span.stride < span.end)
+            open_pair = edge_pair_ok(Ku, __builtin_amdgcn_readfirstlane(a.node_info[n + span.stride].z));
+        // lanes that work for the waiting node in the shared tile (ptA / ptB: half 0 / 1 of this node is the shared tile)
+        const bool ptA = paired && !lh, ptB = paired && lh;
+        const bool lowA = ptA && c < 16, lowB = ptB && c < 16;
+        const int wantA = ptA ? (c < 16 ? 32 + c : c - 16) : c, wantB = ptB ? 32 + (c & 15) : 32 + c;
+        const bool validA = wantA < (lowA ? pend_K : K), validB = wantB < (lowB ? pend_K : K);
+        const int colA = validA ? wantA : 0, colB = validB ? wantB : 0;
+        const int jA = a.E_idx[(size_t)(lowA ? pend_src : src) * 64 + colA];
+        const int jB = a.E_idx[(size_t)(lowB ? pend_src : src) * 64 + colB];
         // this node's P row: one coalesced 512-byte read, staged in the wave's own LDS slot
         // (same wave writes and reads: program order + lgkmcnt, no barrier)
         reinterpret_cast<float2 *>(Pslot)[lane] = reinterpret_cast<const float2 *>(a.P + (size_t)n * HD)[lane];
 
         for (int half = 0; half < 2; ++half) {
             if (32 * half >= K) break;
+            if (half && open_pair) break;                   // the last tile runs with the next node's
+            const bool ptile = half ? ptB : ptA, low = half ? lowB : lowA;
             const bool valid = half ? validB : validA;
-            const int colc = half ? colB : colA, col = 32 * half + c;
+            const int colc = half ? colB : colA;
             const int j = half ? jB : jA;
+            // blocks of this node and of the waiting one are scalar addresses; a lane only selects between the two
+            const int base_l = low ? pend_base : base;
+            const float *rows_n = a.hE_in + (size_t)(a.in_by_src ? src : n) * EDGE_BLOCK;
+            const float *rows_p = a.hE_in + (size_t)(a.in_by_src ? pend_src : pend_n) * EDGE_BLOCK;
+            const float *rows = low ? rows_p : rows_n;
+            float *out_rows = a.hE_out + (size_t)(low ? pend_n : n) * EDGE_BLOCK;
             Tile x, acc, t2;
             StreamedGemm<TERMS, UPD_W1_KS, 8 - UPD_W1_KS, false, 8, true> tail1;
+            // own-node term of a shared tile: the LDS has no room for a second slot per wave, so the waiting node's row
+            // follows this node's through the one slot, each added by its own lanes only (same values, same adds)
+            float2 pend_p = {0.f, 0.f};
+            if (ptile) pend_p = reinterpret_cast<const float2 *>(a.P + (size_t)pend_n * HD)[lane];
             if (!HOISTED) tail1.start(a.W1h, lane);
             // the constants never change, so the compiler would read them once, before the node
             // loop, into ~300 registers and spill those; an opaque zero offset keeps the reads here
@@ -75,11 +102,15 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void upd_kernel_h(EdgeArgs
             asm volatile("" : "+v"(lds_off));
             const float *c_b2 = c_base + lds_off, *c_b3 = c_b2 + HD;
             const float *c_modA = c_b2 + 2 * HD, *c_modB = c_b2 + 3 * HD;
-            tile_load_row(acc, a.Q + (size_t)(base + j) * HD, h);
-            tile_add_row(acc, Pslot, h);
+            tile_load_row(acc, a.Q + (size_t)(base_l + j) * HD, h);
+            if (!low) tile_add_row(acc, Pslot, h);
+            if (ptile) {
+                reinterpret_cast<float2 *>(Pslot)[lane] = pend_p;
+                if (low) tile_add_row(acc, Pslot, h);
+            }
             if (!HOISTED) tile_load_edge<true>(x, rows, colc, h);                // layer-1 operand and residual
             if (HOISTED) {
-                tile_add_edge(acc, a.E1 + (size_t)src * EDGE_BLOCK, colc, h);
+                tile_add_edge(acc, low ? a.E1 + (size_t)pend_src * EDGE_BLOCK : a.E1 + (size_t)src * EDGE_BLOCK, colc, h);
                 // the tile itself (h_E0, shared by the ensemble members: default cache policy) is only the residual here:
                 // requested after the hoisted term has been added, it travels under layer 2.  (Requested first, as the
                 // non-hoisted variant must, hipcc serialised the sixteen E1 loads behind it, one s_waitcnt vmcnt(0) each:
@@ -99,8 +130,14 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void upd_kernel_h(EdgeArgs
             gemm128_h_lds<TERMS, true>(x, t2, w3, lane, a.gelu_b);     // layer 3 on GELU(layer 2)
             tile_layernorm_affine(x, a.ln_eps, c_modA, c_modB, h);
             tile_presplit(x);                                          // stored as the halves the next contraction reads
-            if (valid) tile_store_edge<true>(x, out_rows, col, h);
+            if (valid) tile_store_edge<true>(x, out_rows, colc, h);
         }
+        if (open_pair) {
+            pend_n = n;
+            pend_src = src;
+            pend_base = base;
+            pend_K = K;
+        } else pend_n = -1;
     }
 }
 

@@ -112,6 +112,9 @@ class Job:
         ws.hV, ws.hVenc, ws.S, ws.PQ, ws.hE, ws.status, ws.tile_list = (
             _lib.ptr(t) for t in (self.hV, self.hVenc, self.S, self.PQ, self.hE, self.status, self.tile_list))
         ws.n_tiles = tiles.shape[0]
+        # XCD chunks of the per-node edge kernels, balanced by tile cost (paired last tiles, include/codlad_hip.h)
+        self.xcd_bounds = torch.from_numpy(_lib.edge_plan(info[:, 2])[0]).to(device)
+        ws.xcd_bounds = _lib.ptr(self.xcd_bounds)
         self.ws = ws
 
     def workspace_bytes(self):

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define CODLAD_ABI_VERSION 15
+#define CODLAD_ABI_VERSION 16
 #define CODLAD_H 128          /* hidden width of the denoiser                          */
 #define CODLAD_KNN 64         /* k_neighbors (reference models/latent_model.py:86)      */
 #define CODLAD_MODS_PER_STEP 6016 /* 3*9*128 (enc) + 3*6*128 (dec) + 2*128 (final)      */
@@ -189,7 +189,28 @@ typedef struct {
      * order (the partial neighbour sums are kept apart and added in that order). */
     const int32_t *tile_list;
     int32_t n_tiles;
+    /* optional (NULL = eight equal node ranges): [9] ascending node bounds, bounds[0] = 0, bounds[8] = n_nodes, of the
+     * eight chunks the per-node edge kernels of large jobs deal to the eight XCDs, cut so that every chunk costs the same
+     * number of 32-edge tiles (codlad_edge_plan_host writes them, on the host; this is a DEVICE copy).  Read only while
+     * CODLAD_OPT_EDGE_PAIR is on.  Placement is a speed matter only. */
+    const int32_t *xcd_bounds;
 } codlad_workspace;
+
+/* HOST helper (every pointer is a HOST pointer): the walk of the per-node edge kernels over a job, from the helpers the
+ * kernels themselves decide with.  K_host[n] = node_info[n].K; n_workgroups x waves_per_workgroup = the persistent grid
+ * (one 8-wave workgroup per CU: 256, 8 on MI355X).  pair != 0: paired last tiles (CODLAD_OPT_EDGE_PAIR) - a node whose
+ * last tile holds at most 16 valid columns (K <= 16 or 32 < K <= 48) is eligible, and a wave runs the second tile of a
+ * two-tile eligible node together with the last tile of the next node of its walk when that one is eligible too.
+ * bounds_host [9] (may be NULL): the chunk bounds for codlad_workspace.xcd_bounds - multiples of 32 nodes, each cut where
+ * the tiles the waves have walked so far are nearest to a multiple of an eighth of the total, so that no chunk exceeds the
+ * mean by more than one 32-node group (the walk, not the cost model below, is what is balanced: a wave that meets an odd
+ * number of eligible nodes runs one of them on its own); pair == 0: the eight equal ranges.
+ * stats_host [20] (may be NULL): [0] tiles of the unpaired walk, [1] the job's cost in HALF tiles by the cost model (a
+ * two-tile eligible node 1.5 tiles, any other node its tile count), [2] tiles of the walk as the given grid runs it with
+ * these bounds, [3] pairs it forms, [4..11] cost-model half tiles of each chunk, [12..19] tiles each chunk's waves walk
+ * (zeros for a grid that is not a multiple of 8 workgroups: it is not dealt over the XCDs). */
+int codlad_edge_plan_host(const int32_t *K_host, int n_nodes, int n_workgroups, int waves_per_workgroup, int pair,
+                          int32_t *bounds_host, int64_t *stats_host);
 
 /* Status bits.  NONFINITE: a denoiser output (eps | variance logits) was inf or NaN.  In the split-fp16
  * contraction modes that is also what an operand beyond the fp16 range (|x| > 65504) ends in: its halves
@@ -459,6 +480,9 @@ int codlad_xyz_to_ic(const float *xyz, int n_frames, int n_atoms, const int32_t 
  *                                the next tile prefetched (upd1_kernel_h) where nearly every node has two 32-edge tiles;
  *                                2 = that kernel for every job.  Bit-identical; same speed on MI355X (profiles/r04_upd1_*)
  *   CODLAD_OPT_EDGE_CUS          persistent workgroups of the per-node edge kernels (0 / >= CU count: one per CU)
+ *   CODLAD_OPT_EDGE_PAIR         per-node edge kernels of large jobs (msg_kernel_h, upd_kernel_h): 1 (default) = two nodes whose
+ *                                last tiles hold at most 16 columns each share one 32-edge tile, and the XCD chunks follow
+ *                                codlad_workspace.xcd_bounds; 0 = every node on its own, eight equal chunks.  Same bits.
  *   CODLAD_OPT_EDGE_WIDE_MAX_TILES  tile-wise jobs of up to this many 32-edge tiles give a tile to FOUR waves (one output
  *                                block each, weight quarters in registers: edge_wide_kernels.hip) instead of one; same bits */
 #define CODLAD_OPT_NODEQ_MAX_TILES 0
@@ -469,7 +493,8 @@ int codlad_xyz_to_ic(const float *xyz, int n_frames, int n_atoms, const int32_t 
 #define CODLAD_OPT_EDGE_UPD_VARIANT 5
 #define CODLAD_OPT_EDGE_CUS 6
 #define CODLAD_OPT_EDGE_WIDE_MAX_TILES 7
-#define CODLAD_N_OPTIONS 8
+#define CODLAD_OPT_EDGE_PAIR 8
+#define CODLAD_N_OPTIONS 9
 int codlad_set_option(int option, int value);
 
 /* Measurement aid for bench.py (not part of the reference's interface): while enabled, every edge-kernel launch made
