@@ -2,6 +2,7 @@
 
     python -m codlad_amd.build [--force]
 """
+import glob
 import os
 import subprocess
 import sys
@@ -9,7 +10,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcodlad_hip.so")
-SOURCES = ["api.hip", "denoiser_kernels.hip", "edge_msg_kernel.hip", "edge_upd_kernel.hip", "edge_upd1_kernel.hip", "edge_tile_kernels.hip",
+SOURCES = ["api.hip", "host_util.hip", "edge_plan.hip", "denoiser_forward.hip", "denoiser_f32_kernels.hip", "node_stream_kernel.hip",
+           "sampler_kernels.hip", "edge_msg_kernel.hip", "edge_upd_kernel.hip", "edge_upd1_kernel.hip", "edge_tile_kernels.hip",
            "edge_wide_kernels.hip",
            "node_wide_kernels.hip", "node_quad_kernels.hip", "ode_kernels.hip", "features_kernels.hip", "decode_kernels.hip",
            "ic_decoder_kernels.hip", "encoder_kernels.hip", "encoder_mfma_kernel.hip", "metrics_kernels.hip"]
@@ -25,7 +27,9 @@ EXTRA_FLAGS = {"features_kernels.hip": ["-ffp-contract=off"], "ode_kernels.hip":
                # the packed math that pays (GELU) is written out explicitly in common.h
                # -fno-honor-nans: min/max on MFMA results otherwise get a canonicalising v_max x,x
                # each (3 instructions for min(|x|, c)); nothing on this path produces or tests NaN
-               "denoiser_kernels.hip": ["-fno-slp-vectorize", "-fno-honor-nans"],
+               "denoiser_f32_kernels.hip": ["-fno-slp-vectorize", "-fno-honor-nans"],
+               "node_stream_kernel.hip": ["-fno-slp-vectorize", "-fno-honor-nans"],
+               "sampler_kernels.hip": ["-fno-slp-vectorize", "-fno-honor-nans"],     # final_kernel's non-finite test relies on it
                "edge_tile_kernels.hip": ["-fno-slp-vectorize", "-fno-honor-nans"],
                "edge_wide_kernels.hip": ["-fno-slp-vectorize", "-fno-honor-nans"],
                "edge_msg_kernel.hip": ["-fno-slp-vectorize", "-fno-honor-nans"],
@@ -36,8 +40,7 @@ EXTRA_FLAGS = {"features_kernels.hip": ["-ffp-contract=off"], "ode_kernels.hip":
                "edge_upd1_kernel.hip": ["-fno-slp-vectorize", "-fno-honor-nans", "-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "node_wide_kernels.hip": ["-fno-slp-vectorize", "-fno-honor-nans"],
                "node_quad_kernels.hip": ["-fno-slp-vectorize", "-fno-honor-nans"]}
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "encoder_common.h"), os.path.join(CSRC, "edge_args.h"), os.path.join(CSRC, "node_args.h"),
-           os.path.join(HERE, "..", "include", "codlad_hip.h")]
+HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", "codlad_hip.h")]
 
 
 def hipcc():

@@ -1,6 +1,6 @@
 // Host-side plumbing of libcodlad_hip.so: error reporting and the weight-block packer.
 #include "common.h"
-#include "../../include/codlad_hip.h"
+#include "host_util.h"
 
 #include <stdarg.h>
 #include <stddef.h>
@@ -14,8 +14,6 @@ void codlad_set_error(const char *fmt, ...) {
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
 }
-
-hipError_t codlad_take_attr_error();   // denoiser_kernels.hip: a failed hipFuncSetAttribute, if any
 
 int codlad_check_launch(const char *what) {
     hipError_t e = codlad_take_attr_error();

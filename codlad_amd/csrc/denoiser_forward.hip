@@ -1,0 +1,361 @@
+// The denoiser on the host: which kernel runs an edge / node launch, the launch sequence of one forward (enqueue_forward),
+// the sampling loops around it and the edge-launch probe.  Host only: the kernels are in the units host_util.h lists.
+#include "node_args.h"
+#include "sampler_args.h"
+
+// precision: 0 = fp32 MFMA, 1 = f16x4, 2 = f16x3 (include/codlad_hip.h); terms = 4 or 3 products per split contraction, 0 = fp32
+static void launch_edge_now(bool update, const EdgeArgs &ea, int precision, hipStream_t st, const int2 *tile_list,
+                            int n_tiles) {
+    const int terms = precision == 2 ? 3 : (precision == 1 ? 4 : 0);
+    if (!terms) return launch_edge_f32(update, ea, st);
+    if (tile_list && n_tiles <= option_value(CODLAD_OPT_EDGE_WIDE_MAX_TILES)) return launch_edge_wide(terms, update, ea, tile_list, n_tiles, st);
+    if (tile_list) return launch_edge_tile(terms, update, ea, tile_list, n_tiles, st);
+    if (update) {
+        // upd1_kernel_h gives every node two tiles: worth it while (nearly) every node has two (n_tiles counts the
+        // non-empty ones; 0 = the caller gave no tile list, i.e. nothing is known about the job)
+        const bool two_tiles_each = n_tiles > 0 && 20ll * n_tiles >= 19ll * 2 * ea.n_nodes;
+        const int variant = option_value(CODLAD_OPT_EDGE_UPD_VARIANT);
+        if ((variant == 1 && two_tiles_each) || variant == 2) launch_edge_upd1(terms, ea, st);   // 2: always (tests)
+        else launch_edge_upd(terms, ea, st);
+    } else launch_edge_msg(terms, ea, st);
+}
+
+// Measurement aid (codlad_probe_edge_launches): while on, every edge-kernel launch of a forward is bracketed by a pair
+// of HIP events on its own stream, so bench.py can quote the dominant kernel's duration as it runs inside the job
+// (between node kernels, at the job's clock) rather than in a back-to-back loop of its own.
+#define PROBE_MAX 4096
+static struct {
+    bool on = false;
+    int used = 0;
+    hipEvent_t ev[PROBE_MAX][2] = {};
+    bool made[PROBE_MAX] = {};
+    int kind[PROBE_MAX] = {};
+} g_probe;
+
+static void launch_edge(bool update, const EdgeArgs &ea, int precision, hipStream_t st, const int2 *tile_list = nullptr,
+                        int n_tiles = 0) {
+    const int i = g_probe.used;
+    bool rec = g_probe.on && i < PROBE_MAX;
+    if (rec && !g_probe.made[i]) {
+        rec = hipEventCreate(&g_probe.ev[i][0]) == hipSuccess && hipEventCreate(&g_probe.ev[i][1]) == hipSuccess;
+        g_probe.made[i] = rec;
+    }
+    if (rec) (void)hipEventRecord(g_probe.ev[i][0], st);
+    launch_edge_now(update, ea, precision, st, tile_list, n_tiles);
+    if (rec) {
+        (void)hipEventRecord(g_probe.ev[i][1], st);
+        g_probe.kind[i] = (update ? 1 : 0) + (ea.E1 ? 2 : 0);
+        g_probe.used = i + 1;
+    }
+}
+
+extern "C" int codlad_probe_edge_launches(int enable) {
+    g_probe.on = enable != 0;
+    if (enable) g_probe.used = 0;
+    return 0;
+}
+
+extern "C" int codlad_probe_read(int kind, double *total_ms) {
+    CODLAD_REQUIRE(total_ms && kind >= 0 && kind < 4, "bad arguments");
+    double sum = 0.0;
+    int n = 0;
+    for (int i = 0; i < g_probe.used; ++i) {
+        if (g_probe.kind[i] != kind) continue;
+        float ms = 0.f;
+        hipError_t e = hipEventSynchronize(g_probe.ev[i][1]);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, g_probe.ev[i][0], g_probe.ev[i][1]);
+        if (e != hipSuccess) { codlad_set_error("codlad_probe_read: %s", hipGetErrorString(e)); return -(int)e - 1000; }
+        sum += ms;
+        ++n;
+    }
+    *total_ms = sum;
+    return n;
+}
+
+// Node kernel by job size.  The streaming kernel runs NW waves (32-node tiles) per workgroup, one workgroup per CU (LDS).
+// Four waves give every SIMD one tile and the most workgroups; a job with more tiles than 4 x CUs would then need a
+// second, mostly empty round, and eight waves (two per SIMD, which overlap in this latency-bound kernel; a few dozen
+// spilled registers) finish in one and stream every weight block once per 256 nodes.
+static void launch_node(bool upd, const NodeArgs &na, int precision, hipStream_t st) {
+    const int terms = precision == 2 ? 3 : (precision == 1 ? 4 : 0);
+    if (!terms) return launch_node_f32(upd, na, st);
+    const int tiles = (na.n_nodes + 31) / 32;
+    if (upd && tiles <= option_value(CODLAD_OPT_NODE_QUAD_MAX_TILES)) launch_node_quad(terms, na, st);
+    else if (tiles <= option_value(CODLAD_OPT_NODEQ_MAX_TILES)) launch_node_wide(terms, upd, na, st);
+    else launch_node_stream(terms, tiles > 4 * num_cu() ? 8 : 4, upd, na, st);
+}
+
+// What every launch of one forward shares.
+struct Job {
+    const codlad_denoiser_weights *w;
+    const int4 *ni;
+    const int32_t *E_idx;
+    int n_nodes;
+    const codlad_workspace *ws;
+    bool split;      // split-fp16 mode: biases are the pre-scaled copies, block exponents become scale constants (include/codlad_hip.h)
+    float *PQ(int k) const { return ws->PQ + (size_t)k * n_nodes * HD; }
+};
+
+static EdgeArgs edge_args(const Job &j, const float *hE_in, bool in_by_src) {
+    EdgeArgs ea = {};
+    ea.node_info = j.ni; ea.E_idx = j.E_idx; ea.n_nodes = j.n_nodes;
+    ea.hE_in = hE_in; ea.in_by_src = in_by_src;
+    ea.pair = option_value(CODLAD_OPT_EDGE_PAIR) != 0;
+    ea.xcd_bounds = ea.pair ? j.ws->xcd_bounds : nullptr;
+    return ea;
+}
+// message kernel of an encoder or decoder layer: P / Q in planes 0 / 1 of PQ
+template <class Layer, class LayerH>
+static EdgeArgs msg_args(const Job &j, const Layer &L, const LayerH &Lh, const float *hE_in, bool in_by_src) {
+    EdgeArgs ea = edge_args(j, hE_in, in_by_src);
+    ea.P = j.PQ(0); ea.Q = j.PQ(1); ea.W1 = L.W1e; ea.W2 = L.W2; ea.S = j.ws->S;
+    ea.W1h = Lh.W1e; ea.W2h = Lh.W2;
+    ea.b2 = j.split ? Lh.b2 : L.b2;
+    ea.gelu_a = gelu_consts(j.split ? Lh.e1 : 0);
+    ea.gelu_b = gelu_consts(j.split ? Lh.e1 + Lh.e2 : 0);
+    ea.res_scale = 1.0f; ea.ln_eps = 1e-6f;
+    return ea;
+}
+// edge update of an encoder layer: P / Q in planes 2 / 3, m = the layer's modulation vectors
+static EdgeArgs upd_args(const Job &j, const codlad_enc_layer &L, const codlad_enc_layer_h &Lh, const float *hE_in,
+                         bool in_by_src, const float *m) {
+    EdgeArgs eu = edge_args(j, hE_in, in_by_src);
+    eu.hE_out = j.ws->hE;
+    eu.P = j.PQ(2); eu.Q = j.PQ(3); eu.W1 = L.W11e; eu.W2 = L.W12; eu.W3 = L.W13;
+    eu.mods3 = m + 6 * HD;
+    eu.W1h = Lh.W11e; eu.W2h = Lh.W12; eu.W3h = Lh.W13;
+    eu.b2 = j.split ? Lh.b12 : L.b12; eu.b3 = j.split ? Lh.b13 : L.b13;
+    const int E2 = j.split ? Lh.e11 + Lh.e12 : 0, E3 = j.split ? E2 + Lh.e13 : 0;
+    eu.gelu_a = gelu_consts(j.split ? Lh.e11 : 0);
+    eu.gelu_b = gelu_consts(E2);
+    eu.res_scale = pow2i(E3);
+    eu.ln_eps = 1e-6f * pow2i(2 * E3);
+    return eu;
+}
+
+// scales of a node update that follows a message kernel with accumulated exponent e_msg = e1 + e2
+static void set_node_scales(NodeArgs &na, bool split, int e_msg, int e3, int e_in, int e_out) {
+    na.s_scale = 0.015625f * pow2i(split ? -e_msg : 0);
+    na.t_scale = 64.0f * pow2i(split ? -e3 : 0);
+    na.ffn_scale = pow2i(split ? -(e_in + e_out) : 0);
+    na.gelu_ffn = gelu_consts(split ? e_in : 0);
+}
+// node update of an encoder or decoder layer, without its projections
+template <class Layer, class LayerH>
+static NodeArgs node_update_args(const Job &j, const Layer &L, const LayerH &Lh, const float *mods, bool s_partials) {
+    NodeArgs na = {};
+    na.node_info = j.ni; na.n_nodes = j.n_nodes; na.S = j.ws->S; na.hV = j.ws->hV; na.s_partials = s_partials;
+    na.W3 = L.W3; na.b3 = j.split ? Lh.b3 : L.b3; na.mods = mods;
+    na.b_in = j.split ? Lh.b_in : L.b_in; na.b_out = j.split ? Lh.b_out : L.b_out;
+    set_node_scales(na, j.split, Lh.e1 + Lh.e2, Lh.e3, Lh.e_in, Lh.e_out);
+    na.blk_h[0] = Lh.W3;
+    for (int c = 0; c < 4; ++c) {
+        na.Win[c] = L.Win[c]; na.Wout[c] = L.Wout[c];
+        na.blk_h[1 + 2 * c] = Lh.Win[c]; na.blk_h[2 + 2 * c] = Lh.Wout[c];
+    }
+    return na;
+}
+// appends a projection out = W @ h_V + b (b may be null); blk0 = blocks of NodeArgs::blk_h in front of the projections'
+static void add_proj(NodeArgs &na, int blk0, const float *W, const void *Wh, const float *b, float *out) {
+    const int p = na.n_proj++;
+    na.proj_w[p] = W; na.proj_b[p] = b; na.proj_out[p] = out;
+    na.blk_h[blk0 + p] = Wh;
+}
+// ... the decoder's neighbour term: input h_V + h_Venc, + TS[z]
+static void add_proj_dec_q(NodeArgs &na, const Job &j, const codlad_dec_layer &D, const codlad_dec_layer_h &Dh) {
+    na.proj_flags[na.n_proj] = 3; na.TS = j.split ? Dh.TS : D.TS;
+    add_proj(na, 9, D.W1v, Dh.W1v, nullptr, j.PQ(1));
+}
+
+// One denoiser forward up to (not including) the final layer: leaves h_V in ws->hV.
+static void enqueue_forward(const codlad_denoiser_weights *w, const int32_t *node_info,
+                            int n_nodes, const int32_t *E_idx, const float *h_E0, const float *E1,
+                            size_t n_snodes, const float *x, const float *x_self_cond, const float *mods_t,
+                            const codlad_workspace *ws, hipStream_t st) {
+    const Job j = {w, reinterpret_cast<const int4 *>(node_info), E_idx, n_nodes, ws, w->precision != 0};
+    // small jobs: edge kernels per 32-edge tile, message sums per half (S[2][n_nodes][128])
+    // (while every wave of the persistent grid gets at most one tile: beyond that the per-node order is as good)
+    const bool tilewise = j.split && ws->tile_list && ws->n_tiles > 0 &&
+                          (ws->n_tiles <= 8 * num_cu() || ws->n_tiles <= option_value(CODLAD_OPT_EDGE_WIDE_MAX_TILES)) &&
+                          n_nodes <= option_value(CODLAD_OPT_EDGE_TILE_MAX_NODES);
+    const int2 *tile_list = tilewise ? reinterpret_cast<const int2 *>(ws->tile_list) : nullptr;
+
+    // h_V = x_in(x); P/Q for encoder layer 0's message
+    {
+        NodeArgs na = {};
+        na.node_info = j.ni; na.n_nodes = n_nodes;
+        na.x = x; na.x_in_w = w->x_in_w; na.x_in_b = w->x_in_b; na.hV = ws->hV;
+        na.x_sc = x_self_cond; na.in_dim = w->self_condition ? 6 : 3;
+        add_proj(na, 0, w->enc[0].W1a, w->enc_h[0].W1a, j.split ? w->enc_h[0].b1 : w->enc[0].b1, j.PQ(0));
+        add_proj(na, 0, w->enc[0].W1c, w->enc_h[0].W1c, nullptr, j.PQ(1));
+        set_node_scales(na, j.split, 0, 0, 0, 0);
+        launch_node(false, na, w->precision, st);
+    }
+    for (int l = 0; l < 3; ++l) {
+        const codlad_enc_layer &L = w->enc[l];
+        const codlad_enc_layer_h &Lh = w->enc_h[l];
+        const float *m = mods_t + mods_offset(l);
+        const float *hE_in = l == 0 ? h_E0 : ws->hE;
+        EdgeArgs ea = msg_args(j, L, Lh, hE_in, l == 0);
+        if (l == 0 && E1) ea.E1 = E1;
+        launch_edge(false, ea, w->precision, st, tile_list, ws->n_tiles);
+
+        NodeArgs na = node_update_args(j, L, Lh, m, tilewise);
+        add_proj(na, 9, L.W11a, Lh.W11a, j.split ? Lh.b11 : L.b11, j.PQ(2));   // edge update P
+        add_proj(na, 9, L.W11c, Lh.W11c, nullptr, j.PQ(3));                   // edge update Q
+        if (l < 2) {
+            add_proj(na, 9, w->enc[l + 1].W1a, w->enc_h[l + 1].W1a, j.split ? w->enc_h[l + 1].b1 : w->enc[l + 1].b1, j.PQ(0));
+            add_proj(na, 9, w->enc[l + 1].W1c, w->enc_h[l + 1].W1c, nullptr, j.PQ(1));
+        } else {
+            // first decoder layer: h_Venc := this h_V, so its neighbour term sees 2*h_V
+            add_proj(na, 9, w->dec[0].W1a, w->dec_h[0].W1a, j.split ? w->dec_h[0].b1 : w->dec[0].b1, j.PQ(0));
+            add_proj_dec_q(na, j, w->dec[0], w->dec_h[0]);
+            na.hVenc_out = ws->hVenc; na.venc_is_self = 1;
+        }
+        launch_node(true, na, w->precision, st);
+
+        EdgeArgs eu = upd_args(j, L, Lh, hE_in, l == 0, m);
+        if (l == 0 && E1) eu.E1 = E1 + n_snodes * 64 * HD;
+        launch_edge(true, eu, w->precision, st, tile_list, ws->n_tiles);
+    }
+    for (int l = 0; l < 3; ++l) {
+        const codlad_dec_layer &L = w->dec[l];
+        const codlad_dec_layer_h &Lh = w->dec_h[l];
+        launch_edge(false, msg_args(j, L, Lh, ws->hE, false), w->precision, st, tile_list, ws->n_tiles);
+
+        NodeArgs na = node_update_args(j, L, Lh, mods_t + mods_offset(3 + l), tilewise);
+        if (l < 2) {
+            add_proj(na, 9, w->dec[l + 1].W1a, w->dec_h[l + 1].W1a, j.split ? w->dec_h[l + 1].b1 : w->dec[l + 1].b1, j.PQ(0));
+            add_proj_dec_q(na, j, w->dec[l + 1], w->dec_h[l + 1]);
+            na.hVenc_in = ws->hVenc;
+        }
+        launch_node(true, na, w->precision, st);
+    }
+}
+
+static int check_ws(const codlad_workspace *ws) {
+    return ws && ws->hV && ws->hVenc && ws->S && ws->PQ && ws->hE;
+}
+
+static FinalArgs final_args(const codlad_denoiser_weights *w, const codlad_workspace *ws, const float *mods_t, int n_nodes) {
+    FinalArgs fa = {};
+    fa.hV = ws->hV; fa.mods = mods_t + mods_offset(6); fa.out_w = w->out_w; fa.out_b = w->out_b;
+    fa.n_nodes = n_nodes; fa.status = ws->status; fa.n_out = w->out_dim;
+    return fa;
+}
+
+extern "C" int codlad_denoiser_forward(const codlad_denoiser_weights *w, const int32_t *node_info,
+                                       int n_nodes, const int32_t *E_idx, const float *h_E0,
+                                       const float *E1, int n_snodes, const float *x,
+                                       const float *x_self_cond, const float *mods_t, float *out,
+                                       const codlad_workspace *ws, void *stream) {
+    CODLAD_REQUIRE(w && node_info && E_idx && h_E0 && x && mods_t && out, "null pointer");
+    CODLAD_REQUIRE(check_ws(ws), "incomplete workspace");
+    CODLAD_REQUIRE(n_nodes > 0, "n_nodes must be positive");
+    hipStream_t st = (hipStream_t)stream;
+    CODLAD_REQUIRE(!x_self_cond || w->self_condition, "x_self_cond given to a model without self-conditioning");
+    CODLAD_REQUIRE(w->out_dim == 6 || w->out_dim == 3, "out_dim must be 6 (diffusion) or 3 (flow matching)");
+    enqueue_forward(w, node_info, n_nodes, E_idx, h_E0, E1, (size_t)n_snodes, x, x_self_cond, mods_t, ws, st);
+    FinalArgs fa = final_args(w, ws, mods_t, n_nodes);
+    fa.logits = out;
+    launch_final(fa, CODLAD_STEP_DDPM, nullptr, nullptr, 0, st);
+    return codlad_check_launch("codlad_denoiser_forward");
+}
+
+// the loop of codlad_sample_loop / codlad_sample_loop_pinned / codlad_ddim_loop (pin_x0 == NULL: no pinning).
+// step: CODLAD_STEP_* of final_kernel; `mode` is read by the DDIM steps only.  The forward loops run i = T-1 .. 0 and
+// consume noise entry k at step k; the reverse DDIM loop runs i = 0 .. T-1 and reads no noise.
+static void sample_loop(const codlad_denoiser_weights *w, const int32_t *node_info, int n_nodes, const int32_t *E_idx,
+                        const float *h_E0, const float *E1, int n_snodes, float *x, float *x_start, const float *noise,
+                        const float *mods, const float *coef, int T, const float *pin_x0, const uint8_t *pin_mask,
+                        const codlad_workspace *ws, void *stream, int step = CODLAD_STEP_DDPM, int mode = 0) {
+    hipStream_t st = (hipStream_t)stream;
+    // self-conditioning (gaussian_diffusion.py:530-547): step k reads the pred_xstart step k-1 wrote;
+    // the first step gets none, which the model treats as zeros (latent_model.py:211)
+    const bool sc = w->self_condition != 0;
+    const bool reverse = step == CODLAD_STEP_DDIM_REVERSE;
+    for (int k = 0; k < T; ++k) {
+        const int i = reverse ? k : T - 1 - k;
+        const float *mods_t = mods + (size_t)i * CODLAD_MODS_PER_STEP;
+        enqueue_forward(w, node_info, n_nodes, E_idx, h_E0, E1, (size_t)n_snodes, x, sc && k > 0 ? x_start : nullptr,
+                        mods_t, ws, st);
+        FinalArgs fa = final_args(w, ws, mods_t, n_nodes);
+        fa.x = x; fa.noise = reverse ? nullptr : noise + (size_t)k * n_nodes * 3;
+        fa.coef = coef + (size_t)i * 8; fa.x_start = x_start;
+        launch_final(fa, step, pin_x0, pin_mask, mode, st);
+    }
+}
+
+#define SAMPLE_LOOP_REQUIRE()                                                                                          \
+    CODLAD_REQUIRE(w && node_info && E_idx && h_E0 && x && noise && mods && coef, "null pointer");                     \
+    CODLAD_REQUIRE(check_ws(ws), "incomplete workspace");                                                             \
+    CODLAD_REQUIRE(n_nodes > 0 && T > 0, "n_nodes and T must be positive");                                           \
+    CODLAD_REQUIRE(!w->self_condition || x_start, "a self-conditioned model needs the x_start buffer");               \
+    CODLAD_REQUIRE(w->out_dim == 6 || w->out_dim == 3,                                                                \
+                   "the DDPM loop needs a model with 6 outputs (mean | variance logits) or 3 (fixed-variance samplers)")
+
+extern "C" int codlad_sample_loop(const codlad_denoiser_weights *w, const int32_t *node_info,
+                                  int n_nodes, const int32_t *E_idx, const float *h_E0,
+                                  const float *E1, int n_snodes, float *x, float *x_start,
+                                  const float *noise, const float *mods, const float *coef, int T,
+                                  const codlad_workspace *ws, void *stream) {
+    SAMPLE_LOOP_REQUIRE();
+    sample_loop(w, node_info, n_nodes, E_idx, h_E0, E1, n_snodes, x, x_start, noise, mods, coef, T, nullptr, nullptr, ws,
+                stream);
+    return codlad_check_launch("codlad_sample_loop");
+}
+
+extern "C" int codlad_sample_loop_pinned(const codlad_denoiser_weights *w, const int32_t *node_info,
+                                         int n_nodes, const int32_t *E_idx, const float *h_E0,
+                                         const float *E1, int n_snodes, float *x, float *x_start,
+                                         const float *noise, const float *mods, const float *coef, int T,
+                                         const float *pin_x0, const uint8_t *pin_mask,
+                                         const codlad_workspace *ws, void *stream) {
+    SAMPLE_LOOP_REQUIRE();
+    CODLAD_REQUIRE(pin_x0 && pin_mask, "null pointer (pin_x0 / pin_mask)");
+    sample_loop(w, node_info, n_nodes, E_idx, h_E0, E1, n_snodes, x, x_start, noise, mods, coef, T, pin_x0, pin_mask, ws,
+                stream);
+    return codlad_check_launch("codlad_sample_loop_pinned");
+}
+#undef SAMPLE_LOOP_REQUIRE
+
+extern "C" int codlad_ddim_loop(const codlad_denoiser_weights *w, const int32_t *node_info, int n_nodes,
+                                const int32_t *E_idx, const float *h_E0, const float *E1, int n_snodes, float *x,
+                                float *x_start, const float *noise, const float *mods, const float *coef, int T, int mode,
+                                int reverse, const float *pin_x0, const uint8_t *pin_mask, const codlad_workspace *ws,
+                                void *stream) {
+    CODLAD_REQUIRE(w && node_info && E_idx && h_E0 && x && mods && coef, "null pointer");
+    CODLAD_REQUIRE(reverse || noise, "null pointer (noise: only the reverse loop runs without it)");
+    CODLAD_REQUIRE(!pin_x0 == !pin_mask, "null pointer (pin_x0 and pin_mask come together)");
+    CODLAD_REQUIRE(n_nodes > 0 && T > 0, "n_nodes and T must be positive");
+    CODLAD_REQUIRE(mode >= 0 && mode <= (CODLAD_DDPM_START_X | CODLAD_DDPM_FIXED_VAR | CODLAD_DDPM_CLIP),
+                   "unknown mode bits");
+    CODLAD_REQUIRE(w->out_dim == ((mode & CODLAD_DDPM_FIXED_VAR) ? 3 : 6),
+                   "mode and model disagree: a learned-range sampler needs a model with 6 outputs (mean | variance "
+                   "logits), a fixed-variance one (mode bit 2) a model with 3");
+    CODLAD_REQUIRE(!w->self_condition || x_start, "a self-conditioned model needs the x_start buffer");
+    CODLAD_REQUIRE(check_ws(ws), "incomplete workspace");
+    sample_loop(w, node_info, n_nodes, E_idx, h_E0, E1, n_snodes, x, x_start, noise, mods, coef, T, pin_x0, pin_mask, ws,
+                stream, reverse ? CODLAD_STEP_DDIM_REVERSE : CODLAD_STEP_DDIM, mode);
+    return codlad_check_launch("codlad_ddim_loop");
+}
+
+// Single launch of one of the two edge kernels on encoder layer 0 (reads h_E0 and the P/Q left by
+// a previous forward; idempotent) - lets bench.py time the dominant kernel with HIP events.
+extern "C" int codlad_bench_edge_launch(const codlad_denoiser_weights *w, const int32_t *node_info,
+                                        int n_nodes, const int32_t *E_idx, const float *h_E0,
+                                        const float *mods_t, const codlad_workspace *ws, int which,
+                                        int layer, void *stream) {
+    CODLAD_REQUIRE(w && node_info && E_idx && h_E0 && mods_t, "null pointer");
+    CODLAD_REQUIRE(check_ws(ws), "incomplete workspace");
+    CODLAD_REQUIRE(n_nodes > 0 && (which == 0 || which == 1) && (layer == 0 || layer == 1), "bad arguments");
+    const Job j = {w, reinterpret_cast<const int4 *>(node_info), E_idx, n_nodes, ws, w->precision != 0};
+    const codlad_enc_layer &L = w->enc[layer];
+    const codlad_enc_layer_h &Lh = w->enc_h[layer];
+    // layer 0 reads the shared structure-edge state, layer 1 the per-sample edge state (in place)
+    const float *hE_in = layer == 0 ? h_E0 : ws->hE;
+    EdgeArgs ea = which == 0 ? msg_args(j, L, Lh, hE_in, layer == 0) : upd_args(j, L, Lh, hE_in, layer == 0, mods_t);
+    ea.S = ws->S;      // unused by the edge update; the diagnostic -DU1_STAMP build of upd1_kernel_h reports through it
+    launch_edge(which == 1, ea, w->precision, (hipStream_t)stream, nullptr, ws->n_tiles);
+    return codlad_check_launch("codlad_bench_edge_launch");
+}

@@ -4,13 +4,9 @@
 // loops - scratch 20 -> 88 and 24 -> 116 bytes, -9 % - although their source was unchanged.)
 #pragma once
 #include "common.h"
-#include "../../include/codlad_hip.h"
+#include "host_util.h"     // for the launcher that ends every kernel unit
 
 #define HD 128
-
-void set_max_lds(const void *fn, size_t bytes);   // denoiser_kernels.hip: hipFuncSetAttribute, failure kept for the next check
-int num_cu();
-int edge_cus();     // persistent workgroups of an edge kernel: num_cu() unless CODLAD_OPT_EDGE_CUS says fewer
 
 // ---------------------------------------------------------------------------------------------
 // Edge kernels: one wave = one node = up to 64 neighbour columns (two 32-column passes).

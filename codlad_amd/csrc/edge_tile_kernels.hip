@@ -2,7 +2,7 @@
 #include "edge_args.h"
 
 // ---------------------------------------------------------------------------------------------
-// The same pipelines as upd_kernel_h / msg_kernel_h (denoiser_kernels.hip), with the work dealt out per
+// The same pipelines as upd_kernel_h / msg_kernel_h (edge_upd_kernel.hip, edge_msg_kernel.hip), with the work dealt out per
 // non-empty 32-edge tile {node, half} of the job's tile list instead of per node (twice the busy waves when the
 // job has fewer nodes than the grid has waves); the message kernel then writes one partial neighbour sum per
 // half, S[half][n_nodes][128], which the node kernel adds up.  Kept as separate kernels with their own argument

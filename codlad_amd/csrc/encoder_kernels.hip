@@ -15,11 +15,7 @@
 // consumed at once.  Outputs are produced one (irrep, w) at a time, summed over the group's lanes by shuffles and
 // accumulated in an LDS slot per node, so a node of any degree needs no atomics and the sum has a fixed order.
 #include "encoder_common.h"
-
-int tp_conv_variant();                                                       // denoiser_kernels.hip: CODLAD_OPT_TP_CONV_VARIANT
-void launch_tp_conv_mfma(const codlad_tp_conv_args &a, hipStream_t st);      // encoder_mfma_kernel.hip
-void launch_tp_conv_pack(const codlad_tp_conv_args &a, void *image, hipStream_t st);
-int tp_conv_image_bytes(int depth);
+#include "host_util.h"
 
 namespace {
 
@@ -443,7 +439,8 @@ __global__ __launch_bounds__(256) void csr_sort_kernel(int n, const int *ptr, co
 
 template <int DEPTH>
 void launch_tp(const codlad_tp_conv_args &a, hipStream_t st) {
-    if (tp_conv_variant() == 0 || (tp_conv_variant() == 2 && a.group == 64)) return launch_tp_conv_mfma(a, st);
+    const int variant = option_value(CODLAD_OPT_TP_CONV_VARIANT);
+    if (variant == 0 || (variant == 2 && a.group == 64)) return launch_tp_conv_mfma(a, st);
     if (a.group == 1) hipLaunchKernelGGL((tp_conv_kernel<DEPTH, 1>), dim3((a.n_recv + 63) / 64), dim3(64), 0, st, a);
     else if (a.group == 16) hipLaunchKernelGGL((tp_conv_kernel<DEPTH, 16>), dim3((a.n_recv + 3) / 4), dim3(64), 0, st, a);
     else hipLaunchKernelGGL((tp_conv_kernel<DEPTH, 64>), dim3(a.n_recv), dim3(64), 0, st, a);

@@ -28,15 +28,13 @@
 // edge, so the scale is a per-lane number) - and the products are descaled exactly; the descale of fc.3 rides on the
 // factor that zeroes the inputs of a lane without an edge, so it costs nothing.
 #include "encoder_common.h"
+#include "host_util.h"
 
 // Measurement-only build switch (tools/ablate_encoder.sh; results are wrong with it): 1 = no fc.3 blocks, 2 = every lane
 // reads the receiving node's own row instead of its sender's (no gather), 3 = both.
 #ifndef CODLAD_TP_ABLATE
 #define CODLAD_TP_ABLATE 0
 #endif
-
-int num_cu();                                       // denoiser_kernels.hip
-void set_max_lds(const void *fn, size_t bytes);     // denoiser_kernels.hip
 
 namespace {
 

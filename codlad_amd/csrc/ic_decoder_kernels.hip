@@ -19,10 +19,7 @@
 // (V node-major since round 3: a receiving residue's 40 sums leave as one coalesced 160-byte store; feature-major, a wave
 // wrote 40 dwords a column apart - 101 MB of write traffic per launch for 5.7 MB of sums.)
 #include "common.h"
-#include "../../include/codlad_hip.h"
-
-int num_cu();             // denoiser_kernels.hip
-int dec_edge_variant();   // denoiser_kernels.hip: CODLAD_OPT_DEC_EDGE_VARIANT
+#include "host_util.h"
 
 #define DF 40
 #define PI_F 3.14159265358979323846f
@@ -536,7 +533,7 @@ extern "C" int codlad_ic_decode(const codlad_decoder_weights *w, const float *z_
     hipStream_t st = (hipStream_t)stream;
     const dim3 per_lane((M + 63) / 64), per_wave((M + EDGE_WAVES - 1) / EDGE_WAVES), block(256);
     const int edge_grid = M < 16 * num_cu() ? M : 16 * num_cu();    // persistent waves, four per SIMD
-    const bool exact = dec_edge_variant() == 1;
+    const bool exact = option_value(CODLAD_OPT_DEC_EDGE_VARIANT) == 1;
     hipLaunchKernelGGL(dec_init_kernel, per_lane, block, 0, st, *w, z_q, cg_z, M, scratch);
     for (int blk = 0; blk < 4; ++blk) {
         if (exact) hipLaunchKernelGGL(dec_edge_exact_kernel, per_wave, dim3(64 * EDGE_WAVES), 0, st, *w, blk, cg_xyz, csr_ptr, csr_src, M, scratch);

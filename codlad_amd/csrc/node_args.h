@@ -1,4 +1,4 @@
-// Arguments of the node kernels (shared by denoiser_kernels.hip and node_wide_kernels.hip).
+// Arguments of the node kernels (every unit that holds one) and the x_in projection of node_kernel / node_kernel_h.
 #pragma once
 #include "edge_args.h"
 
@@ -34,3 +34,30 @@ struct NodeArgs {
     int s_partials;                    // 1: S holds one partial sum per half, S[2][n_nodes][128] (tile-wise message kernel)
 };
 
+// h_V = x_in([x_self_cond |] x) of the one-wave-per-tile kernels (node_kernel, node_kernel_h): a node's inputs, read once ...
+struct XIn {
+    float x0, x1, x2, s0, s1, s2;
+    bool sc;                           // input = cat(x_self_cond, x): weight columns 0-2 | 3-5
+};
+DEV XIn x_in_load(const NodeArgs &a, int nc) {
+    const float x0 = a.x[nc * 3 + 0], x1 = a.x[nc * 3 + 1], x2 = a.x[nc * 3 + 2];
+    const bool sc = a.in_dim == 6;
+    const bool have_sc = sc && a.x_sc != nullptr;
+    const float s0 = have_sc ? a.x_sc[nc * 3 + 0] : 0.f, s1 = have_sc ? a.x_sc[nc * 3 + 1] : 0.f,
+                s2 = have_sc ? a.x_sc[nc * 3 + 2] : 0.f;
+    return {x0, x1, x2, s0, s1, s2, sc};
+}
+// ... and the projection for output block bo (features 32 bo .. 32 bo + 31), added onto v, which holds the bias
+DEV void x_in_block(f32x16 &v, const XIn &x, const NodeArgs &a, int bo, int h) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int f = 32 * bo + (r & 3) + 8 * (r >> 2) + 4 * h;
+        const float *wr = a.x_in_w + f * a.in_dim;
+        float acc = 0.f;
+        if (x.sc) {
+            acc = fmaf(x.s2, wr[2], fmaf(x.s1, wr[1], x.s0 * wr[0]));
+            wr += 3;
+        }
+        v[r] += fmaf(x.x2, wr[2], fmaf(x.x1, wr[1], fmaf(x.x0, wr[0], acc)));
+    }
+}

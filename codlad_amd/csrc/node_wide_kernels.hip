@@ -1,6 +1,6 @@
 // Split-fp16 node update for SMALL and medium jobs ("wide" kernel), its own translation unit (see edge_args.h).
 //
-// node_kernel_h (denoiser_kernels.hip) gives a 32-node tile to ONE wave, which walks the up to 13 weight blocks of
+// node_kernel_h (node_stream_kernel.hip) gives a 32-node tile to ONE wave, which walks the up to 13 weight blocks of
 // the update one after the other: right when thousands of tiles share every block through LDS, but a job of a
 // few hundred nodes then keeps a handful of waves busy for 13 dependent block fetches (46 us per launch at 87
 // nodes: half of a DDPM step).  Here a workgroup of EIGHT waves (g, bo), g in {0, 1}, owns one tile:

@@ -1,0 +1,27 @@
+// Arguments of final_kernel (sampler_kernels.hip), filled by the loops of denoiser_forward.hip.
+#pragma once
+#include "edge_args.h"     // HD, host_util.h
+
+// FinalLayer (latent_model.py:31-35) + ancestral DDPM update (gaussian_diffusion.py:303-367,446).
+struct FinalArgs {
+    const float *hV;
+    const float *mods;  // shift, scale (2 x 128)
+    const float *out_w, *out_b;
+    int n_nodes;
+    float *logits;      // [n][6] or null
+    float *x;           // in/out [n][3] (update mode)
+    const float *noise; // [n][3]
+    const float *coef;  // device [8]
+    float *x_start;     // [n][3] or null: pred_xstart of this step (self-conditioning input of the next)
+    int *status;        // sticky status word or null (CODLAD_STATUS_NONFINITE)
+    int n_out;          // 6 (eps | variance logits, diffusion) or 3 (velocity, flow matching: logits mode only)
+};
+
+// the update final_kernel applies: ddpm_step (mode: the table's column 7) or ddim_step (the host's `mode`; reverse reads no noise)
+#define CODLAD_STEP_DDPM 0
+#define CODLAD_STEP_DDIM 1
+#define CODLAD_STEP_DDIM_REVERSE 2
+
+static inline int mods_offset(int head) {  // enc0..2, dec0..2, final
+    return head < 3 ? head * 9 * HD : (head < 6 ? 27 * HD + (head - 3) * 6 * HD : 45 * HD);
+}

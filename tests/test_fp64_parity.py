@@ -179,8 +179,8 @@ def test_forward_after_features_against_float64(name, mode):
 @pytest.mark.parametrize("name", list(cases.DENOISER_CASES) + list(DDIM_FIRST_STEPS))
 def test_forward_after_features_against_float64_large_job_kernels(name, mode):
     """The same with the small-job switches off, so that the kernels of the headline job are held to float64 directly and
-    not only through bit-identity with their small-job twins (the dispatch: enqueue_forward / launch_edge_h /
-    launch_node_h in denoiser_kernels.hip):
+    not only through bit-identity with their small-job twins (the dispatch: enqueue_forward / launch_edge_now /
+    launch_node in denoiser_forward.hip):
       CODLAD_OPT_EDGE_TILE_MAX_NODES = 0   no job is `tilewise`, no tile list is passed on: msg_kernel_h and (edge-update
                                            variant 0, the default) upd_kernel_h, one workgroup pass per node;
       CODLAD_OPT_NODE_QUAD_MAX_TILES = 0 and CODLAD_OPT_NODEQ_MAX_TILES = 0   neither node_kernel_q nor node_kernel_w:

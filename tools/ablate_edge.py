@@ -32,9 +32,7 @@ VARIANTS = {
     "nogelu": ([], [("common.h", "    if (GELU_IN) {\n        f32x2 t[1] = {x};", "    if (false) {\n        f32x2 t[1] = {x};"),
                     (MSG, "        tile_gelu(t2, a.gelu_b);\n", "")]),
     # node kernel (timed through the whole job: tools/ablate_edge.py bench <variants>)
-    "node_nofetch": ([], [("denoiser_kernels.hip", "        if (more) fetch(cur + 1);\n", ""),
-                          ("denoiser_kernels.hip", "        if (more) commit(cur + 1);\n", "")]),
-    "node_nobarrier": ([], [("denoiser_kernels.hip", "        if (more) commit(cur + 1);\n        __syncthreads();\n", "        if (more) commit(cur + 1);\n")]),
+    "node_nofetch": ([], [("node_stream_kernel.hip", "        if (more) fetch(cur + 1);\n", "")]),
     "noglb": ([], [(UPD, "                tail1.run(acc, x, lane, a.gelu_a);                                    // layer 1, streamed k-steps\n", "")]),
     "noln": ([], [(UPD, "            tile_layernorm_affine(x, a.ln_eps, c_modA, c_modB, h);\n", "")]),
     "nostore": ([], [(UPD, STORE, NOSTORE)]),
