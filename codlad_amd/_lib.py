@@ -10,7 +10,7 @@ import os
 import torch  # noqa: F401  (must precede the dlopen below)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 16   # CODLAD_ABI_VERSION of include/codlad_hip.h this binding was written against
+ABI_VERSION = 17   # CODLAD_ABI_VERSION of include/codlad_hip.h this binding was written against
 # CODLAD_HIP_LIB: an alternative build of the same ABI (A/B measurements, tools/ablate_edge.py)
 LIB_PATH = os.environ.get("CODLAD_HIP_LIB") or os.path.join(_HERE, "libcodlad_hip.so")
 
@@ -88,6 +88,11 @@ class MetricInputs(C.Structure):
                 ("ic", P), ("ic_recon", P), ("ic_mask", P), ("n_ic", C.c_int64)]
 
 
+class LossTerms(C.Structure):
+    """codlad_loss_terms: the per-sample results of the loss kernels, each may be NULL."""
+    _fields_ = [(n, P) for n in ("kl", "nll", "vb", "mse", "xstart_mse", "eps_mse", "pred_xstart")]
+
+
 _SIGS = {
     "codlad_abi_version": (C.c_int, []),
     "codlad_probe_edge_launches": (C.c_int, [C.c_int]),
@@ -118,6 +123,14 @@ _SIGS = {
     "codlad_ddim_loop": (C.c_int, [C.POINTER(DenoiserWeights), P, C.c_int, P, P, P, C.c_int, P, P, P, P, P, C.c_int,
                                    C.c_int, C.c_int, P, P, C.POINTER(Workspace), P]),
     "codlad_ddim_step": (C.c_int, [P, P, P, P, P, C.c_int, C.c_int, P, P, P]),
+    "codlad_q_sample": (C.c_int, [P, P, P, C.c_int, P, C.c_int, P, C.c_int, P, P, P, P]),
+    "codlad_q_posterior": (C.c_int, [P, P, P, C.c_int, P, C.c_int, P, C.c_int, P, P, P, P]),
+    "codlad_vb_terms": (C.c_int, [P, P, P, P, P, C.c_int, P, C.c_int, P, C.c_int, C.POINTER(LossTerms), P]),
+    "codlad_prior_bpd": (C.c_int, [P, P, C.c_int, P, C.c_int, P, P]),
+    "codlad_loss_forward": (C.c_int, [C.POINTER(DenoiserWeights), P, C.c_int, P, P, P, C.c_int, P, P, P, P, P, P, C.c_int,
+                                      C.c_int, P, C.c_int, P, C.POINTER(LossTerms), C.POINTER(Workspace), P]),
+    "codlad_bpd_loop": (C.c_int, [C.POINTER(DenoiserWeights), P, C.c_int, P, P, P, C.c_int, P, P, P, P, P, C.c_int, P,
+                                  C.c_int, P, P, P, P, P, C.POINTER(Workspace), P]),
     "codlad_vq_lookup": (C.c_int, [P, C.c_int, P, P, P, C.c_int, P, P, P, P]),
     "codlad_ic_decode": (C.c_int, [C.POINTER(DecoderWeights), P, P, P, P, P, C.c_int, P, P, P]),
     "codlad_cg_graph": (C.c_int, [P, P, C.c_int, C.c_float, P, P, P, P]),

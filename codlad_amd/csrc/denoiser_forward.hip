@@ -2,6 +2,7 @@
 // the sampling loops around it and the edge-launch probe.  Host only: the kernels are in the units host_util.h lists.
 #include "node_args.h"
 #include "sampler_args.h"
+#include "loss_args.h"
 
 // precision: 0 = fp32 MFMA, 1 = f16x4, 2 = f16x3 (include/codlad_hip.h); terms = 4 or 3 products per split contraction, 0 = fp32
 static void launch_edge_now(bool update, const EdgeArgs &ea, int precision, hipStream_t st, const int2 *tile_list,
@@ -339,6 +340,68 @@ extern "C" int codlad_ddim_loop(const codlad_denoiser_weights *w, const int32_t 
                 stream, reverse ? CODLAD_STEP_DDIM_REVERSE : CODLAD_STEP_DDIM, mode);
     return codlad_check_launch("codlad_ddim_loop");
 }
+
+// Loss evaluation around a forward (loss_kernels.hip): loss_kernel takes final_kernel's place after enqueue_forward.
+static LossArgs loss_args(const codlad_denoiser_weights *w, const codlad_workspace *ws, const float *mods_t, int n_nodes,
+                          const float *x_start, const float *x_t, const float *noise, const LossSamples &s) {
+    LossArgs la = {};
+    la.head = final_args(w, ws, mods_t, n_nodes);
+    la.x0 = x_start; la.xt = x_t; la.noise = noise; la.s = s;
+    return la;
+}
+
+#define LOSS_MODEL_REQUIRE()                                                                                            \
+    CODLAD_REQUIRE(check_ws(ws), "incomplete workspace");                                                              \
+    CODLAD_REQUIRE(n_nodes > 0 && T > 0 && n_samples > 0, "n_nodes, T and n_samples must be positive");                \
+    CODLAD_REQUIRE(w->out_dim == 6 || w->out_dim == 3,                                                                 \
+                   "the loss needs a model with 6 outputs (mean | variance logits) or 3 (fixed-variance samplers)")
+
+extern "C" int codlad_loss_forward(const codlad_denoiser_weights *w, const int32_t *node_info, int n_nodes,
+                                   const int32_t *E_idx, const float *h_E0, const float *E1, int n_snodes,
+                                   const float *x_start, const float *x_t, const float *noise, const float *x_self_cond,
+                                   const float *mods_t, const float *coef, int T, int t, const int32_t *sample_off,
+                                   int n_samples, float *model_out, const codlad_loss_terms *terms,
+                                   const codlad_workspace *ws, void *stream) {
+    CODLAD_REQUIRE(w && node_info && E_idx && h_E0 && x_start && x_t && mods_t && coef && sample_off && terms, "null pointer");
+    LOSS_MODEL_REQUIRE();
+    CODLAD_REQUIRE(t >= 0 && t < T, "t outside [0, T)");
+    CODLAD_REQUIRE(!x_self_cond || w->self_condition, "x_self_cond given to a model without self-conditioning");
+    hipStream_t st = (hipStream_t)stream;
+    enqueue_forward(w, node_info, n_nodes, E_idx, h_E0, E1, (size_t)n_snodes, x_t, x_self_cond, mods_t, ws, st);
+    LossArgs la = loss_args(w, ws, mods_t, n_nodes, x_start, x_t, noise, {sample_off, nullptr, t, T, n_samples, coef});
+    la.head.logits = model_out;
+    la.out = *terms;
+    launch_loss(la, st);
+    return codlad_check_launch("codlad_loss_forward");
+}
+
+extern "C" int codlad_bpd_loop(const codlad_denoiser_weights *w, const int32_t *node_info, int n_nodes,
+                               const int32_t *E_idx, const float *h_E0, const float *E1, int n_snodes, const float *x_start,
+                               const float *noise, float *x_t, const float *mods, const float *coef, int T,
+                               const int32_t *sample_off, int n_samples, float *vb, float *mse, float *xstart_mse,
+                               float *prior_bpd, float *total_bpd, const codlad_workspace *ws, void *stream) {
+    CODLAD_REQUIRE(w && node_info && E_idx && h_E0 && x_start && noise && x_t && mods && coef && sample_off, "null pointer");
+    CODLAD_REQUIRE(vb && mse && xstart_mse && prior_bpd && total_bpd, "null pointer (results)");
+    LOSS_MODEL_REQUIRE();
+    hipStream_t st = (hipStream_t)stream;
+    for (int k = 0; k < T; ++k) {
+        const int i = T - 1 - k;
+        const LossSamples s = {sample_off, nullptr, i, T, n_samples, coef};
+        const float *eps = noise + (size_t)k * n_nodes * 3;
+        const float *mods_t = mods + (size_t)i * CODLAD_MODS_PER_STEP;
+        launch_q_affine(x_start, eps, 8, 9, 10, 11, s, x_t, nullptr, nullptr, st);
+        // x_self_cond = null: zeros, the x_self_cond=None of calc_bpd_loop's model calls (latent_model.py:211)
+        enqueue_forward(w, node_info, n_nodes, E_idx, h_E0, E1, (size_t)n_snodes, x_t, nullptr, mods_t, ws, st);
+        LossArgs la = loss_args(w, ws, mods_t, n_nodes, x_start, x_t, eps, s);
+        la.out.vb = vb + (size_t)i * n_samples;
+        la.out.eps_mse = mse + (size_t)i * n_samples;
+        la.out.xstart_mse = xstart_mse + (size_t)i * n_samples;
+        launch_loss(la, st);
+    }
+    launch_prior(x_start, {sample_off, nullptr, T - 1, T, n_samples, coef}, vb, prior_bpd, total_bpd, st);
+    return codlad_check_launch("codlad_bpd_loop");
+}
+#undef LOSS_MODEL_REQUIRE
 
 // Single launch of one of the two edge kernels on encoder layer 0 (reads h_E0 and the P/Q left by
 // a previous forward; idempotent) - lets bench.py time the dominant kernel with HIP events.

@@ -1,4 +1,4 @@
-"""Drop-in for the reference's `diffusion_and_flow.create_diffusion` (sampling half).
+"""Drop-in for the reference's `diffusion_and_flow.create_diffusion` (sampling and forward-only loss evaluation).
 
 Same call surface as the reference (`diffusion_and_flow/__init__.py:10-60`): the returned object has
 `.p_sample_loop(model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device,
@@ -12,9 +12,14 @@ other callable runs between the two halves of the split step (`codlad_ddpm_pred_
 `codlad_ddpm_posterior_step`).  DDIM (the IDDPM release's `ddim_sample`, `ddim_reverse_sample`, `ddim_sample_loop`,
 `ddim_sample_loop_progressive`, with `eta`; `ddim_reverse_sample_loop` returns x_T) follows the same rule: the loop is
 one `codlad_ddim_loop` call for the HIP model with no hook or only a `PinLatents`, any other case steps through the
-model and `codlad_ddpm_pred_xstart` / `codlad_ddim_step`.  Training losses are out of scope.
+model and `codlad_ddpm_pred_xstart` / `codlad_ddim_step`.  The forward process and the losses (`q_mean_variance`,
+`q_sample`, `q_posterior_mean_variance`, `_vb_terms_bpd`, `training_losses`, and the IDDPM release's `calc_bpd_loop`) are
+evaluated forward-only: the HIP model runs `codlad_loss_forward` per group of equal timesteps and `codlad_bpd_loop` for the
+whole bound, any other CUDA callable is followed by `codlad_vb_terms`.  Gradients and training are out of scope; forward-only
+loss evaluation is built.
 """
 import enum
+import random
 
 import torch
 
@@ -32,6 +37,16 @@ class ModelVarType(enum.Enum):
     FIXED_SMALL = enum.auto()
     FIXED_LARGE = enum.auto()
     LEARNED_RANGE = enum.auto()
+
+
+class LossType(enum.Enum):
+    MSE = enum.auto()            # raw MSE (and the vb term when the variance is learned)
+    RESCALED_MSE = enum.auto()   # raw MSE, the vb term scaled by T / 1000
+    KL = enum.auto()             # the variational bound
+    RESCALED_KL = enum.auto()    # like KL, times T: an estimate of the full bound
+
+    def is_vb(self):
+        return self in (LossType.KL, LossType.RESCALED_KL)
 
 
 class PinLatents:
@@ -67,7 +82,158 @@ def _check_hook_output(v, x, what):
         raise ValueError(f"{what} must return a floating-point CUDA tensor of the sample's shape {tuple(x.shape)}, got {desc}")
 
 
-class SpacedDiffusion(Tables):
+# -- forward process and losses (forward-only) ---------------------------------------------------
+def _flat3(x, what):
+    """[N, L, 3] latents -> ([N * L, 3], nodes per sample); the refusals every loss entry point shares."""
+    if not x.is_cuda:
+        raise RuntimeError(f"{what} (codlad_amd) runs on the MI355X only")
+    if x.dim() != 3 or x.shape[-1] != 3:
+        raise NotImplementedError(f"{what}: latents [N, L, 3] only (the reference's angle wrap for a channel width of 2 is "
+                                  f"not built), got {tuple(x.shape)}")
+    return x.reshape(-1, 3), [int(x.shape[1])] * int(x.shape[0])
+
+
+class _LossEvaluation:
+    """The forward process and the forward-only losses of SpacedDiffusion (its second base class)."""
+
+    def loss_coefs(self, clip_denoised):
+        """The [T, 16] table of the loss kernels for this diffusion's branches (schedule.Tables.loss_coefficients)."""
+        cache = self.__dict__.setdefault("_loss_tables", {})
+        key = bool(clip_denoised)
+        if key not in cache:
+            var = {ModelVarType.FIXED_SMALL: "fixed_small",
+                   ModelVarType.FIXED_LARGE: "fixed_large"}.get(self.model_var_type, "learned_range")
+            cache[key] = self.loss_coefficients(predict_xstart=self.model_mean_type is ModelMeanType.START_X, var_type=var,
+                                                clip_denoised=key)
+        return cache[key]
+
+    def q_mean_variance(self, x_start, t):
+        """q(x_t | x_0): (mean, variance, log_variance), each of x_start's shape (gaussian_diffusion.py:211-221)."""
+        from ..engine import Denoiser
+        flat, lens = _flat3(x_start, "q_mean_variance")
+        return tuple(v.view(x_start.shape) for v in Denoiser.q_affine("q_sample", flat, None, lens, t, self.loss_coefs(False)))
+
+    def q_sample(self, x_start, t, noise=None):
+        """A sample of q(x_t | x_0) (gaussian_diffusion.py:223-238); t [N] int64, values may differ per sample."""
+        from ..engine import Denoiser
+        flat, lens = _flat3(x_start, "q_sample")
+        if noise is None:
+            noise = torch.randn_like(x_start)
+        if tuple(noise.shape) != tuple(x_start.shape):
+            raise ValueError(f"q_sample: noise {tuple(noise.shape)} does not match x_start {tuple(x_start.shape)}")
+        return Denoiser.q_affine("q_sample", flat, noise.reshape(-1, 3), lens, t, self.loss_coefs(False))[0].view(x_start.shape)
+
+    def q_posterior_mean_variance(self, x_start, x_t, t):
+        """q(x_{t-1} | x_t, x_0): (mean, variance, log_variance clipped) (gaussian_diffusion.py:240-260)."""
+        from ..engine import Denoiser
+        flat, lens = _flat3(x_start, "q_posterior_mean_variance")
+        if tuple(x_t.shape) != tuple(x_start.shape):
+            raise ValueError(f"q_posterior_mean_variance: x_t {tuple(x_t.shape)} does not match x_start {tuple(x_start.shape)}")
+        return tuple(v.view(x_start.shape)
+                     for v in Denoiser.q_affine("q_posterior", flat, x_t.reshape(-1, 3), lens, t, self.loss_coefs(False)))
+
+    def _map_t(self, t):
+        return torch.tensor(self.timestep_map, device=t.device, dtype=t.dtype)[t]          # respace.py:124-129
+
+    def _loss_terms(self, model, x_start, x_t, t, noise, clip_denoised, model_kwargs, x_self_cond=None):
+        """The loss kernels' terms for model(x_t, t): the HIP model through codlad_loss_forward (grouped by timestep), any
+        other callable through its output and codlad_vb_terms."""
+        from ..engine import Denoiser
+        flat, lens = _flat3(x_start, "the loss evaluation")
+        coef = self.loss_coefs(clip_denoised)
+        mod = self._hip_module(model)
+        nz = None if noise is None else noise.reshape(-1, 3)
+        if mod is not None:
+            job, _pin = self._fused_job(mod, x_start, model_kwargs, None)
+            sc = None if x_self_cond is None else x_self_cond.reshape(-1, 3)
+            return mod.engine().loss_terms(job, flat, t, nz, self, coef=coef, x_t=x_t.reshape(-1, 3), x_self_cond=sc)
+        kwargs = dict(model_kwargs)
+        if self.self_condition:
+            kwargs["x_self_cond"] = x_self_cond
+        model_out = model(x_t, self._map_t(t), **kwargs)
+        width = 3 if self.fixed_variance else 6
+        if not isinstance(model_out, torch.Tensor) or tuple(model_out.shape) != tuple(x_start.shape[:-1]) + (width,):
+            raise ValueError(f"the model must return a tensor {tuple(x_start.shape[:-1]) + (width,)} (a fixed-variance "
+                             "diffusion takes a model without variance channels)")
+        return Denoiser.vb_terms(model_out.reshape(-1, width), flat, x_t.reshape(-1, 3), nz, lens, t, coef)
+
+    def _vb_terms_bpd(self, model, x_start, x_t, t, clip_denoised=True, model_kwargs=None):
+        """One term of the variational bound in bits per dimension: {"output": [N] (the decoder NLL where t == 0, else the
+        KL), "pred_xstart"} (gaussian_diffusion.py:549-596).  Unlike the reference, whose own call drops model_kwargs and
+        so cannot run with this model, the model receives model_kwargs."""
+        r = self._loss_terms(model, x_start, x_t, t, None, clip_denoised, dict(model_kwargs or {}))
+        return {"output": r["vb"], "pred_xstart": r["pred_xstart"].view(x_start.shape)}
+
+    def training_losses(self, model, x_start, t, model_kwargs=None, noise=None):
+        """The training losses of one batch, forward-only (gaussian_diffusion.py:598-725): {"loss", "mse" [N], and "vb" for
+        a learned variance}; t [N] int64 may differ per sample.  RESCALED_MSE scales vb by T / 1000, RESCALED_KL the loss
+        by T.  A self-conditioned diffusion draws `random() < 0.5` from Python's global `random` where the reference does.
+        KL / RESCALED_KL: the vb term is computed from the model's actual output on (x_t, t, **model_kwargs); the
+        reference's own path for them hands model_kwargs=None to the model and cannot run with this model."""
+        _flat3(x_start, "training_losses")
+        if not isinstance(self.loss_type, LossType):
+            raise NotImplementedError(self.loss_type)
+        model_kwargs = dict(model_kwargs or {})
+        model_kwargs.pop("epoch", None)
+        if noise is None:
+            noise = torch.randn_like(x_start)
+        x_t = self.q_sample(x_start, t, noise=noise)
+        x_self_cond = None
+        if self.self_condition and random.random() < 0.5 and not self.loss_type.is_vb():
+            x_self_cond = self._loss_terms(model, x_start, x_t, t, None, False, model_kwargs)["pred_xstart"].view(x_start.shape)
+        r = self._loss_terms(model, x_start, x_t, t, noise, False, model_kwargs, x_self_cond=x_self_cond)
+        terms = {}
+        if self.loss_type.is_vb():
+            terms["loss"] = r["vb"] * self.num_timesteps if self.loss_type is LossType.RESCALED_KL else r["vb"]
+            return terms
+        terms["mse"] = r["mse"]
+        if not self.fixed_variance:
+            terms["vb"] = r["vb"] * (self.num_timesteps / 1000.0) if self.loss_type is LossType.RESCALED_MSE else r["vb"]
+            terms["loss"] = terms["mse"] + terms["vb"]
+        else:
+            terms["loss"] = terms["mse"]
+        return terms
+
+    def calc_bpd_loop(self, model, x_start, clip_denoised=True, model_kwargs=None, step_noise=None):
+        """The whole variational bound in bits per dimension (the IDDPM release's calc_bpd_loop): {"total_bpd", "prior_bpd"
+        [N]; "vb", "xstart_mse", "mse" [N, T], column k = step T-1-k, the order the loop visits them}.  One
+        codlad_bpd_loop call when `model` is the HIP model's forward; `step_noise` [T, *x_start.shape] optionally gives
+        the per-step noise (loop order) instead of T draws of randn_like(x_start)."""
+        from ..engine import Denoiser
+        flat, lens = _flat3(x_start, "calc_bpd_loop")
+        model_kwargs = dict(model_kwargs or {})
+        T = self.num_timesteps
+        eps = step_noise if step_noise is not None else self._draw_noise(x_start)
+        if tuple(eps.shape) != (T,) + tuple(x_start.shape):
+            raise ValueError(f"step_noise must be [T, *x_start.shape] = {(T,) + tuple(x_start.shape)}, got {tuple(eps.shape)}")
+        layout = lambda a: a.flip(0).t().contiguous()                      # noqa: E731  [T, N] by step -> [N, T] in loop order
+        mod = self._hip_module(model)
+        if mod is not None:
+            job, _pin = self._fused_job(mod, x_start, model_kwargs, None)
+            r = mod.engine().bpd(job, flat, eps.reshape(T, -1, 3), self, coef=self.loss_coefs(clip_denoised))
+            return {"total_bpd": r["total_bpd"], "prior_bpd": r["prior_bpd"], "vb": layout(r["vb"]),
+                    "xstart_mse": layout(r["xstart_mse"]), "mse": layout(r["mse"])}
+        from .. import _lib
+        import numpy as np
+        rows = {"vb": [], "xstart_mse": [], "eps_mse": []}
+        for k, i in enumerate(range(T - 1, -1, -1)):
+            t = torch.full((x_start.shape[0],), i, device=x_start.device, dtype=torch.int64)
+            x_t = self.q_sample(x_start, t, noise=eps[k])
+            r = self._loss_terms(model, x_start, x_t, t, eps[k], clip_denoised, model_kwargs)
+            for key in rows:
+                rows[key].append(r[key])
+        coef = torch.from_numpy(np.ascontiguousarray(self.loss_coefs(clip_denoised))).to(x_start.device)
+        prior = torch.empty(len(lens), dtype=torch.float32, device=x_start.device)
+        rc = _lib.lib().codlad_prior_bpd(_lib.ptr(flat.contiguous().float()), _lib.ptr(coef), T,
+                                         _lib.ptr(Denoiser.sample_offsets(lens, x_start.device)), len(lens), _lib.ptr(prior),
+                                         _lib.stream_ptr(x_start.device))
+        _lib.check(rc, "codlad_prior_bpd")
+        vb = torch.stack(rows["vb"], dim=1)
+        return {"total_bpd": vb.sum(dim=1) + prior, "prior_bpd": prior, "vb": vb,
+                "xstart_mse": torch.stack(rows["xstart_mse"], dim=1), "mse": torch.stack(rows["eps_mse"], dim=1)}
+
+
+class SpacedDiffusion(_LossEvaluation, Tables):
     """Respaced ancestral sampler (reference respace.py:65-114 + gaussian_diffusion.py:404-547) with every branch of
     p_mean_variance that `create_diffusion` can select (gaussian_diffusion.py:303-349): the model predicts the noise
     (EPSILON, the default) or x_0 (START_X, test.py --predict_xstart); the variance is the learned range
@@ -429,7 +595,9 @@ def create_diffusion(timestep_respacing, noise_schedule="linear", use_kl=False, 
     mean_type = ModelMeanType.START_X if predict_xstart else ModelMeanType.EPSILON
     var_type = ModelVarType.LEARNED_RANGE if learn_sigma else (ModelVarType.FIXED_SMALL if sigma_small
                                                                else ModelVarType.FIXED_LARGE)
+    # reference diffusion_and_flow/__init__.py:44-50
+    loss_type = LossType.RESCALED_KL if use_kl else (LossType.RESCALED_MSE if rescale_learned_sigmas else LossType.MSE)
     return SpacedDiffusion(use_timesteps=space_timesteps(diffusion_steps, timestep_respacing),
                            betas=named_betas(noise_schedule, diffusion_steps),
                            model_mean_type=mean_type, model_var_type=var_type,
-                           loss_type=None, self_condition=self_condition)
+                           loss_type=loss_type, self_condition=self_condition)

@@ -393,6 +393,293 @@ class Denoiser:
                 self.check_status(job)
         return outs
 
+    # -- forward-only loss evaluation -------------------------------------------------------------
+    @staticmethod
+    def loss_table(tables, coef=None):
+        """(device-ready [T, 16] fp32 numpy table, T): `coef` or the default sampler's Tables.loss_coefficients()."""
+        coef = tables.loss_coefficients() if coef is None else coef
+        coef = np.ascontiguousarray(coef, dtype=np.float32)
+        if coef.shape != (tables.num_timesteps, tables.LOSS_COLUMNS):
+            raise ValueError(f"coef must be a Tables.loss_coefficients table [{tables.num_timesteps}, "
+                             f"{tables.LOSS_COLUMNS}], got {coef.shape}")
+        return coef
+
+    @staticmethod
+    def sample_offsets(lens, device):
+        """Device int32 [n_samples + 1]: first node of every sample, the node ranges of the loss kernels."""
+        off = np.concatenate([[0], np.cumsum(np.asarray(lens, dtype=np.int64))])
+        if (np.diff(off) < 1).any() or off[-1] >= 2 ** 31 // 3:
+            raise ValueError("every sample needs at least one node (and all of them fit 32-bit element indices)")
+        return torch.from_numpy(off.astype(np.int32)).to(device)
+
+    @staticmethod
+    def _timesteps(t, n_samples, T, device):
+        """t: one value or one per sample -> (list of ints, shared value or None, device int32 [n_samples] or None)."""
+        if isinstance(t, torch.Tensor):
+            t = t.reshape(-1).tolist()
+        ts = [int(t)] * n_samples if np.ndim(t) == 0 else [int(v) for v in t]
+        if len(ts) != n_samples:
+            raise ValueError(f"t must be one value or one per sample ({n_samples}), got {len(ts)}")
+        if min(ts) < 0 or max(ts) >= T:
+            raise ValueError(f"t must lie in [0, {T}), got {min(ts)} .. {max(ts)}")
+        if len(set(ts)) == 1:
+            return ts, ts[0], None
+        return ts, None, torch.tensor(ts, dtype=torch.int32, device=device)
+
+    @staticmethod
+    def q_affine(kind, a, b, lens, t, coef):
+        """The forward process on flat [n, 3] latents, samples of `lens` nodes each, t one value or one per sample, coef a
+        Tables.loss_coefficients table.  kind "q_sample": sqrt_acp * a + sqrt(1 - acp) * b (b = noise; None: the mean of
+        q_mean_variance) -> (x_t, 1 - acp, log(1 - acp)); "q_posterior": post_coef1 * a + post_coef2 * b (a = x_start,
+        b = x_t) -> (mean, posterior_variance, posterior_log_variance_clipped); the last two broadcast to a's shape."""
+        _require_cuda(a, "x_start")
+        a = a.contiguous().float()
+        if b is not None:
+            _require_cuda(b, "noise" if kind == "q_sample" else "x_t")
+            b = b.contiguous().float()
+            if b.shape != a.shape:
+                raise ValueError(f"{kind}: operands differ in shape, {tuple(a.shape)} and {tuple(b.shape)}")
+        if a.numel() != 3 * int(sum(lens)):
+            raise ValueError(f"{kind}: {a.numel()} values for {int(sum(lens))} nodes of 3 channels")
+        T = coef.shape[0]
+        _ts, shared, t_dev = Denoiser._timesteps(t, len(lens), T, a.device)
+        off = Denoiser.sample_offsets(lens, a.device)
+        coef_dev = torch.from_numpy(np.ascontiguousarray(coef, dtype=np.float32)).to(a.device)
+        out, var, logvar = torch.empty_like(a), torch.empty_like(a), torch.empty_like(a)
+        fn = {"q_sample": _lib.lib().codlad_q_sample, "q_posterior": _lib.lib().codlad_q_posterior}[kind]
+        rc = fn(_lib.ptr(a), _lib.ptr(b), _lib.ptr(coef_dev), T, _lib.ptr(off), len(lens), _lib.ptr(t_dev),
+                0 if shared is None else shared, _lib.ptr(out), _lib.ptr(var), _lib.ptr(logvar), _lib.stream_ptr(a.device))
+        _lib.check(rc, f"codlad_{kind}")
+        return out, var, logvar
+
+    LOSS_KEYS = ("kl", "nll", "vb", "mse", "xstart_mse", "eps_mse")
+
+    @staticmethod
+    def _loss_outputs(n_samples, n_nodes, device, noise):
+        res = {k: torch.empty(n_samples, dtype=torch.float32, device=device) for k in Denoiser.LOSS_KEYS
+               if noise is not None or k not in ("mse", "eps_mse")}
+        res["pred_xstart"] = torch.empty(n_nodes, 3, dtype=torch.float32, device=device)
+        terms = _lib.LossTerms()
+        for k, v in res.items():
+            setattr(terms, k, v.data_ptr())
+        return res, terms
+
+    @staticmethod
+    def vb_terms(model_out, x_start, x_t, noise, lens, t, coef):
+        """_vb_terms_bpd / training_losses / calc_bpd_loop terms from a given model output (codlad_vb_terms): flat [n, 3]
+        latents, model_out [n, 6] ([n, 3] under the table's fixed-variance bit), samples of `lens` nodes, t one value or
+        one per sample -> {kl, nll, vb, xstart_mse [n_samples], pred_xstart [n, 3]; mse, eps_mse when noise is given}."""
+        _require_cuda(x_start, "x_start")
+        x_start = x_start.contiguous().float()
+        n = int(sum(lens))
+        coef = np.ascontiguousarray(coef, dtype=np.float32)
+        _check_step_operands(x_start.reshape(n, 3), model_out, coef[0, :8], x_t=x_t, noise=noise)
+        T = coef.shape[0]
+        _ts, shared, t_dev = Denoiser._timesteps(t, len(lens), T, x_start.device)
+        off = Denoiser.sample_offsets(lens, x_start.device)
+        coef_dev = torch.from_numpy(coef).to(x_start.device)
+        nz = None if noise is None else noise.contiguous().float()
+        res, terms = Denoiser._loss_outputs(len(lens), n, x_start.device, nz)
+        rc = _lib.lib().codlad_vb_terms(_lib.ptr(model_out.contiguous().float()), _lib.ptr(x_start),
+                                        _lib.ptr(x_t.contiguous().float()), _lib.ptr(nz), _lib.ptr(coef_dev), T,
+                                        _lib.ptr(off), len(lens), _lib.ptr(t_dev), 0 if shared is None else shared,
+                                        C.byref(terms), _lib.stream_ptr(x_start.device))
+        _lib.check(rc, "codlad_vb_terms")
+        return res
+
+    def _job_offsets(self, job):
+        if getattr(job, "sample_off_dev", None) is None:
+            job.sample_off_dev = self.sample_offsets(job.sample_lens, self.device)
+        return job.sample_off_dev
+
+    def q_sample(self, job, x_start, t, noise, tables, coef=None):
+        """x_t [n_nodes, 3] = q_sample(x_start, t, noise) on the job's samples; t one respaced step or one per sample."""
+        assert x_start.shape == (job.n_nodes, 3) and noise.shape == (job.n_nodes, 3)
+        return self.q_affine("q_sample", x_start, noise, job.sample_lens, t, self.loss_table(tables, coef))[0]
+
+    def _t_group_job(self, job, members, start):
+        """The ragged sub-job of the samples `members` of `job` -> (job, node indices of its samples in `job`).  Like
+        Job.parts, it keeps its edge state in a slice of the parent's buffer, from node `start` (the groups of a call are
+        disjoint, and a job and its sub-jobs are never in flight together); the small tables are its own.  Cached on the
+        job, which keeps the tensors alive: that pays when a grouping recurs (a fixed evaluation schedule, a shared
+        timestep pattern per batch); with random timesteps it rarely does, so the cache is kept small."""
+        cache = job.__dict__.setdefault("_t_groups", {})
+        key = (start, tuple(members))
+        if key not in cache:
+            if len(cache) >= 64:
+                cache.clear()
+            n = int(sum(job.sample_lens[m] for m in members))
+            sub = Job(job.structures, [job.sample_struct[m] for m in members], self.device,
+                      edge_state=job.hE[start:start + n])
+            idx = np.concatenate([np.arange(job.sample_off[m], job.sample_off[m + 1]) for m in members])
+            cache[key] = (sub, torch.from_numpy(idx).to(self.device))
+        return cache[key]
+
+    def _check_all(self, jobs):
+        """check_status on every job - each one's sticky word is read and reset - and then the first failure raised."""
+        first = None
+        for jb in jobs:
+            try:
+                self.check_status(jb)
+            except RuntimeError as e:
+                first = first or e
+        if first is not None:
+            raise first
+
+    def _on_streams(self, tasks, n_streams=2):
+        """Runs the callables round-robin on up to n_streams side streams (sample_many's arrangement) -> their results."""
+        if not hasattr(self, "_streams"):
+            self._streams = []
+        n_streams = min(n_streams, len(tasks))
+        while len(self._streams) < n_streams:
+            self._streams.append(torch.cuda.Stream(device=self.device))
+        cur = torch.cuda.current_stream(self.device)
+        for st in self._streams[:n_streams]:
+            st.wait_stream(cur)
+        outs = []
+        for k, task in enumerate(tasks):
+            with torch.cuda.stream(self._streams[k % n_streams]):
+                outs.append(task())
+        for st in self._streams[:n_streams]:
+            cur.wait_stream(st)
+        return outs
+
+    def _loss_forward(self, job, x_start, x_t, noise, t, coef_dev, T, mods, x_self_cond, want_model_out):
+        st = job.structures
+        res, terms = self._loss_outputs(len(job.sample_struct), job.n_nodes, self.device, noise)
+        if want_model_out:
+            res["model_out"] = torch.empty(job.n_nodes, self.weights.out_dim, dtype=torch.float32, device=self.device)
+        rc = self.lib.codlad_loss_forward(C.byref(self.weights.struct), _lib.ptr(job.node_info), job.n_nodes,
+                                          _lib.ptr(st.E_idx), _lib.ptr(st.h_E0), _lib.ptr(st.E1), st.n_snodes,
+                                          _lib.ptr(x_start), _lib.ptr(x_t), _lib.ptr(noise), _lib.ptr(x_self_cond),
+                                          _lib.ptr(mods[t]), _lib.ptr(coef_dev), T, t, _lib.ptr(self._job_offsets(job)),
+                                          len(job.sample_struct), _lib.ptr(res.get("model_out")), C.byref(terms),
+                                          C.byref(job.ws), _lib.stream_ptr(self.device))
+        _lib.check(rc, "codlad_loss_forward")
+        return res
+
+    def _check_loss_model(self, coef):
+        fixed_var = bool(int(coef[0, 7]) & 2)
+        if self.weights.out_dim != (3 if fixed_var else 6):
+            raise ValueError("the loss needs a model with 6 outputs (mean | variance logits), or 3 with a fixed-variance "
+                             "diffusion (create_diffusion(learn_sigma=False))")
+
+    def loss_terms(self, job, x_start, t, noise, tables, coef=None, x_t=None, x_self_cond=None, check=True,
+                   want_model_out=False):
+        """One denoiser forward on x_t = q_sample(x_start, t, noise) and the loss terms per sample (codlad_loss_forward):
+        {kl, nll, vb, mse, xstart_mse, eps_mse [n_samples], pred_xstart [n_nodes, 3] (, model_out)}; mse is
+        training_losses' (target by the mean type), xstart_mse / eps_mse are calc_bpd_loop's.
+        t: one respaced step, or one per sample: the samples are then grouped by equal t and every group runs as a ragged
+        sub-job at its t, on two streams; a sample's result does not depend on what shares its job, so the result is, bit
+        for bit, that of calling each group alone.  x_t: given instead of computed (noise may then be None: no mse /
+        eps_mse).  coef: the Tables.loss_coefficients table when it is not the default diffusion's."""
+        coef = self.loss_table(tables, coef)
+        self._check_loss_model(coef)
+        T, S = tables.num_timesteps, len(job.sample_struct)
+        _require_cuda(x_start, "x_start")
+        x_start = x_start.contiguous().float()
+        assert x_start.shape == (job.n_nodes, 3)
+        if noise is not None:
+            _require_cuda(noise, "noise")
+            noise = noise.contiguous().float()
+            assert noise.shape == x_start.shape
+        if x_t is None:
+            if noise is None:
+                raise ValueError("loss_terms needs noise or x_t")
+            x_t = self.q_sample(job, x_start, t, noise, tables, coef)
+        else:
+            _require_cuda(x_t, "x_t")
+            x_t = x_t.contiguous().float()
+            assert x_t.shape == x_start.shape
+        if x_self_cond is not None:
+            if not self.self_condition:
+                raise ValueError("x_self_cond given to a model built without self_condition")
+            _require_cuda(x_self_cond, "x_self_cond")
+            x_self_cond = x_self_cond.contiguous().float()
+            assert x_self_cond.shape == x_start.shape
+        ts, shared, _t_dev = self._timesteps(t, S, T, self.device)
+        self._fresh_features(job.structures)
+        mods = self.step_mods(tables.timestep_map)
+        coef_dev = torch.from_numpy(coef).to(self.device)
+        if shared is not None:
+            res = self._loss_forward(job, x_start, x_t, noise, shared, coef_dev, T, mods, x_self_cond, want_model_out)
+            if check:
+                self.check_status(job)
+            return res
+        groups = [(tv, [m for m in range(S) if ts[m] == tv]) for tv in sorted(set(ts))]
+        subs, start = [], 0
+        for _tv, members in groups:
+            subs.append(self._t_group_job(job, members, start))
+            start += subs[-1][0].n_nodes
+        pick = lambda a, i: None if a is None else a[i]            # noqa: E731
+        tasks = [lambda tv=tv, sub=sub, i=i: self._loss_forward(sub, x_start[i], x_t[i], pick(noise, i), tv, coef_dev, T,
+                                                                mods, pick(x_self_cond, i), want_model_out)
+                 for (tv, _m), (sub, i) in zip(groups, subs)]
+        outs = self._on_streams(tasks)
+        res = {}
+        for (_tv, members), (sub, i), o in zip(groups, subs, outs):
+            m = torch.tensor(members, dtype=torch.int64, device=self.device)
+            for k, v in o.items():
+                per_node = k in ("pred_xstart", "model_out")
+                if k not in res:
+                    res[k] = torch.empty((job.n_nodes if per_node else S,) + tuple(v.shape[1:]), dtype=v.dtype,
+                                         device=self.device)
+                res[k][i if per_node else m] = v
+        if check:
+            self._check_all([sub for sub, _i in subs])
+        return res
+
+    def bpd(self, job, x_start, noise, tables, streams=None, coef=None, check=True):
+        """The variational bound in bits per dimension over all T steps, fused (codlad_bpd_loop; the IDDPM release's
+        calc_bpd_loop): x_start [n_nodes, 3], noise [T, n_nodes, 3] in loop order (entry 0 at step T-1) ->
+        {total_bpd, prior_bpd [n_samples]; vb, mse, xstart_mse [T, n_samples], row i = respaced step i}.
+        streams as for `sample`: None = two half-jobs on two streams from SPLIT_MIN_NODES nodes up."""
+        coef = self.loss_table(tables, coef)
+        self._check_loss_model(coef)
+        T, S = tables.num_timesteps, len(job.sample_struct)
+        _require_cuda(x_start, "x_start")
+        _require_cuda(noise, "noise")
+        assert x_start.shape == (job.n_nodes, 3) and noise.shape == (T, job.n_nodes, 3)
+        if streams is None:
+            streams = 2 if job.n_nodes >= self.SPLIT_MIN_NODES and S >= 2 else 1
+        self._fresh_features(job.structures)
+        mods = self.step_mods(tables.timestep_map)
+        coef_dev = torch.from_numpy(coef).to(self.device)
+
+        def run(jb, x0, eps):
+            x0, eps = x0.contiguous().float(), eps.contiguous().float()
+            n = len(jb.sample_struct)
+            f32 = dict(dtype=torch.float32, device=self.device)
+            out = {k: torch.empty(T, n, **f32) for k in ("vb", "mse", "xstart_mse")}
+            out.update({k: torch.empty(n, **f32) for k in ("prior_bpd", "total_bpd")})
+            x_t = torch.empty_like(x0)
+            st = jb.structures
+            rc = self.lib.codlad_bpd_loop(C.byref(self.weights.struct), _lib.ptr(jb.node_info), jb.n_nodes,
+                                          _lib.ptr(st.E_idx), _lib.ptr(st.h_E0), _lib.ptr(st.E1), st.n_snodes, _lib.ptr(x0),
+                                          _lib.ptr(eps), _lib.ptr(x_t), _lib.ptr(mods), _lib.ptr(coef_dev), T,
+                                          _lib.ptr(self._job_offsets(jb)), n, _lib.ptr(out["vb"]), _lib.ptr(out["mse"]),
+                                          _lib.ptr(out["xstart_mse"]), _lib.ptr(out["prior_bpd"]),
+                                          _lib.ptr(out["total_bpd"]), C.byref(jb.ws), _lib.stream_ptr(self.device))
+            _lib.check(rc, "codlad_bpd_loop")
+            return out
+
+        if streams <= 1:
+            res = run(job, x_start, noise)
+            if check:
+                self.check_status(job)
+            return res
+        parts = job.parts(streams)
+        outs = self._on_streams([lambda p=p, i=i: run(p, x_start[i], noise[:, i]) for p, i in parts], streams)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        res = {k: torch.empty(T, S, **f32) for k in ("vb", "mse", "xstart_mse")}
+        res.update({k: torch.empty(S, **f32) for k in ("prior_bpd", "total_bpd")})
+        for p, o in enumerate(outs):
+            for k, v in o.items():
+                res[k][..., p::streams] = v
+        if check:
+            self._check_all([p for p, _i in parts])
+        return res
+
     @staticmethod
     def _pin_arrays(pin, n_nodes):
         """(x0, mask) -> (x0 fp32 [n_nodes,3] contiguous, mask uint8 [n_nodes]) on the GPU, checked."""

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define CODLAD_ABI_VERSION 16
+#define CODLAD_ABI_VERSION 17
 #define CODLAD_H 128          /* hidden width of the denoiser                          */
 #define CODLAD_KNN 64         /* k_neighbors (reference models/latent_model.py:86)      */
 #define CODLAD_MODS_PER_STEP 6016 /* 3*9*128 (enc) + 3*6*128 (dec) + 2*128 (final)      */
@@ -326,6 +326,78 @@ int codlad_ddim_loop(const codlad_denoiser_weights *w, const int32_t *node_info,
 int codlad_ddim_step(const float *x, const float *pred_xstart, const float *noise /* NULL iff reverse */,
                      const float *grad /* may be NULL */, const float *coef_host, int reverse, int n_nodes, float *x_out,
                      float *x_start_out /* may be NULL */, void *stream);
+
+/* Forward-only loss evaluation (gaussian_diffusion.py:211-260, 549-725; the IDDPM release's calc_bpd_loop / _prior_bpd).
+ *
+ * Samples are node ranges: sample s owns nodes sample_off[s] .. sample_off[s + 1] - 1 (device int32 [n_samples + 1]).
+ * Precondition (device memory, not checked by the host): sample_off is non-decreasing from >= 0 and ends within the node
+ * arrays (at n_nodes for the entries that run the denoiser); a sample with an empty range is skipped: its results are not
+ * written.  Its
+ * respaced step is t_of_sample[s] (device int32 [n_samples]), or `t` for every sample when t_of_sample is NULL.
+ * coef (device) [T][16] = Tables.loss_coefficients, every entry the float64 table value cast to fp32:
+ *   {sqrt_recip_acp, sqrt_recipm1_acp, post_coef1, post_coef2, model log variance (minimum of the learned range, or THE log
+ *    variance under mode bit 2), log_beta, posterior_log_variance_clipped, mode, sqrt_acp, sqrt(1 - acp), 1 - acp,
+ *    log(1 - acp), posterior_variance, 0, 0, 0}; the mode bits are those of the step table above.
+ * Every product, sum and quotient is rounded separately, as the reference's elementwise tensor ops round.
+ *
+ * Per-sample results (each pointer may be NULL): the means over the sample's own L x 3 elements of
+ *   kl          normal_kl(true posterior, model posterior) / ln 2
+ *   nll         -discretized_gaussian_log_likelihood(x_start; model mean, 0.5 * model log variance) / ln 2
+ *   vb          nll where the sample's step is 0, else kl (_vb_terms_bpd's "output")
+ *   mse         (target - model mean output)^2, target = noise, or x_start under mode bit 1 (training_losses)
+ *   xstart_mse  (pred_xstart - x_start)^2                                             (calc_bpd_loop)
+ *   eps_mse     (eps - noise)^2, eps recomputed from pred_xstart (_predict_eps_from_xstart)  (calc_bpd_loop)
+ * and pred_xstart [n_nodes][3].  mse and eps_mse are written only when noise is given.  The sums run in a fixed order that
+ * depends on the sample's length alone (no floating-point atomics): the same bits whatever else shares the call. */
+typedef struct {
+    float *kl, *nll, *vb, *mse, *xstart_mse, *eps_mse;   /* [n_samples] each */
+    float *pred_xstart;                                  /* [n_nodes][3] */
+} codlad_loss_terms;
+
+/* x_t = sqrt_acp * x_start + sqrt(1 - acp) * noise (q_sample).  noise NULL: x_t = sqrt_acp * x_start, q_mean_variance's
+ * mean.  variance / log_variance [n_nodes][3] (may be NULL) receive 1 - acp / log(1 - acp) (q_mean_variance). */
+int codlad_q_sample(const float *x_start, const float *noise /* may be NULL */, const float *coef, int T,
+                    const int32_t *sample_off, int n_samples, const int32_t *t_of_sample /* may be NULL */, int t, float *x_t,
+                    float *variance /* may be NULL */, float *log_variance /* may be NULL */, void *stream);
+
+/* q_posterior_mean_variance: mean = post_coef1 * x_start + post_coef2 * x_t; variance / log_variance (may be NULL) receive
+ * posterior_variance / posterior_log_variance_clipped. */
+int codlad_q_posterior(const float *x_start, const float *x_t, const float *coef, int T, const int32_t *sample_off,
+                       int n_samples, const int32_t *t_of_sample /* may be NULL */, int t, float *mean,
+                       float *variance /* may be NULL */, float *log_variance /* may be NULL */, void *stream);
+
+/* The terms above from a given model output: model_out [n_nodes][6] (mean | variance logits), or [n_nodes][3] under mode
+ * bit 2.  Stand-alone, as codlad_ddpm_update is for the sampling loop. */
+int codlad_vb_terms(const float *model_out, const float *x_start, const float *x_t, const float *noise /* may be NULL */,
+                    const float *coef, int T, const int32_t *sample_off, int n_samples,
+                    const int32_t *t_of_sample /* may be NULL */, int t, const codlad_loss_terms *terms, void *stream);
+
+/* prior_bpd [n_samples] = mean of normal_kl(q(x_{T-1} | x_start), N(0, 1)) / ln 2 (the IDDPM release's _prior_bpd). */
+int codlad_prior_bpd(const float *x_start, const float *coef, int T, const int32_t *sample_off, int n_samples,
+                     float *prior_bpd, void *stream);
+
+/* One denoiser forward on x_t at respaced step t (mods_t = that step's modulation floats) followed by the terms above,
+ * the final layer fused into their kernel: its head gives the bits of codlad_denoiser_forward's output.  model_out
+ * [n_nodes][out_dim] (may be NULL) receives that output.  x_self_cond as for codlad_denoiser_forward.  The workspace's
+ * status word is set as by every forward. */
+int codlad_loss_forward(const codlad_denoiser_weights *w, const int32_t *node_info, int n_nodes, const int32_t *E_idx,
+                        const float *h_E0, const float *E1, int n_snodes, const float *x_start, const float *x_t,
+                        const float *noise /* may be NULL */, const float *x_self_cond /* may be NULL */,
+                        const float *mods_t, const float *coef, int T, int t, const int32_t *sample_off, int n_samples,
+                        float *model_out /* may be NULL */, const codlad_loss_terms *terms, const codlad_workspace *ws,
+                        void *stream);
+
+/* The variational bound over all T steps, fused (calc_bpd_loop): for i = T-1 .. 0, x_t = q_sample of x_start with noise
+ * entry T-1-i (loop order, as the sampling loops consume theirs) at step i, one forward with mods row i, then the terms
+ * into row i of vb, mse (calc_bpd_loop's: eps_mse above) and xstart_mse, each [T][n_samples]; then prior_bpd
+ * [n_samples] and total_bpd [n_samples] = vb summed in loop order, + prior_bpd.  x_t [n_nodes][3] is scratch.  No host
+ * synchronisation; the sticky status word as in the sampling loops.  A self-conditioned model is conditioned on zeros
+ * (calc_bpd_loop has no self-conditioning). */
+int codlad_bpd_loop(const codlad_denoiser_weights *w, const int32_t *node_info, int n_nodes, const int32_t *E_idx,
+                    const float *h_E0, const float *E1, int n_snodes, const float *x_start, const float *noise,
+                    float *x_t, const float *mods, const float *coef, int T, const int32_t *sample_off, int n_samples,
+                    float *vb, float *mse, float *xstart_mse, float *prior_bpd, float *total_bpd,
+                    const codlad_workspace *ws, void *stream);
 
 /* Row 8: get_norm_feature(norm_in=False) + nearest code
  * (utils/dataset_module.py:253; utils/vq_module.py:61-68 / VectorQuantize eval lookup).

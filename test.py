@@ -15,6 +15,9 @@ them) or `--synthetic` (no PED/PDB/Atlas files ship with the reference).
 Addition: `--fix_residues SPEC` keeps the VQ-VAE encoder's latents of the chosen residues (residue pinning, a
 `PinLatents` denoised_fn) and samples the rest of each structure conditioned on them.
 Addition: `--sampler ddim [--eta E]` samples the latents with DDIM (ddim_sample_loop) instead of the ancestral DDPM loop.
+Addition: `--experiment bpd` scores the checkpoint instead of sampling from it: the variational bound in bits per dimension
+(calc_bpd_loop over --num_sampling_steps respaced steps, one fused loop per batch) of the batch's own VQ-VAE latents; prints
+the mean total_bpd / prior_bpd per file and saves vb / mse / xstart_mse [N, T] as .npy.  One rank only.
 """
 import argparse
 import os
@@ -123,10 +126,26 @@ def check_sampler(args):
                          "its ODE solver")
 
 
+def check_bpd(args, world):
+    """--experiment bpd: the variational bound of the batch's own latents under the diffusion model."""
+    if args.experiment != "bpd":
+        return
+    if world > 1:
+        raise SystemExit("--experiment bpd runs on one rank: gathering its per-step tables across ranks is not built "
+                         f"(WORLD_SIZE={world})")
+    if args.model != "diffusion":
+        raise SystemExit(f"--experiment bpd needs --model diffusion: {args.model!r} is a flow-matching model, which has no "
+                         "variational bound")
+    if args.vae_type not in ("N6", "K3", "K4"):
+        raise SystemExit(f"--experiment bpd needs a VQ-VAE (N6 / K3 / K4) to encode the structures, not {args.vae_type!r}")
+    if not (args.synthetic or getattr(args, "pdb_files", None) or args.data_process):
+        raise SystemExit("--experiment bpd needs input with atoms: --pdb_files, --data_process --data_files or --synthetic")
+
+
 def load_vae(args, device, load=True):
     """The VQ-VAE; with its e3nn encoder when the run needs it (`--experiment recon` encodes the batch's atoms, so does
-    --fix_residues for the latents it pins)."""
-    enc = args.experiment == "recon" or getattr(args, "fix_residues", None) is not None
+    --fix_residues for the latents it pins and `--experiment bpd` for the latents it scores)."""
+    enc = args.experiment in ("recon", "bpd") or getattr(args, "fix_residues", None) is not None
     if not load:
         return build_vae(args.vae_type, with_encoder=enc).to(device).eval()
     if args.synthetic_weights:
@@ -189,7 +208,7 @@ def iter_batches(args):
                 _TOPOLOGY[out] = (names, [synth.PDB_ATOM_ORDER[nm] for nm in names])
                 batch = synth.make_batch(prot, range(a, b))
                 # the encoder reads the all-atom side of the batch (recon; the known latents of --fix_residues)
-                if getattr(args, "experiment", "latent") == "recon" or getattr(args, "fix_residues", None) is not None:
+                if getattr(args, "experiment", "latent") in ("recon", "bpd") or getattr(args, "fix_residues", None) is not None:
                     batch.update(synth.make_atoms(prot, range(a, b), seed=1000 + i))
                 yield out, batch, prot["info"]
         return
@@ -288,6 +307,7 @@ def main(args):
     # one process per GPU under torch.distributed.run: batches (independent units) are dealt to the
     # ranks longest-first, every rank samples and decodes its own, rank 0 reports the totals
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
+    check_bpd(args, world)
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     backend = os.environ.get("CODLAD_DIST_BACKEND", "nccl")   # "gloo": rehearsal of N > 1 on a one-GPU box
     dev_index = local_rank if backend == "nccl" else local_rank % torch.cuda.device_count()
@@ -315,7 +335,7 @@ def main(args):
     model, cvae = None, None
     if args.experiment == "genzprot":
         cvae = load_cvae(args, device, load=rank == 0)
-    if args.experiment == "latent":
+    if args.experiment in ("latent", "bpd"):
         model = load_denoiser(args, device, load=rank == 0)
         diffusion = None if args.model != "diffusion" else create_diffusion(str(args.num_sampling_steps), noise_schedule=args.noise_schedule,
                                      predict_xstart=args.predict_xstart,
@@ -323,7 +343,7 @@ def main(args):
                                      # reference test.py:297-303
                                      self_condition=hasattr(model, "self_condition") and args.self_condition)
     elif args.experiment not in ("recon", "genzprot"):
-        raise NotImplementedError(f"experiment {args.experiment!r}: latent, recon and genzprot are built")
+        raise NotImplementedError(f"experiment {args.experiment!r}: latent, recon, genzprot and bpd are built")
     if world > 1:
         from codlad_amd import parallel
         mods = [m for m in (model, vae, cvae) if m is not None]
@@ -354,6 +374,22 @@ def main(args):
         mask = torch.ones(B * E, L, dtype=torch.bool, device=device)
         # E ensemble members of every frame = the batch repeated E times along the sample axis
         rep = {k: v for k, v in batch.items()}
+        if args.experiment == "bpd":
+            # the frames' own latents (the VQ-VAE encoder on the batch's atoms, normalised exactly as --fix_residues
+            # normalises its known latents) scored by the variational bound over the respaced steps: one fused loop
+            x0 = get_norm_feature(vae.get_latent_wovq(batch)[0], args.vae_type, norm_channel=args.norm,
+                                  norm_single=args.norm_single, norm_in=True, dataname=args.data_type).contiguous()
+            r = diffusion.calc_bpd_loop(model.forward, x0, clip_denoised=False,
+                                        model_kwargs=dict(y=None, mask=mask[:B], batch=rep),
+                                        step_noise=diffusion._draw_noise(x0, generator=gen))
+            torch.cuda.synchronize()
+            dt = time.time() - st
+            total += B
+            for key in ("vb", "mse", "xstart_mse"):                 # [N, T], column k = step T-1-k (the IDDPM layout)
+                np.save(os.path.join(save_dir, f"{name}_bpd_{key}.npy"), r[key].cpu().numpy())
+            print(f"{name}: {B} frames, L={L}, T={diffusion.num_timesteps}: total_bpd {float(r['total_bpd'].mean()):.6f} "
+                  f"prior_bpd {float(r['prior_bpd'].mean()):.6e}: {dt:.2f}s ({B / dt:.1f} structures/s)", flush=True)
+            continue
         if args.experiment == "latent":
             z = torch.randn(B * E, L, args.latent_size, device=device, generator=gen)
             if args.model == "diffusion":
@@ -445,7 +481,7 @@ if __name__ == "__main__":
     p.add_argument("--predict_xstart", action="store_true", default=False)
     p.add_argument("--rescale_learned_sigmas", action="store_true", default=False)
     p.add_argument("--noise_schedule", type=str, default="linear", choices=["linear", "squaredcos_cap_v2"])
-    p.add_argument("--experiment", type=str, default="latent", choices=["genzprot", "recon", "latent"])
+    p.add_argument("--experiment", type=str, default="latent", choices=["genzprot", "recon", "latent", "bpd"])
     p.add_argument("--ckpt_type", type=str, default="net")
     p.add_argument("--sample_index", type=int, default=0)
     for ignored, kw in (("--compute_nfe", dict(action="store_true")), ("--iteration", dict(type=int, default=1000)),

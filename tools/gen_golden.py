@@ -701,6 +701,252 @@ def g18_ddim(ref, model):
         save(f"g18_ddim_{name}", **arrays)
 
 
+def loss_reference_terms(d, out, x_start, x_t, noise, t, mask, clip_denoised):
+    """Every per-sample term of the loss kernels from a given model output, by the reference's own functions
+    (q_posterior_mean_variance, p_mean_variance, normal_kl, discretized_gaussian_log_likelihood, mean_flat,
+    _predict_eps_from_xstart), composed as _vb_terms_bpd / training_losses / calc_bpd_loop compose them; in the dtype of
+    the tensors handed in (fp32, or float64 for the `.double()` evaluation: the schedule values stay the fp32 ones of
+    _extract_into_tensor).  -> dict of [N] tensors + pred_xstart."""
+    import diffusion_and_flow.gaussian_diffusion as gd
+    from diffusion_and_flow.diffusion_utils import discretized_gaussian_log_likelihood, normal_kl
+    if x_start.dtype == torch.float64 and torch.get_default_dtype() != torch.float64:
+        # _extract_into_tensor broadcasts by adding zeros of the DEFAULT dtype: with fp32 zeros the table log variances
+        # of a fixed-variance model stay fp32 tensors and exp() of them runs in fp32 inside the "double" evaluation
+        torch.set_default_dtype(torch.float64)
+        try:
+            return loss_reference_terms(d, out, x_start, x_t, noise, t, mask, clip_denoised)
+        finally:
+            torch.set_default_dtype(torch.float32)
+    m = mask.unsqueeze(-1).expand_as(x_start)
+    true_mean, _, true_logvar = d.q_posterior_mean_variance(x_start=x_start, x_t=x_t, t=t)
+    p = d.p_mean_variance(lambda *a, r=out, **k: r, x_t, t, clip_denoised=clip_denoised, model_kwargs=None)
+    kl = gd.mean_flat(normal_kl(true_mean, true_logvar, p["mean"], p["log_variance"]), m) / np.log(2.0)
+    nll = gd.mean_flat(-discretized_gaussian_log_likelihood(x_start, means=p["mean"], log_scales=0.5 * p["log_variance"]),
+                       m) / np.log(2.0)
+    mean_out = out[..., :3]
+    target = x_start if d.model_mean_type == gd.ModelMeanType.START_X else noise
+    eps = d._predict_eps_from_xstart(x_t, t, p["pred_xstart"])
+    return dict(kl=kl, nll=nll, vb=torch.where(t == 0, nll, kl), mse=gd.mean_flat((target - mean_out) ** 2, m),
+                xstart_mse=gd.mean_flat((p["pred_xstart"] - x_start) ** 2), eps_mse=gd.mean_flat((eps - noise) ** 2),
+                pred_xstart=p["pred_xstart"])
+
+
+def g19_losses(ref, model):
+    """Forward-only loss evaluation (tests/loss_cases.py): the reference's own q_sample / q_mean_variance /
+    q_posterior_mean_variance / training_losses / _vb_terms_bpd on the seeded denoiser; for the bound loop the loop of the
+    IDDPM release's calc_bpd_loop and its _prior_bpd RESTATED around those functions.  Every case also stores the model
+    output, the terms re-evaluated from it by the same functions in fp32 and on `.double()` tensors, and the relative
+    deviation between the two per term class (ref_dev_case; ref_dev = the largest over the cases).  The inputs of the t = 0 samples are
+    chosen clear of the likelihood's 1e-12 clamp (clear_of_the_clamp) and stored with the case."""
+    import random
+    import diffusion_and_flow.gaussian_diffusion as gd
+    from diffusion_and_flow.diffusion_utils import normal_kl
+    from tests import conditioning as cond
+    from tests import loss_cases as lc
+    print("g19 loss evaluation (q_sample, training_losses, the variational bound)")
+    models = guidance_models(ref, model)
+    T = lc.T
+    outs = {k: [] for k in models}
+    hooks = [m.register_forward_hook(lambda _m, _i, o, k=k: outs[k].append(o)) for k, m in models.items()]
+
+    def geometry_ok(L, B, seed, batch, mask, E_idx):
+        # no edge on the reference's quaternion discontinuity (tests/ddim_cases.py DDIM_TOL): 1 + trace R at rounding-noise
+        # level, where relu() of it is decided by the rounding; and the ordinary share of ill-conditioned edges
+        from oracle import denoiser as oden
+        _z, cg_xyz, _m = oden.batch_to_dense(batch)
+        cg_xyz = cg_xyz[:B]
+        q = cond.edge_quantities(cg_xyz, E_idx[:B])
+        # ... which decides the quaternion only where its vector part vanishes too (all sign arguments exactly 0: two
+        # partly zeroed frames): normalize(0, 0, 0, w) is (0, 0, 0, 1) for any w > 0 and the zero quaternion for w = 0
+        vec = (0.5 * q["r"].abs().sqrt() * (q["s"] != 0)).abs().amax(-1)
+        on_jump = (q["tr1"].abs() < 1e-6) & (vec < 1e-3)
+        assert not bool(on_jump.any()), (L, B, seed, on_jump.nonzero().tolist())
+        assert float(cond.edge_conditioning(cg_xyz, E_idx[:B]).double().mean()) <= cond.MAX_ILL_SHARE
+
+    def classes_dev(t32, t64, t):
+        # kl at every step; nll where the bound uses it (t == 0): at t > 0 _vb_terms_bpd's where() discards it, and there
+        # it is rounding noise (the model variance shrinks with t while the error of an untrained model does not)
+        dev = {"kl": 0.0, "nll": 0.0, "mse": 0.0}
+        for k, cls in lc.TERM_CLASS.items():
+            if cls is None:
+                continue
+            used = (t == 0) if cls == "nll" else torch.ones_like(t, dtype=torch.bool)
+            if bool(used.any()):
+                r = ((t32[k].double() - t64[k]).abs() / t64[k].abs().clamp_min(1e-300))[used]
+                dev[cls] = max(dev[cls], float(r.max()))
+        return np.array([dev["kl"], dev["nll"], dev["mse"]])
+
+    def t0_branches(x_start, p_mean, p_logvar, t):
+        """(elements in the three branches of the discretized likelihood, middle-branch elements on the 1e-12 clamp, those
+        within 1e-6 of it: there the difference of two fp32 CDF values, each good to 6e-8, has few digits left) over the
+        t == 0 samples, evaluated in float64."""
+        from diffusion_and_flow.diffusion_utils import approx_standard_normal_cdf
+        sel = t == 0
+        x, mu, ls = x_start[sel].double(), p_mean[sel].double(), 0.5 * p_logvar[sel].double()
+        delta = approx_standard_normal_cdf(torch.exp(-ls) * (x - mu + 1.0 / 255.0)) - \
+            approx_standard_normal_cdf(torch.exp(-ls) * (x - mu - 1.0 / 255.0))
+        mid = (x >= -0.999) & (x <= 0.999)
+        return (np.array([int((x < -0.999).sum()), int((x > 0.999).sum()), int(mid.sum())]), int((mid & (delta < 1e-11)).sum()),
+                int((mid & (delta < 1e-6)).sum()))
+
+    def clear_of_the_clamp(d, net, x_start, noise, t, mask, batch, seed):
+        """The t = 0 samples' inputs chosen so that the decoder likelihood of the UNTRAINED model is well conditioned: there
+        sigma is 0.01 and a seeded model's prediction lies many sigma off a seeded x_0, on the 1e-12 clamp.  An x_0 predictor
+        gets as x_start a fixed point of x -> model(q_sample(x, 0, noise)) (the map contracts: 4 digits per iteration),
+        an eps predictor as noise a fixed point of n -> model(q_sample(x_start, 0, n)); then a seeded Gaussian of 0.7
+        sigma is added, so that the normalised error is spread over +-2 and not 0.  Returned as the fixture's inputs."""
+        sel = t == 0
+        if not bool(sel.any()):
+            return x_start, noise
+        wrapped = d._wrap_model(net)
+        xstart_model = d.model_mean_type == gd.ModelMeanType.START_X
+        x_start, noise = x_start.clone(), noise.clone()
+        for _ in range(10):
+            out = wrapped(d.q_sample(x_start, t, noise=noise), t, y=None, mask=mask, batch=batch)[..., :3]
+            (x_start if xstart_model else noise)[sel] = out[sel]
+        spread = synth.gaussian(tuple(x_start.shape), 9000 + seed)
+        if xstart_model:
+            sigma0 = float(np.exp(0.5 * d.posterior_log_variance_clipped[0]))
+            x_start[sel] = x_start[sel] + 0.7 * sigma0 * spread[sel]
+        else:
+            noise[sel] = noise[sel] + 0.7 * spread[sel]
+        return x_start, noise
+
+    files, branch_total, clamped = {}, np.zeros(3, dtype=np.int64), {}
+    d = ref["create_diffusion"](str(T), noise_schedule="linear")
+    files["g19_schedule_10"] = dict(
+        sqrt_alphas_cumprod=d.sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod=d.sqrt_one_minus_alphas_cumprod,
+        log_one_minus_alphas_cumprod=d.log_one_minus_alphas_cumprod, one_minus_alphas_cumprod=1.0 - d.alphas_cumprod,
+        posterior_variance=d.posterior_variance, ref_dev_case=np.zeros(3), t0_near_clamp=np.int64(0),
+        # every schedule value as _extract_into_tensor hands it to the formulas, at every step
+        extracted=torch.stack([gd._extract_into_tensor(a, torch.arange(T), (T,)) for a in (
+            d.sqrt_alphas_cumprod, d.sqrt_one_minus_alphas_cumprod, 1.0 - d.alphas_cumprod, d.log_one_minus_alphas_cumprod,
+            d.posterior_variance, d.posterior_log_variance_clipped, d.posterior_mean_coef1, d.posterior_mean_coef2,
+            np.log(np.append(d.posterior_variance[1], d.betas[1:])))]))
+    e_idx_tap = []
+    hook_f = model.features.register_forward_hook(lambda _m, _i, o: e_idx_tap.append(o[1]))
+    for name, (L, B, seed, n_rep, kw, loss_type, kind, ts, rseed) in lc.LOSS_CASES.items():
+        prot, batch, mask, x_start, noise = lc.inputs(L, B, seed, n_rep)
+        noise = noise[0]
+        kw = dict(noise_schedule="linear", **kw)
+        d = ref["create_diffusion"](str(T), **kw)
+        if loss_type is not None:
+            d.loss_type = gd.LossType[loss_type]
+        t = torch.tensor(ts, dtype=torch.int64)
+        assert t.shape[0] == x_start.shape[0]
+        net = models[kind]
+        x_start, noise = clear_of_the_clamp(d, net, x_start, noise, t, mask, batch, seed)
+        outs[kind].clear()
+        if d.loss_type.is_vb():
+            # the reference hands model_kwargs=None to the model on this path (gaussian_diffusion.py:565): the kwargs are
+            # bound here instead
+            fn = lambda x, tt, **k: net(x, tt, None, mask=mask, batch=batch)                  # noqa: E731
+            mk = dict(mask=mask)
+        else:
+            fn, mk = net.__call__, dict(y=None, mask=mask, batch=batch)     # (a bound method, with the forward hooks)
+        draw = -1.0
+        if rseed is not None:
+            random.seed(rseed)
+            draw = random.random()
+            assert (draw < 0.5) == ("_drawn" in name and "not_drawn" not in name), (name, draw)
+            random.seed(rseed)
+        losses = d.training_losses(fn, x_start, t, model_kwargs=mk, noise=noise)
+        assert len(outs[kind]) == (2 if 0 <= draw < 0.5 else 1)
+        out = outs[kind][-1]
+        if kind == "eps" and not e_idx_tap:
+            model(x_start[:B], t[:B] * 0 + 5, None, mask=mask[:B], batch={**batch, "randn": batch["randn"][:B]})
+        x_t = d.q_sample(x_start, t, noise=noise)
+        t32 = loss_reference_terms(d, out, x_start, x_t, noise, t, mask, False)
+        t64 = loss_reference_terms(d, out.double(), x_start.double(), x_t.double(), noise.double(), t, mask, False)
+        # the composition above is training_losses' own: its results to the bit
+        if "mse" in losses:
+            assert torch.equal(losses["mse"], t32["mse"])
+        key = "loss" if d.loss_type.is_vb() else "vb"
+        if key in losses:
+            scale = {gd.LossType.RESCALED_KL: float(T), gd.LossType.RESCALED_MSE: T / 1000.0}.get(d.loss_type, 1.0)
+            assert torch.equal(losses[key], t32["vb"] * scale if scale != 1.0 else t32["vb"]), name
+        p32 = d.p_mean_variance(lambda *a, r=out, **k: r, x_t, t, clip_denoised=False, model_kwargs=None)
+        br, on_clamp, near_clamp = t0_branches(x_start, p32["mean"], p32["log_variance"], t)
+        branch_total += br
+        assert on_clamp == 0 and near_clamp == 0, (name, on_clamp, near_clamp)
+        qm = d.q_mean_variance(x_start, t)
+        qp = d.q_posterior_mean_variance(x_start, x_t, t)
+        arrays = dict(t=t, x_start=x_start, noise=noise, x_t=x_t, model_out=out, pred_xstart=t32["pred_xstart"], random_draw=np.float64(draw),
+                      q_mean=qm[0], q_variance=qm[1], q_log_variance=qm[2], post_mean=qp[0], post_variance=qp[1],
+                      post_log_variance=qp[2], ref_dev_case=classes_dev(t32, t64, t), t0_on_clamp=np.int64(0),
+                      t0_near_clamp=np.int64(near_clamp))
+        arrays.update({"loss_" + k: v for k, v in losses.items()})
+        arrays.update({"f32_" + k: v for k, v in t32.items() if k != "pred_xstart"})
+        arrays.update({"f64_" + k: v for k, v in t64.items() if k != "pred_xstart"})
+        files["g19_loss_" + name] = arrays
+    for name, (L, B, seed, kw, kind, clip) in lc.BPD_CASES.items():
+        prot, batch, mask, x_start, eps = lc.inputs(L, B, seed, 1, n_steps=T)
+        d = ref["create_diffusion"](str(T), noise_schedule="linear", **kw)
+        net = models[kind]
+        fn = lambda x, tt, **k: net(x, tt, None, mask=mask, batch=batch)                      # noqa: E731
+        x_start, eps = x_start.clone(), eps.clone()
+        x_start, eps[T - 1] = clear_of_the_clamp(d, net, x_start, eps[T - 1], torch.zeros(x_start.shape[0], dtype=torch.int64),
+                                                 mask, batch, seed)            # (the last entry is step 0's noise)
+        rows32, rows64, model_outs, x_ts, devs = [], [], [], [], []
+        # ---- restated: the loop of the IDDPM release's calc_bpd_loop around the reference's functions ----
+        vb, xstart_mse, mse = [], [], []
+        for k, i in enumerate(range(T - 1, -1, -1)):
+            t = torch.tensor([i] * x_start.shape[0])
+            noise = eps[k]
+            x_t = d.q_sample(x_start=x_start, t=t, noise=noise)
+            outs[kind].clear()
+            out = d._vb_terms_bpd(fn, x_start=x_start, x_t=x_t, t=t, clip_denoised=clip, model_kwargs=dict(mask=mask))
+            vb.append(out["output"])
+            xstart_mse.append(gd.mean_flat((out["pred_xstart"] - x_start) ** 2))
+            e = d._predict_eps_from_xstart(x_t, t, out["pred_xstart"])
+            mse.append(gd.mean_flat((e - noise) ** 2))
+            # ---- (not part of the loop: this step's model output and the terms re-evaluated from it) ----
+            mo = outs[kind][-1]
+            t32 = loss_reference_terms(d, mo, x_start, x_t, noise, t, mask, clip)
+            t64 = loss_reference_terms(d, mo.double(), x_start.double(), x_t.double(), noise.double(), t, mask, clip)
+            assert torch.equal(t32["vb"], vb[-1]) and torch.equal(t32["xstart_mse"], xstart_mse[-1]) and \
+                torch.equal(t32["eps_mse"], mse[-1])
+            model_outs.append(mo); x_ts.append(x_t); rows32.append(t32); rows64.append(t64)
+            devs.append(classes_dev(t32, t64, t))
+            if i == 0:
+                p32 = d.p_mean_variance(lambda *a, r=mo, **k2: r, x_t, t, clip_denoised=clip, model_kwargs=None)
+                br, clamped[name], near_clamp = t0_branches(x_start, p32["mean"], p32["log_variance"], t)
+                branch_total += br
+        vb, xstart_mse, mse = torch.stack(vb, dim=1), torch.stack(xstart_mse, dim=1), torch.stack(mse, dim=1)
+        t_last = torch.tensor([T - 1] * x_start.shape[0])
+        qt_mean, _, qt_log_variance = d.q_mean_variance(x_start, t_last)
+        prior_bpd = gd.mean_flat(normal_kl(mean1=qt_mean, logvar1=qt_log_variance, mean2=0.0, logvar2=0.0)) / np.log(2.0)
+        total_bpd = vb.sum(dim=1) + prior_bpd
+        # ---- end of the restated lines ----
+        qm64 = d.q_mean_variance(x_start.double(), t_last)
+        prior64 = gd.mean_flat(normal_kl(mean1=qm64[0], logvar1=qm64[2].double(), mean2=0.0, logvar2=0.0)) / np.log(2.0)
+        assert clamped[name] == 0 and near_clamp == 0, (name, clamped[name], near_clamp)
+        arrays = dict(x_start=x_start, step_noise=eps, total_bpd=total_bpd, prior_bpd=prior_bpd, vb=vb, xstart_mse=xstart_mse, mse=mse, f64_prior_bpd=prior64,
+                      model_out=torch.stack(model_outs), x_t=torch.stack(x_ts), ref_dev_case=np.max(np.stack(devs), axis=0),
+                      t0_on_clamp=np.int64(clamped[name]), t0_near_clamp=np.int64(near_clamp))
+        for k in ("kl", "nll", "vb", "mse", "xstart_mse", "eps_mse"):      # [T, N] in loop order (row k = step T-1-k)
+            arrays["f32_" + k] = torch.stack([r[k] for r in rows32])
+            arrays["f64_" + k] = torch.stack([r[k] for r in rows64])
+        files["g19_" + name] = arrays
+    for h in hooks + [hook_f]:
+        h.remove()
+    # the geometries: none on the reference's quaternion discontinuity
+    for L, B, seed in sorted({(c[0], c[1], c[2]) for c in list(lc.LOSS_CASES.values()) + list(lc.BPD_CASES.values())}):
+        prot, batch, mask, _x, _n = lc.inputs(L, B, seed, 1)
+        _o, taps = run_forward_with_taps(model, _x, torch.full((B,), 5), mask, batch)
+        geometry_ok(L, B, seed, batch, mask, taps["features"][1])
+    # the t = 0 elements populate all three branches of the discretized likelihood (and, asserted per case above, no
+    # middle-branch element is within 1e-6 of the 1e-12 clamp)
+    assert (branch_total > 0).all(), branch_total
+    print(f"  t = 0 elements per branch (x < -0.999, x > 0.999, middle): {branch_total.tolist()}; on the clamp: {clamped}")
+    # class-wide: a case has one to four samples, too few for its own maximum to be a property of the arithmetic
+    ref_dev = np.max(np.stack([a["ref_dev_case"] for a in files.values()]), axis=0)
+    print(f"  ref_dev (kl, nll, mse): {ref_dev.tolist()}")
+    for n, a in files.items():
+        print(f"    {n}: ref_dev_case {a['ref_dev_case'].tolist()}, t = 0 elements near the clamp {int(a['t0_near_clamp'])}")
+        save(n, ref_dev=ref_dev, **a)
+
+
 def g15_e3nn_encoder_prior(ref):
     """Row 8f-1, the reference's own lines executed: e3nnPrior.forward (models/vae_model.py:275-294), e3nnEncoder.forward
     (:112-164, with build_atom / build_cg / build_cross_conv_graph :166-204) and TensorProductConvLayer.forward
@@ -790,6 +1036,7 @@ def main():
     if want("g16"): g16_sampler_branches(ref, model)
     if want("g17"): g17_guidance(ref, model)
     if want("g18"): g18_ddim(ref, model)
+    if want("g19"): g19_losses(ref, model)
 
 
 if __name__ == "__main__":
