@@ -10,7 +10,7 @@ import os
 import torch  # noqa: F401  (must precede the dlopen below)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 17   # CODLAD_ABI_VERSION of include/codlad_hip.h this binding was written against
+ABI_VERSION = 18   # CODLAD_ABI_VERSION of include/codlad_hip.h this binding was written against
 # CODLAD_HIP_LIB: an alternative build of the same ABI (A/B measurements, tools/ablate_edge.py)
 LIB_PATH = os.environ.get("CODLAD_HIP_LIB") or os.path.join(_HERE, "libcodlad_hip.so")
 
@@ -93,6 +93,21 @@ class LossTerms(C.Structure):
     _fields_ = [(n, P) for n in ("kl", "nll", "vb", "mse", "xstart_mse", "eps_mse", "pred_xstart")]
 
 
+class OdeState(C.Structure):
+    """codlad_ode_state: the adaptive ODE method's device state block (read back after every attempt)."""
+    _fields_ = [(n, C.c_double) for n in ("t", "h", "t_end", "ratio", "hh")] + \
+               [(n, C.c_int32) for n in ("accepted", "n_accept", "n_reject", "clipped", "nonfinite", "status")] + \
+               [("hh_f", C.c_float), ("tf", C.c_float * 6), ("pad_", C.c_float)]
+
+
+class OdeDopri5Bufs(C.Structure):
+    """codlad_ode_dopri5_bufs"""
+    _fields_ = [("y", P), ("y1", P), ("xin", P), ("k", P * 7), ("mods", P), ("state", P), ("norm", P)]
+
+
+ODE_METHODS = {"euler": 0, "midpoint": 1, "rk4": 2}    # CODLAD_ODE_* of include/codlad_hip.h
+ODE_NORM_WORDS = 257                                   # CODLAD_ODE_NORM_WORDS
+
 _SIGS = {
     "codlad_abi_version": (C.c_int, []),
     "codlad_probe_edge_launches": (C.c_int, [C.c_int]),
@@ -107,6 +122,12 @@ _SIGS = {
     "codlad_step_mods": (C.c_int, [C.POINTER(DenoiserWeights), P, C.c_int, P, P]),
     "codlad_step_mods_f": (C.c_int, [C.POINTER(DenoiserWeights), P, C.c_int, P, P]),
     "codlad_ode_combine": (C.c_int, [P, P, P, C.c_int, C.c_float, C.c_size_t, P, P]),
+    "codlad_ode_error_norm": (C.c_int, [P, P, P, C.c_size_t, C.c_float, C.c_float, P, P]),
+    "codlad_ode_loop": (C.c_int, [C.POINTER(DenoiserWeights), P, C.c_int, P, P, P, C.c_int, P, P, P, C.c_int, P, C.c_int,
+                                  P, C.POINTER(Workspace), P]),
+    "codlad_ode_dopri5_attempt": (C.c_int, [C.POINTER(DenoiserWeights), P, C.c_int, P, P, P, C.c_int,
+                                            C.POINTER(OdeDopri5Bufs), C.c_double, C.c_float, C.c_float,
+                                            C.POINTER(Workspace), P]),
     "codlad_layer0_edge_terms": (C.c_int, [C.POINTER(DenoiserWeights), P, C.c_int, P, P, P]),
     "codlad_denoiser_forward": (C.c_int, [C.POINTER(DenoiserWeights), P, C.c_int, P, P, P, C.c_int, P, P, P, P,
                                           C.POINTER(Workspace), P]),

@@ -3,6 +3,7 @@
 #include "node_args.h"
 #include "sampler_args.h"
 #include "loss_args.h"
+#include "ode_args.h"
 
 // precision: 0 = fp32 MFMA, 1 = f16x4, 2 = f16x3 (include/codlad_hip.h); terms = 4 or 3 products per split contraction, 0 = fp32
 static void launch_edge_now(bool update, const EdgeArgs &ea, int precision, hipStream_t st, const int2 *tile_list,
@@ -402,6 +403,125 @@ extern "C" int codlad_bpd_loop(const codlad_denoiser_weights *w, const int32_t *
     return codlad_check_launch("codlad_bpd_loop");
 }
 #undef LOSS_MODEL_REQUIRE
+
+// The fused ODE samplers of the flow-matching models (ode_kernels.hip): ode_stage_kernel takes final_kernel's place after
+// enqueue_forward.  x_self_cond = null throughout: zeros, as the reference's run_sampling calls the model.
+static OdeStageArgs ode_stage_args(const codlad_denoiser_weights *w, const codlad_workspace *ws, const float *mods_t,
+                                   int n_nodes) {
+    OdeStageArgs a = {};
+    a.hV = ws->hV; a.mods = mods_t + mods_offset(6); a.out_w = w->out_w; a.out_b = w->out_b;
+    a.n_nodes = n_nodes; a.status = ws->status; a.self = -1;
+    return a;
+}
+
+// A stage's sum: the slopes (by stage index) in the order torchdiffeq lists them, and their coefficients
+struct OdeRow {
+    int n_k;
+    int k[4];
+    double coef[4];
+};
+static const OdeRow ODE_EULER[1] = {{1, {0}, {1.0}}};
+static const OdeRow ODE_MIDPOINT[2] = {{1, {0}, {0.5}}, {1, {1}, {1.0}}};
+static const OdeRow ODE_RK4[4] = {{1, {0}, {1.0 / 3}},                       // the 3/8 rule (rk4_alt_step_func)
+                                  {2, {1, 0}, {1.0, -1.0 / 3}},
+                                  {3, {0, 1, 2}, {1.0, -1.0, 1.0}},
+                                  {4, {0, 1, 2, 3}, {0.125, 0.375, 0.375, 0.125}}};
+
+extern "C" int codlad_ode_loop(const codlad_denoiser_weights *w, const int32_t *node_info, int n_nodes,
+                               const int32_t *E_idx, const float *h_E0, const float *E1, int n_snodes, const float *y,
+                               float *traj, const float *mods, int method, const float *dt_host, int n_intervals,
+                               float *scratch, const codlad_workspace *ws, void *stream) {
+    CODLAD_REQUIRE(w && node_info && E_idx && h_E0 && y && traj && mods && dt_host && scratch, "null pointer");
+    CODLAD_REQUIRE(check_ws(ws), "incomplete workspace");
+    CODLAD_REQUIRE(n_nodes > 0 && n_intervals > 0, "n_nodes and n_intervals must be positive");
+    CODLAD_REQUIRE(method >= CODLAD_ODE_EULER && method <= CODLAD_ODE_RK4, "unknown method id");
+    CODLAD_REQUIRE(w->out_dim == 3, "the ODE samplers need a flow-matching model (3 outputs: the velocity)");
+    hipStream_t st = (hipStream_t)stream;
+    const OdeRow *rows = method == CODLAD_ODE_EULER ? ODE_EULER : (method == CODLAD_ODE_MIDPOINT ? ODE_MIDPOINT : ODE_RK4);
+    const int stages = method == CODLAD_ODE_EULER ? 1 : (method == CODLAD_ODE_MIDPOINT ? 2 : 4);
+    const size_t n3 = (size_t)n_nodes * 3;
+    float *xin = scratch + 4 * n3;
+    if (y != traj) {
+        hipError_t e = hipMemcpyAsync(traj, y, n3 * sizeof(float), hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess) {
+            codlad_set_error("codlad_ode_loop: %s", hipGetErrorString(e));
+            return (int)e;
+        }
+    }
+    for (int i = 0; i < n_intervals; ++i) {
+        const float *y_i = traj + (size_t)i * n3;
+        for (int s = 0; s < stages; ++s) {
+            const float *mods_t = mods + ((size_t)i * stages + s) * CODLAD_MODS_PER_STEP;
+            enqueue_forward(w, node_info, n_nodes, E_idx, h_E0, E1, (size_t)n_snodes, s == 0 ? y_i : xin, nullptr, mods_t,
+                            ws, st);
+            OdeStageArgs a = ode_stage_args(w, ws, mods_t, n_nodes);
+            a.k_out = scratch + s * n3; a.y = y_i; a.h = dt_host[i];
+            a.n_k = rows[s].n_k;
+            for (int m = 0; m < a.n_k; ++m) {
+                a.k[m] = scratch + rows[s].k[m] * n3;
+                a.coef[m] = (float)rows[s].coef[m];
+                if (rows[s].k[m] == s) a.self = m;
+            }
+            a.out = s == stages - 1 ? traj + (size_t)(i + 1) * n3 : xin;    // the last stage writes the next slot in place
+            launch_ode_stage(a, st);
+        }
+    }
+    return codlad_check_launch("codlad_ode_loop");
+}
+
+// Dormand-Prince 5(4), the constants of codlad_amd/diffusion_and_flow/ode.py (double, cast to fp32 where a sum reads them)
+static const double DP_BETA[6][6] = {{1.0 / 5},
+                                     {3.0 / 40, 9.0 / 40},
+                                     {44.0 / 45, -56.0 / 15, 32.0 / 9},
+                                     {19372.0 / 6561, -25360.0 / 2187, 64448.0 / 6561, -212.0 / 729},
+                                     {9017.0 / 3168, -355.0 / 33, 46732.0 / 5247, 49.0 / 176, -5103.0 / 18656},
+                                     {35.0 / 384, 0.0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84}};
+static const double DP_C_SOL[7] = {35.0 / 384, 0.0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84, 0.0};
+static const double DP_C_ERR[7] = {35.0 / 384 - 1951.0 / 21600, 0.0, 500.0 / 1113 - 22642.0 / 50085,
+                                   125.0 / 192 - 451.0 / 720, -2187.0 / 6784 - -12231.0 / 42400,
+                                   11.0 / 84 - 649.0 / 6300, -1.0 / 60.0};
+
+extern "C" int codlad_ode_dopri5_attempt(const codlad_denoiser_weights *w, const int32_t *node_info, int n_nodes,
+                                         const int32_t *E_idx, const float *h_E0, const float *E1, int n_snodes,
+                                         const codlad_ode_dopri5_bufs *bufs, double t_end, float rtol, float atol,
+                                         const codlad_workspace *ws, void *stream) {
+    CODLAD_REQUIRE(w && node_info && E_idx && h_E0 && bufs, "null pointer");
+    CODLAD_REQUIRE(bufs->y && bufs->y1 && bufs->xin && bufs->mods && bufs->state && bufs->norm, "null pointer (buffers)");
+    for (int j = 0; j < 7; ++j) CODLAD_REQUIRE(bufs->k[j], "null pointer (slopes)");
+    CODLAD_REQUIRE(check_ws(ws), "incomplete workspace");
+    CODLAD_REQUIRE(n_nodes > 0, "n_nodes must be positive");
+    CODLAD_REQUIRE(w->out_dim == 3, "the ODE samplers need a flow-matching model (3 outputs: the velocity)");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n3 = (size_t)n_nodes * 3;
+    const float *hh = &bufs->state->hh_f;       // device addresses inside the state block (nothing is read here)
+    launch_ode_times(bufs->state, t_end, (float)DP_BETA[0][0], bufs->y, bufs->k[0], bufs->xin, n3, st);
+    const int rc = codlad_step_mods_f(w, bufs->state->tf, 6, bufs->mods, stream);    // mods_kernel, 6 workgroups
+    if (rc) return rc;
+    for (int i = 0; i < 6; ++i) {
+        const float *mods_t = bufs->mods + (size_t)i * CODLAD_MODS_PER_STEP;
+        enqueue_forward(w, node_info, n_nodes, E_idx, h_E0, E1, (size_t)n_snodes, bufs->xin, nullptr, mods_t, ws, st);
+        OdeStageArgs a = ode_stage_args(w, ws, mods_t, n_nodes);
+        a.k_out = bufs->k[i + 1]; a.y = bufs->y; a.h_dev = hh; a.self = i + 1;
+        const double *coef = i < 5 ? DP_BETA[i + 1] : DP_C_SOL;      // after k7: the step's result, all seven terms
+        a.n_k = i + 2;
+        for (int m = 0; m < a.n_k; ++m) {
+            a.k[m] = bufs->k[m];
+            a.coef[m] = (float)coef[m];
+        }
+        a.out = i < 5 ? bufs->xin : bufs->y1;
+        launch_ode_stage(a, st);
+    }
+    OdeNormArgs na = {};
+    na.y = bufs->y; na.y1 = bufs->y1; na.h_dev = hh; na.n = n3; na.rtol = rtol; na.atol = atol; na.out = bufs->norm;
+    na.state = bufs->state; na.status = ws->status;
+    for (int m = 0; m < 7; ++m) {
+        na.k[m] = bufs->k[m];
+        na.c_err[m] = (float)DP_C_ERR[m];
+    }
+    launch_ode_norm(na, st);
+    launch_ode_commit(bufs->state, bufs->y, bufs->y1, bufs->k[0], bufs->k[6], n3, st);
+    return codlad_check_launch("codlad_ode_dopri5_attempt");
+}
 
 // Single launch of one of the two edge kernels on encoder layer 0 (reads h_E0 and the P/Q left by
 // a previous forward; idempotent) - lets bench.py time the dominant kernel with HIP events.

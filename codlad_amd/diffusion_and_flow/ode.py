@@ -9,10 +9,19 @@ UNPINNED for the solver layer (the model evaluation under it is pinned as everyw
                     [0.2, 10], Hairer's initial step).  Deviation, stated: steps are clipped to end on the output
                     times instead of overshooting them and evaluating a dense-output polynomial; results agree with
                     any other solver of the same tolerance to that tolerance.
-State updates run on the device through codlad_ode_combine (one launch per stage); only the scalar error norm of
-the adaptive method comes back to the host.
+Two paths, the same numbers:
+  fused      `func` is a ModelVelocity over the HIP model (3-output head): Denoiser.sample_ode - a fixed grid is ONE
+             codlad_ode_loop call (every stage's forward ends in ode_stage_kernel, which forms the next stage's input), an
+             adaptive step one codlad_ode_dopri5_attempt with the error norm and the step controller on the device and one
+             small readback.  Fixed grids give the step-wise path's bits; dopri5 the same step sequence (its error norm is
+             summed in another - fixed - order, so the step sizes may differ in their last bits).
+  step-wise  any other callable: one func call per stage, state updates through codlad_ode_combine (one launch per
+             stage); the scalar error norm of the adaptive method comes back to the host.
+Fixed grids may decrease (a flow model integrated from data back to noise, the counterpart of ddim_reverse_sample_loop);
+dopri5 takes increasing grids only.
 """
 import ctypes as C
+import math
 
 import torch
 
@@ -67,6 +76,69 @@ def _fixed_step(func, method, t0, dt, t1, y0):
     raise NotImplementedError(f"odeint method {method!r}: euler, midpoint, rk4 and dopri5 are built")
 
 
+def check_grid(ts, method):
+    """ts: at least two strictly monotonic times; decreasing ones for the fixed-grid methods only."""
+    if method not in ("euler", "midpoint", "rk4", "dopri5"):
+        raise NotImplementedError(f"odeint method {method!r}: euler, midpoint, rk4 and dopri5 are built")
+    inc = all(b > a for a, b in zip(ts, ts[1:]))
+    dec = all(b < a for a, b in zip(ts, ts[1:]))
+    if len(ts) < 2 or not (inc or dec):
+        raise ValueError("t must hold at least two times and be strictly monotonic")
+    if dec and method == "dopri5":
+        raise ValueError("dopri5 integrates over an increasing time grid only; a decreasing grid (data back to noise) "
+                         "runs with the fixed-grid methods euler, midpoint and rk4")
+
+
+def stage_times(method, ts):
+    """The times at which `_fixed_step` evaluates the model over the grid ts, interval by interval and stage by stage,
+    formed in double and rounded to float32 as `_tt` does: the rows of the fused loop's modulation table."""
+    out = []
+    for t0, t1 in zip(ts, ts[1:]):
+        dt = t1 - t0
+        if method == "euler":
+            out += [t0]
+        elif method == "midpoint":
+            out += [t0, t0 + 0.5 * dt]
+        elif method == "rk4":
+            out += [t0, t0 + dt / 3, t0 + dt * 2 / 3, t1]
+        else:
+            raise NotImplementedError(f"no fixed grid for method {method!r}")
+    return torch.tensor(out, dtype=torch.float64).float().tolist()
+
+
+class ModelVelocity:
+    """f(t, x) = model.forward(x, t, None, mask=mask, batch=batch): the velocity field the reference's run_sampling hands
+    to odeint (test.py:221-236), as an ordinary callable - valid for any odeint.  This module's `odeint` recognises it:
+    over the HIP model with a 3-output head the whole integration runs fused (Denoiser.sample_ode)."""
+
+    def __init__(self, model, mask=None, batch=None):
+        self.model, self.mask, self.batch = model, mask, batch
+
+    def __call__(self, t, x):
+        return self.model.forward(x, t, None, mask=self.mask, batch=self.batch)
+
+    def fused_job(self, y0):
+        """(engine, job) when this field can run fused on y0 [N, L, 3], else None (-> the step-wise path)."""
+        from ..models.latent_model import ProteinMPNN_diffusion_new
+        mod = self.model
+        if not isinstance(mod, ProteinMPNN_diffusion_new) or mod.W_out.linear.out_features != 3:
+            return None
+        if not y0.is_cuda:
+            raise RuntimeError("odeint (codlad_amd) runs on the MI355X only")
+        if self.batch is None or y0.dim() != 3 or y0.shape[-1] != 3:
+            raise ValueError("ModelVelocity over the HIP model needs batch= and a state of shape [N, L, 3]")
+        B = int(self.batch["num_CGs"].shape[0])
+        if y0.shape[0] % B:
+            raise ValueError("x batch size must be a multiple of the number of structures in batch")
+        n_rep = y0.shape[0] // B
+        job, lens = mod.job_for(self.batch, n_rep)
+        mod._check_mask(self.mask, lens, n_rep)
+        if len(set(lens)) != 1:
+            raise NotImplementedError("fused loop on a padded mixed-length batch; pass equal-length "
+                                      "structures per call (what the reference's loaders produce)")
+        return mod.engine(), job
+
+
 def _rms(x):
     return float(x.double().pow(2).mean().sqrt())
 
@@ -82,7 +154,9 @@ def _initial_step(func, t0, y0, f0, rtol, atol, order=4):
     return min(100 * h0, h1)
 
 
-def _dopri5(func, y0, ts, rtol, atol, max_steps=100000):
+def _dopri5(func, y0, ts, rtol, atol, max_steps=100000, stats=None):
+    stats = {} if stats is None else stats
+    stats.update(n_accept=0, n_reject=0)
     out = [y0]
     t, y = float(ts[0]), y0
     f = func(_tt(t, y), y)
@@ -102,6 +176,10 @@ def _dopri5(func, y0, ts, rtol, atol, max_steps=100000):
             err = combine(torch.zeros_like(y), ks, _DP_C_ERR, hh)
             tol = atol + rtol * torch.maximum(y.abs(), y1.abs())
             ratio = _rms(err / tol)
+            if not math.isfinite(ratio):                    # never <= 1: the controller would run to max_steps
+                raise RuntimeError(f"dopri5: the model output or the error norm is not finite in the step from t = "
+                                   f"{t!r} (h = {hh!r}), attempt {n_steps}")
+            stats["n_accept" if ratio <= 1.0 else "n_reject"] += 1
             if ratio <= 1.0:                                # accept; FSAL: k7 = f(t + h, y1)
                 # a clipped step lands on the output time exactly (t + (t_end - t) can be one ulp short, which would
                 # cost a further step of ~1e-16 and restart the controller from there)
@@ -118,16 +196,40 @@ def _dopri5(func, y0, ts, rtol, atol, max_steps=100000):
     return torch.stack(out)
 
 
-def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None):
-    """-> [len(t), *y0.shape]: y at the times t (same call shape as torchdiffeq.odeint; func(t, y) -> dy/dt)."""
+class _Counted:
+    def __init__(self, func):
+        self.func, self.n = func, 0
+
+    def __call__(self, t, y):
+        self.n += 1
+        return self.func(t, y)
+
+
+def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, return_stats=False):
+    """-> [len(t), *y0.shape]: y at the times t (same call shape as torchdiffeq.odeint; func(t, y) -> dy/dt).
+    t: strictly monotonic; decreasing for euler / midpoint / rk4 only.  func a ModelVelocity over the HIP flow-matching
+    model: fused (see the module's header); any other callable: step by step.
+    return_stats: -> (traj, {"n_eval", "n_accept", "n_reject"}) on both paths."""
     method = method or "dopri5"
     ts = [float(v) for v in torch.as_tensor(t).reshape(-1).tolist()]
-    assert len(ts) >= 2 and all(b > a for a, b in zip(ts, ts[1:])), "t must be increasing"
+    check_grid(ts, method)
     y0 = y0.contiguous().float()
+    fused = func.fused_job(y0) if isinstance(func, ModelVelocity) else None
+    if fused is not None:
+        eng, job = fused
+        traj, stats = eng.sample_ode(job, y0.reshape(-1, 3), ts, method=method, rtol=rtol, atol=atol)
+        traj = traj.view(len(ts), *y0.shape)
+        return (traj, stats) if return_stats else traj
+    func = _Counted(func)
     if method == "dopri5":
-        return _dopri5(func, y0, ts, rtol, atol)
-    out, y = [y0], y0
-    for t0, t1 in zip(ts, ts[1:]):
-        y = _fixed_step(func, method, t0, t1 - t0, t1, y)
-        out.append(y)
-    return torch.stack(out)
+        stats = {}
+        traj = _dopri5(func, y0, ts, rtol, atol, stats=stats)
+    else:
+        out, y = [y0], y0
+        for t0, t1 in zip(ts, ts[1:]):
+            y = _fixed_step(func, method, t0, t1 - t0, t1, y)
+            out.append(y)
+        traj = torch.stack(out)
+        stats = {"n_accept": len(ts) - 1, "n_reject": 0}
+    stats["n_eval"] = func.n
+    return (traj, stats) if return_stats else traj

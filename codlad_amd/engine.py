@@ -393,6 +393,122 @@ class Denoiser:
                 self.check_status(job)
         return outs
 
+    # -- ODE sampling of the flow-matching models ---------------------------------------------------
+    ODE_STAGES = {"euler": 1, "midpoint": 2, "rk4": 4}
+
+    def _ode_fixed(self, job, y0, method, dts, mods):
+        """One codlad_ode_loop call on the current stream -> traj [len(dts) + 1, n_nodes, 3]."""
+        st = job.structures
+        f32 = dict(dtype=torch.float32, device=self.device)
+        y0 = y0.contiguous().float()
+        traj = torch.empty(len(dts) + 1, job.n_nodes, 3, **f32)
+        scratch = torch.empty(5, job.n_nodes, 3, **f32)
+        dt = (C.c_float * len(dts))(*dts)
+        rc = self.lib.codlad_ode_loop(C.byref(self.weights.struct), _lib.ptr(job.node_info), job.n_nodes,
+                                      _lib.ptr(st.E_idx), _lib.ptr(st.h_E0), _lib.ptr(st.E1), st.n_snodes, _lib.ptr(y0),
+                                      _lib.ptr(traj), _lib.ptr(mods), _lib.ODE_METHODS[method], dt, len(dts),
+                                      _lib.ptr(scratch), C.byref(job.ws), _lib.stream_ptr(self.device))
+        _lib.check(rc, "codlad_ode_loop")
+        return traj
+
+    def sample_ode(self, job, y0, ts, method="dopri5", rtol=1e-7, atol=1e-9, check=True, streams=None, max_steps=100000,
+                   first_step=None):
+        """The ODE sampler of a flow-matching model (3 outputs), fused: y0 [n_nodes, 3] at ts[0] -> (traj [len(ts),
+        n_nodes, 3], {"n_eval", "n_accept", "n_reject"}).  ts: strictly monotonic host floats; x_self_cond of a
+        self-conditioned model is zeros, as the reference's run_sampling calls it.
+        euler / midpoint / rk4 (the 3/8 rule): one codlad_ode_loop call over the whole grid, increasing or decreasing;
+        streams as for `sample` (None = two half-jobs on two streams from SPLIT_MIN_NODES nodes up; every unit's result
+        is that of the unit alone, to the bit).
+        dopri5: the error norm runs over the WHOLE state, so all samples of the job share one step size, as a batch does
+        under torchdiffeq; it therefore always runs on one stream (`streams` is not read), and a sample's result depends
+        on what shares its job.  One codlad_ode_dopri5_attempt per attempted step, then one small copy of the state block
+        (with the job's status word in it) back to the host.  A non-finite error norm or model output stops the loop with
+        a RuntimeError that names the time.  Increasing grids only.  first_step: the initial step size (torchdiffeq's
+        option of that name) instead of Hairer's estimate, which costs a second evaluation and is always checked."""
+        from .diffusion_and_flow import ode
+        ts = [float(v) for v in ts]
+        _require_cuda(y0, "y0")
+        assert y0.shape == (job.n_nodes, 3)
+        if self.weights.out_dim != 3:
+            raise ValueError("sample_ode needs a flow-matching model (3 outputs: the velocity); a diffusion model is "
+                             "sampled with Denoiser.sample")
+        ode.check_grid(ts, method)
+        self._fresh_features(job.structures)
+        if method == "dopri5":
+            return self._sample_dopri5(job, y0, ts, rtol, atol, check, max_steps, first_step)
+        stages = self.ODE_STAGES[method]
+        mods = self.step_mods(ode.stage_times(method, ts))
+        dts = [b - a for a, b in zip(ts, ts[1:])]
+        stats = {"n_eval": stages * len(dts), "n_accept": len(dts), "n_reject": 0}
+        if streams is None:
+            streams = 2 if job.n_nodes >= self.SPLIT_MIN_NODES and len(job.sample_struct) >= 2 else 1
+        if streams <= 1:
+            traj = self._ode_fixed(job, y0, method, dts, mods)
+            if check:
+                self.check_status(job)
+            return traj, stats
+        parts = job.parts(streams)
+        outs = self._on_streams([lambda p=p, i=i: self._ode_fixed(p, y0[i], method, dts, mods) for p, i in parts], streams)
+        traj = torch.empty(len(ts), job.n_nodes, 3, dtype=torch.float32, device=self.device)
+        for (_p, i), o in zip(parts, outs):
+            traj[:, i] = o
+        if check:
+            self._check_all([p for p, _i in parts])
+        return traj, stats
+
+    def _sample_dopri5(self, job, y0, ts, rtol, atol, check, max_steps, first_step):
+        from .diffusion_and_flow import ode
+        f32 = dict(dtype=torch.float32, device=self.device)
+        n = job.n_nodes
+
+        def f(t, y, check=True):                        # the evaluations before the first attempt
+            try:
+                return self.forward(job, y, float(t), check=check)
+            except RuntimeError as e:
+                if "not finite" not in str(e):
+                    raise
+                raise RuntimeError(f"dopri5: the model output is not finite at t = {float(t)!r}") from e
+
+        y = y0.detach().clone().contiguous().float()
+        k = [f(ode._tt(ts[0], y), y, check or first_step is None)] + [torch.empty(n, 3, **f32) for _ in range(6)]
+        h = ode._initial_step(f, ts[0], y, k[0], rtol, atol) if first_step is None else float(first_step)
+        n_first = 2 if first_step is None else 1
+        y1, xin = torch.empty(n, 3, **f32), torch.empty(n, 3, **f32)
+        mods = torch.empty(6, MODS, **f32)
+        norm = torch.empty(_lib.ODE_NORM_WORDS, dtype=torch.float64, device=self.device)
+        host = _lib.OdeState()
+        host.t, host.h = ts[0], h
+        state = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(self.device)
+        bufs = _lib.OdeDopri5Bufs()
+        bufs.y, bufs.y1, bufs.xin, bufs.mods, bufs.state, bufs.norm = (
+            _lib.ptr(t_) for t_ in (y, y1, xin, mods, state, norm))
+        for j in range(7):
+            bufs.k[j] = k[j].data_ptr()
+        st = job.structures
+        traj = torch.empty(len(ts), n, 3, **f32)
+        traj[0] = y
+        nxt, attempts = 1, 0
+        while nxt < len(ts):
+            attempts += 1
+            if attempts > max_steps:
+                raise RuntimeError("dopri5: max_steps exceeded")
+            t_before = host.t
+            rc = self.lib.codlad_ode_dopri5_attempt(C.byref(self.weights.struct), _lib.ptr(job.node_info), n,
+                                                    _lib.ptr(st.E_idx), _lib.ptr(st.h_E0), _lib.ptr(st.E1), st.n_snodes,
+                                                    C.byref(bufs), C.c_double(ts[nxt]), C.c_float(rtol), C.c_float(atol),
+                                                    C.byref(job.ws), _lib.stream_ptr(self.device))
+            _lib.check(rc, "codlad_ode_dopri5_attempt")
+            host = _lib.OdeState.from_buffer_copy(state.cpu().numpy().tobytes())   # the one readback: copy + synchronise
+            if host.nonfinite or (check and host.status):
+                job.status.zero_()
+                raise RuntimeError(f"dopri5: the model output or the error norm is not finite in the step from t = "
+                                   f"{t_before!r} (h = {host.hh!r}), attempt {attempts}: "
+                                   f"{n_first + 6 * attempts} model evaluations so far")
+            if host.accepted and host.t >= ts[nxt]:
+                traj[nxt] = y
+                nxt += 1
+        return traj, {"n_eval": n_first + 6 * attempts, "n_accept": int(host.n_accept), "n_reject": int(host.n_reject)}
+
     # -- forward-only loss evaluation -------------------------------------------------------------
     @staticmethod
     def loss_table(tables, coef=None):

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define CODLAD_ABI_VERSION 17
+#define CODLAD_ABI_VERSION 18
 #define CODLAD_H 128          /* hidden width of the denoiser                          */
 #define CODLAD_KNN 64         /* k_neighbors (reference models/latent_model.py:86)      */
 #define CODLAD_MODS_PER_STEP 6016 /* 3*9*128 (enc) + 3*6*128 (dec) + 2*128 (final)      */
@@ -173,6 +173,18 @@ int codlad_step_mods_f(const codlad_denoiser_weights *w, const float *t_values, 
  * rounded separately, summed left to right.  k_host: HOST array of n_k DEVICE pointers; coef_host: HOST floats. */
 int codlad_ode_combine(const float *y, const float *const *k_host, const float *coef_host, int n_k, float h,
                        size_t n, float *out, void *stream);
+
+/* The deterministic error norm of the adaptive method: out[0] = sqrt(mean_i((err[i] / tol[i])^2)) with
+ * tol[i] = atol + rtol * max(|y[i]|, |y1[i]|); tolerance and quotient in fp32, each operation rounded separately (as
+ * torch forms them on fp32 tensors with rtol / atol cast to fp32), the squares and their sum in double.  The sum is a
+ * fixed tree: at most CODLAD_ODE_NORM_BLOCKS contiguous chunks, one workgroup each (thread j of 256 adds elements j,
+ * j + 256, .. of the chunk in order, then the threads pairwise), the partials by one workgroup in the same way.  No
+ * floating-point atomics: the result depends on n alone, not on the run.
+ * out_double: DEVICE double [CODLAD_ODE_NORM_WORDS]: [0] the result, the rest scratch for the partials. */
+#define CODLAD_ODE_NORM_BLOCKS 256
+#define CODLAD_ODE_NORM_WORDS (1 + CODLAD_ODE_NORM_BLOCKS)
+int codlad_ode_error_norm(const float *err, const float *y, const float *y1, size_t n, float rtol, float atol,
+                          double *out_double, void *stream);
 
 /* Workspace of one job, all caller-allocated. */
 typedef struct {
@@ -398,6 +410,62 @@ int codlad_bpd_loop(const codlad_denoiser_weights *w, const int32_t *node_info, 
                     float *x_t, const float *mods, const float *coef, int T, const int32_t *sample_off, int n_samples,
                     float *vb, float *mse, float *xstart_mse, float *prior_bpd, float *total_bpd,
                     const codlad_workspace *ws, void *stream);
+
+/* Next row 8f-4, fused: the ODE samplers of the flow-matching models as one call per fixed grid / per attempted adaptive
+ * step.  ode_stage_kernel takes final_kernel's place after a forward: the final layer's 3-row velocity head (the bits of
+ * final_kernel's logits mode), the slope stored, and in the same kernel the next stage's input (after the last stage:
+ * the step's result) y + sum_m k_m * (coef_m * h), summed in the order the stage lists its slopes, every operation
+ * rounded separately - codlad_ode_combine's bits.  The model must have 3 outputs; x_self_cond of a self-conditioned
+ * model is zeros (reference test.py run_sampling passes none).
+ *
+ * codlad_ode_loop: a fixed grid.  method: CODLAD_ODE_EULER / MIDPOINT / RK4 (torchdiffeq's rk4 = the 3/8 rule; its stage
+ * 3 lists [k2, k1]).  dt_host: HOST float [n_intervals], the fp32 step of every interval (negative on a decreasing
+ * grid).  mods: DEVICE [n_intervals * stages][6016], row i * stages + s for stage s of interval i (codlad_step_mods_f
+ * over the stage times; stages = 1, 2, 4).  y [n_nodes][3] is copied to traj[0]; traj [n_intervals + 1][n_nodes][3]
+ * receives the state after every interval (the last stage writes it in place).  scratch: DEVICE float
+ * [5][n_nodes][3] (four slopes and the stage input). */
+#define CODLAD_ODE_EULER 0
+#define CODLAD_ODE_MIDPOINT 1
+#define CODLAD_ODE_RK4 2
+int codlad_ode_loop(const codlad_denoiser_weights *w, const int32_t *node_info, int n_nodes, const int32_t *E_idx,
+                    const float *h_E0, const float *E1, int n_snodes, const float *y, float *traj, const float *mods,
+                    int method, const float *dt_host, int n_intervals, float *scratch, const codlad_workspace *ws,
+                    void *stream);
+
+/* State of the adaptive method (Dormand-Prince 5(4), torchdiffeq's controller) on the DEVICE; the host writes t and h
+ * once and reads the block back after every attempt. */
+typedef struct {
+    double t, h, t_end;     /* current time, the controller's step, the output time this attempt may not pass */
+    double ratio;           /* error norm of the last attempt */
+    double hh;              /* the step the last attempt took: h, or t_end - t when clipped */
+    int32_t accepted;       /* last attempt: ratio <= 1 */
+    int32_t n_accept, n_reject;
+    int32_t clipped;        /* last attempt: h >= t_end - t */
+    int32_t nonfinite;      /* sticky: an attempt's ratio was inf / NaN (a reject; h is left as it was) */
+    int32_t status;         /* copy of the workspace's status word at the end of the last attempt */
+    float hh_f;             /* (float)hh, the word the stage kernels read */
+    float tf[6];            /* the six stage times (float)(t + alpha_i * hh) */
+    float pad_;
+} codlad_ode_state;
+
+/* Device buffers of the adaptive method, caller-allocated; y and k[0] = f(t, y) are its running state. */
+typedef struct {
+    float *y, *y1, *xin;    /* [n_nodes][3]: state, candidate, stage input */
+    float *k[7];            /* [n_nodes][3] each: k[0] = f(t, y) (FSAL: an accepted step's k[6] is copied into it) */
+    float *mods;            /* [6][6016] */
+    codlad_ode_state *state;
+    double *norm;           /* [CODLAD_ODE_NORM_WORDS] */
+} codlad_ode_dopri5_bufs;
+
+/* One attempted step, a fixed sequence of launches (nothing waits on the device): the stage times and the first stage's
+ * input from the state block, the six adaLN rows (one launch of 6 workgroups), six forwards each ending in
+ * ode_stage_kernel, the error norm with the controller in its second pass (accept: ratio <= 1; factor: safety 0.9,
+ * growth in [0.2, 10], 1 at least when accepted, 10 at ratio 0; after an accepted clipped step h = max(h, hh * factor)
+ * and t = t_end exactly), and the commit (accepted: y1 -> y, k[6] -> k[0]).  t_end is stored into the state first. */
+int codlad_ode_dopri5_attempt(const codlad_denoiser_weights *w, const int32_t *node_info, int n_nodes,
+                              const int32_t *E_idx, const float *h_E0, const float *E1, int n_snodes,
+                              const codlad_ode_dopri5_bufs *bufs, double t_end, float rtol, float atol,
+                              const codlad_workspace *ws, void *stream);
 
 /* Row 8: get_norm_feature(norm_in=False) + nearest code
  * (utils/dataset_module.py:253; utils/vq_module.py:61-68 / VectorQuantize eval lookup).

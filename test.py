@@ -15,6 +15,8 @@ them) or `--synthetic` (no PED/PDB/Atlas files ship with the reference).
 Addition: `--fix_residues SPEC` keeps the VQ-VAE encoder's latents of the chosen residues (residue pinning, a
 `PinLatents` denoised_fn) and samples the rest of each structure conditioned on them.
 Addition: `--sampler ddim [--eta E]` samples the latents with DDIM (ddim_sample_loop) instead of the ancestral DDPM loop.
+Flow matching (`--model fm ...`): the ODE sampler runs fused on the device; `--compute_nfe` prints the model evaluations of
+every batch; addition: `--ode_stepwise` integrates with one model call per stage from the host instead (same numbers).
 Addition: `--experiment bpd` scores the checkpoint instead of sampling from it: the variational bound in bits per dimension
 (calc_bpd_loop over --num_sampling_steps respaced steps, one fused loop per batch) of the batch's own VQ-VAE latents; prints
 the mean total_bpd / prior_bpd per file and saves vb / mse / xstart_mse [N, T] as .npy.  One rank only.
@@ -293,11 +295,19 @@ def unit_generator(args, batch_id, device):
 def run_sampling(model, args, x, mask=None, batch=None):
     """Flow-matching sampling, reference test.py:214-250: integrate dx/dt = model(x, t) from t = 0 (noise) to 1 over
     t_span = linspace(0, 1, --steps) with --method / --atol / --rtol; torchdiffeq.odeint is replaced by
-    codlad_amd.diffusion_and_flow.ode.odeint (euler / midpoint / rk4 / dopri5)."""
-    from codlad_amd.diffusion_and_flow.ode import odeint
+    codlad_amd.diffusion_and_flow.ode.odeint (euler / midpoint / rk4 / dopri5), which runs a ModelVelocity over the HIP
+    model fused (the numbers of the step-wise path).  --compute_nfe: the model evaluations of the batch, as the
+    reference's NFECount reports them."""
+    from codlad_amd.diffusion_and_flow.ode import ModelVelocity, odeint
     t_span = torch.linspace(0, 1, args.steps).to(x.device)
-    fwd = lambda t, x_in: model.forward(x_in, t, None, mask=mask, batch=batch)  # noqa: E731
-    return odeint(fwd, x, t_span, rtol=args.rtol, atol=args.atol, method=args.method)[-1]
+    func = ModelVelocity(model, mask=mask, batch=batch)
+    if getattr(args, "ode_stepwise", False):            # any callable that is not a ModelVelocity steps through odeint
+        func = lambda t, x_in, f=func: f(t, x_in)       # noqa: E731
+    traj, stats = odeint(func, x, t_span, rtol=args.rtol, atol=args.atol, method=args.method, return_stats=True)
+    if getattr(args, "compute_nfe", False):
+        print(f"NFE: {stats['n_eval']} model evaluations ({args.method}: {stats['n_accept']} steps accepted, "
+              f"{stats['n_reject']} rejected)", flush=True)
+    return traj[-1]
 
 
 def main(args):
@@ -484,7 +494,9 @@ if __name__ == "__main__":
     p.add_argument("--experiment", type=str, default="latent", choices=["genzprot", "recon", "latent", "bpd"])
     p.add_argument("--ckpt_type", type=str, default="net")
     p.add_argument("--sample_index", type=int, default=0)
-    for ignored, kw in (("--compute_nfe", dict(action="store_true")), ("--iteration", dict(type=int, default=1000)),
+    p.add_argument("--compute_nfe", action="store_true",
+                   help="ODE sampling: print the number of model evaluations of every batch")
+    for ignored, kw in (("--iteration", dict(type=int, default=1000)),
                         ("--n_sample", dict(type=int, default=50000)), ("--dataset", dict(default="cifar10")),
                         ("--num_steps", dict(type=int, default=40)), ("--batch_size", dict(type=int, default=200)),
                         ("--feature_path", dict(type=str, default="./datasets/features_N6")),
@@ -500,6 +512,8 @@ if __name__ == "__main__":
     p.add_argument("--synthetic", action="store_true", help="synthetic PED/PDB/Atlas-shaped proteins")
     p.add_argument("--synthetic_frames", type=int, default=10)
     p.add_argument("--synthetic_weights", action="store_true", help="seeded random weights (no checkpoints ship)")
+    p.add_argument("--ode_stepwise", action="store_true",
+                   help="ODE sampling: one model call per stage from the host instead of the fused loop (same numbers)")
     p.add_argument("--save_pdb", action="store_true", help="also write the generated ensemble as a multi-model PDB and an .xtc trajectory")
     p.add_argument("--pdb_files", nargs="*", default=None,
                    help="multi-model PDB ensembles to build the test set from (the reference's load_dataset, without mdtraj)")
