@@ -14,6 +14,12 @@
 // is wave-uniform and comes through the scalar cache, the weight is formed as a 36-term dot product with SGPR operands and
 // consumed at once.  Outputs are produced one (irrep, w) at a time, summed over the group's lanes by shuffles and
 // accumulated in an LDS slot per node, so a node of any degree needs no atomics and the sum has a fixed order.
+//
+// Both layers of fc and the sums over a path's inputs accumulate in float64 and are rounded to fp32 once per edge and
+// output channel: an edge's message is a sum of 36 x 16 products that can cancel (a sender with large scalars leaves 1/30
+// of its terms in a channel), and this kernel - not the default one, see CODLAD_OPT_TP_CONV_VARIANT - is the on-device
+// check of the matrix-pipe kernel, so it must not be the less accurate of the two where they differ.  The edge's
+// geometry, harmonics, embedding and the pre-contracted path inputs stay fp32, as does the sum over a node's edges.
 #include "encoder_common.h"
 #include "host_util.h"
 
@@ -26,12 +32,13 @@ DEV float group_sum(float v) {
     return v;
 }
 
-// one per-edge weight: fc.3 row `idx` (wave-uniform) . hid + bias
-DEV float edge_weight(kfloat_p fc3_w, kfloat_p fc3_b, int idx, const float (&hid)[36]) {
+// one per-edge weight: fc.3 row `idx` (wave-uniform) . hid + bias, in float64; hid: the lane's column of the hidden
+// vector in LDS, unit m at hid[64 m] (36 doubles per lane next to the path inputs do not fit the register file)
+DEV double edge_weight(kfloat_p fc3_w, kfloat_p fc3_b, int idx, const double *hid) {
     kfloat_p row = fc3_w + idx * 36;
-    float acc = fc3_b[idx];
-#pragma unroll
-    for (int m = 0; m < 36; ++m) acc = fmaf(hid[m], row[m], acc);
+    double acc = (double)fc3_b[idx];
+#pragma unroll 4
+    for (int m = 0; m < 36; ++m) acc = fma(hid[64 * m], (double)row[m], acc);
     return acc;
 }
 
@@ -40,6 +47,7 @@ __global__ __launch_bounds__(64) void tp_conv_kernel(codlad_tp_conv_args a) {
     constexpr int NODES = 64 / GROUP;                    // receiving nodes per wave
     constexpr int D_IN = width_of(DEPTH), D_OUT = width_of(DEPTH + 1);
     __shared__ float acc_sh[NODES][48];
+    __shared__ double hid_sh[36][64];                    // fc's hidden layer, a column per lane
     const int lane = threadIdx.x, g = lane / GROUP, gl = lane % GROUP;
     const int n = blockIdx.x * NODES + g;
     const bool node_ok = n < a.n_recv;
@@ -131,13 +139,13 @@ __global__ __launch_bounds__(64) void tp_conv_kernel(codlad_tp_conv_args a) {
             in36[12 + k] = a.attr_recv_first ? hr[k] : x0[k];
             in36[24 + k] = a.attr_recv_first ? x0[k] : hr[k];
         }
-        float hid[36];
-#pragma unroll
+        double *hid = &hid_sh[0][lane];
+#pragma unroll 1
         for (int o = 0; o < 36; ++o) {
-            float acc = fc0_b[o];
+            double acc = (double)fc0_b[o];
 #pragma unroll
-            for (int k = 0; k < 36; ++k) acc = fmaf(in36[k], fc0_w[o * 36 + k], acc);
-            hid[o] = fmaxf(acc, 0.f);
+            for (int k = 0; k < 36; ++k) acc = fma((double)in36[k], (double)fc0_w[o * 36 + k], acc);
+            hid[64 * o] = fmax(acc, 0.0);
         }
         // pre-contracted inputs of the paths that start from a vector block
         Vec3 v1[NV], v2[NV];
@@ -168,47 +176,49 @@ __global__ __launch_bounds__(64) void tp_conv_kernel(codlad_tp_conv_args a) {
         constexpr float C1O = DEPTH == 0 ? 0.5f : (DEPTH == 1 ? 0.38729833462074170f : 0.35355339059327379f);   // sqrt(3/12, 3/20, 3/24)
         constexpr float C1E = DEPTH == 1 ? 0.86602540378443865f : 0.5f;                                   // sqrt(3/4), sqrt(3/12)
         constexpr float C0O = 0.5f;                                                                        // sqrt(1/4)
+        constexpr double D_INV_SQRT3 = 0.57735026918962576, D_INV_SQRT6 = 0.40824829046386302;
         float *acc = acc_sh[g];
         // ---- 12x0e
         for (int w = 0; w < NS; ++w) {
-            float r = 0.f;
+            double r = 0.0;
 #pragma unroll
-            for (int u = 0; u < NS; ++u) r = fmaf(edge_weight(fc3_w, fc3_b, O1 + u * NS + w, hid), x0[u], r);
+            for (int u = 0; u < NS; ++u) r = fma(edge_weight(fc3_w, fc3_b, O1 + u * NS + w, hid), (double)x0[u], r);
             if (DEPTH >= 1) {
 #pragma unroll
-                for (int u = 0; u < NV; ++u) r = fmaf(edge_weight(fc3_w, fc3_b, O4 + u * NS + w, hid), d4[u], r);
+                for (int u = 0; u < NV; ++u) r = fma(edge_weight(fc3_w, fc3_b, O4 + u * NS + w, hid), (double)d4[u], r);
             }
-            r = group_sum<GROUP>(live ? C0E * r : 0.f);
-            if (gl == 0) acc[w] += r;
+            const float sum = group_sum<GROUP>(live ? (float)((double)C0E * r) : 0.f);
+            if (gl == 0) acc[w] += sum;
         }
         // ---- 4x1o
         for (int w = 0; w < NV; ++w) {
-            float t = 0.f;
+            double t = 0.0;
 #pragma unroll
-            for (int u = 0; u < NS; ++u) t = fmaf(edge_weight(fc3_w, fc3_b, O2 + u * NV + w, hid), x0[u], t);
-            t *= INV_SQRT3;
-            Vec3 r = {t * y1.x, t * y1.y, t * y1.z};
+            for (int u = 0; u < NS; ++u) t = fma(edge_weight(fc3_w, fc3_b, O2 + u * NV + w, hid), (double)x0[u], t);
+            t *= D_INV_SQRT3;
+            double rx = t * (double)y1.x, ry = t * (double)y1.y, rz = t * (double)y1.z;
             if (DEPTH >= 1) {
 #pragma unroll
                 for (int u = 0; u < NV; ++u) {
-                    const float w3 = edge_weight(fc3_w, fc3_b, O3 + u * NV + w, hid) * INV_SQRT3;
-                    const float w6 = edge_weight(fc3_w, fc3_b, O6 + u * NV + w, hid);
-                    r.x = fmaf(w3, v1[u].x, fmaf(w6, q6[u].x, r.x));
-                    r.y = fmaf(w3, v1[u].y, fmaf(w6, q6[u].y, r.y));
-                    r.z = fmaf(w3, v1[u].z, fmaf(w6, q6[u].z, r.z));
+                    const double w3 = edge_weight(fc3_w, fc3_b, O3 + u * NV + w, hid) * D_INV_SQRT3;
+                    const double w6 = edge_weight(fc3_w, fc3_b, O6 + u * NV + w, hid);
+                    rx = fma(w3, (double)v1[u].x, fma(w6, (double)q6[u].x, rx));
+                    ry = fma(w3, (double)v1[u].y, fma(w6, (double)q6[u].y, ry));
+                    rz = fma(w3, (double)v1[u].z, fma(w6, (double)q6[u].z, rz));
                 }
             }
             if (DEPTH >= 2) {
 #pragma unroll
                 for (int u = 0; u < NV; ++u) {
-                    const float w8 = edge_weight(fc3_w, fc3_b, O8 + u * NV + w, hid) * INV_SQRT6;
-                    r.x = fmaf(w8, c8[u].x, r.x);
-                    r.y = fmaf(w8, c8[u].y, r.y);
-                    r.z = fmaf(w8, c8[u].z, r.z);
+                    const double w8 = edge_weight(fc3_w, fc3_b, O8 + u * NV + w, hid) * D_INV_SQRT6;
+                    rx = fma(w8, (double)c8[u].x, rx);
+                    ry = fma(w8, (double)c8[u].y, ry);
+                    rz = fma(w8, (double)c8[u].z, rz);
                 }
             }
-            const float sx = group_sum<GROUP>(live ? C1O * r.x : 0.f), sy = group_sum<GROUP>(live ? C1O * r.y : 0.f),
-                        sz = group_sum<GROUP>(live ? C1O * r.z : 0.f);
+            const float sx = group_sum<GROUP>(live ? (float)((double)C1O * rx) : 0.f),
+                        sy = group_sum<GROUP>(live ? (float)((double)C1O * ry) : 0.f),
+                        sz = group_sum<GROUP>(live ? (float)((double)C1O * rz) : 0.f);
             if (gl == 0) {
                 acc[12 + 3 * w] += sx; acc[13 + 3 * w] += sy; acc[14 + 3 * w] += sz;
             }
@@ -216,26 +226,27 @@ __global__ __launch_bounds__(64) void tp_conv_kernel(codlad_tp_conv_args a) {
         // ---- 4x1e
         if (DEPTH >= 1) {
             for (int w = 0; w < NV; ++w) {
-                Vec3 r = {0.f, 0.f, 0.f};
+                double rx = 0.0, ry = 0.0, rz = 0.0;
 #pragma unroll
                 for (int u = 0; u < NV; ++u) {
-                    const float w5 = edge_weight(fc3_w, fc3_b, O5 + u * NV + w, hid) * INV_SQRT6;
-                    r.x = fmaf(w5, c5[u].x, r.x);
-                    r.y = fmaf(w5, c5[u].y, r.y);
-                    r.z = fmaf(w5, c5[u].z, r.z);
+                    const double w5 = edge_weight(fc3_w, fc3_b, O5 + u * NV + w, hid) * D_INV_SQRT6;
+                    rx = fma(w5, (double)c5[u].x, rx);
+                    ry = fma(w5, (double)c5[u].y, ry);
+                    rz = fma(w5, (double)c5[u].z, rz);
                 }
                 if (DEPTH >= 2) {
 #pragma unroll
                     for (int u = 0; u < NV; ++u) {
-                        const float w7 = edge_weight(fc3_w, fc3_b, O7 + u * NV + w, hid) * INV_SQRT3;
-                        const float w10 = edge_weight(fc3_w, fc3_b, O10 + u * NV + w, hid);
-                        r.x = fmaf(w7, v2[u].x, fmaf(w10, q10[u].x, r.x));
-                        r.y = fmaf(w7, v2[u].y, fmaf(w10, q10[u].y, r.y));
-                        r.z = fmaf(w7, v2[u].z, fmaf(w10, q10[u].z, r.z));
+                        const double w7 = edge_weight(fc3_w, fc3_b, O7 + u * NV + w, hid) * D_INV_SQRT3;
+                        const double w10 = edge_weight(fc3_w, fc3_b, O10 + u * NV + w, hid);
+                        rx = fma(w7, (double)v2[u].x, fma(w10, (double)q10[u].x, rx));
+                        ry = fma(w7, (double)v2[u].y, fma(w10, (double)q10[u].y, ry));
+                        rz = fma(w7, (double)v2[u].z, fma(w10, (double)q10[u].z, rz));
                     }
                 }
-                const float sx = group_sum<GROUP>(live ? C1E * r.x : 0.f), sy = group_sum<GROUP>(live ? C1E * r.y : 0.f),
-                            sz = group_sum<GROUP>(live ? C1E * r.z : 0.f);
+                const float sx = group_sum<GROUP>(live ? (float)((double)C1E * rx) : 0.f),
+                            sy = group_sum<GROUP>(live ? (float)((double)C1E * ry) : 0.f),
+                            sz = group_sum<GROUP>(live ? (float)((double)C1E * rz) : 0.f);
                 if (gl == 0) {
                     acc[24 + 3 * w] += sx; acc[25 + 3 * w] += sy; acc[26 + 3 * w] += sz;
                 }
@@ -244,11 +255,11 @@ __global__ __launch_bounds__(64) void tp_conv_kernel(codlad_tp_conv_args a) {
         // ---- 12x0o
         if (DEPTH >= 2) {
             for (int w = 0; w < NS; ++w) {
-                float r = 0.f;
+                double r = 0.0;
 #pragma unroll
-                for (int u = 0; u < NV; ++u) r = fmaf(edge_weight(fc3_w, fc3_b, O9 + u * NS + w, hid), d9[u], r);
-                r = group_sum<GROUP>(live ? C0O * r : 0.f);
-                if (gl == 0) acc[36 + w] += r;
+                for (int u = 0; u < NV; ++u) r = fma(edge_weight(fc3_w, fc3_b, O9 + u * NS + w, hid), (double)d9[u], r);
+                const float sum = group_sum<GROUP>(live ? (float)((double)C0O * r) : 0.f);
+                if (gl == 0) acc[36 + w] += sum;
             }
         }
     }

@@ -200,7 +200,7 @@ def tp_conv_layer(sd, prefix, tp, node_attr, edge_index, edge_attr, edge_sh, out
 
 def gaussian_smearing(dist, start, stop, n):
     """reference gcn_nn.GaussianSmearing (:163-173)."""
-    offset = torch.linspace(start, stop, n)
+    offset = torch.linspace(start, stop, n, dtype=dist.dtype)
     coeff = -0.5 / (offset[1] - offset[0]).item() ** 2
     return torch.exp(coeff * (dist.view(-1, 1) - offset.view(1, -1)) ** 2)
 
@@ -220,10 +220,10 @@ def layer_tps(num_conv_layers=3, ns=12, nv=4, sh_lmax=2):
 
 
 def _graph(z, xyz, nbr_list, max_radius, n_embed, sh_lmax, in_edge_features=4):
-    """build_*_conv_graph (reference vae_model.py:164-194 / 268-283)."""
+    """build_*_conv_graph (reference vae_model.py:164-194 / 268-283), in the dtype of the coordinates."""
     nb = make_directed(nbr_list)
-    edge_attr = torch.cat([z[nb[:, 0]].unsqueeze(-1).float(), z[nb[:, 1]].unsqueeze(-1).float(),
-                           torch.zeros(nb.shape[0], in_edge_features)], -1)
+    edge_attr = torch.cat([z[nb[:, 0]].unsqueeze(-1).to(xyz.dtype), z[nb[:, 1]].unsqueeze(-1).to(xyz.dtype),
+                           torch.zeros(nb.shape[0], in_edge_features, dtype=xyz.dtype)], -1)
     r = xyz[nb[:, 1]] - xyz[nb[:, 0]]
     edge_attr = torch.cat([edge_attr, gaussian_smearing(r.norm(dim=-1), 0.0, max_radius, n_embed)], -1)
     return (nb[:, 0], nb[:, 1]), edge_attr, spherical_harmonics(sh_lmax, r)
@@ -233,8 +233,36 @@ def _embed_edges(sd, prefix, x):
     return linear(sd, prefix + ".3", torch.relu(linear(sd, prefix + ".0", x)))
 
 
+def conv_reference(sd, layer, depth, csr, xyz_recv, xyz_snd, typ_recv, typ_snd, r_sign, smear_stop, emb, emb_in, h_recv,
+                   h_snd, recv_first, dtype, ns=12, nv=4, sh_lmax=2):
+    """What ONE TensorProductConvLayer call of the encoder / prior computes, from the parts above, in `dtype`: the
+    arguments are those of codlad_amd.encoder's `conv` (receivers' CSR `(ptr, snd)`, r = r_sign (x_snd - x_recv), edge
+    attributes [embedding | scalars of the receiver | of the sender] or, recv_first False, [embedding | sender |
+    receiver]; emb_in 14: the embedding's input is [type recv, type snd, 0 0 0 0, smearing], 8: the smearing alone).
+    -> the update [n_recv, 12 (depth + 2)], the mean over a receiver's edges, 0 for a receiver without one.  Which
+    node is `edge_src` / `edge_dst` and whose scalars come first in the two cross directions: reference
+    models/gcn_nn.py:181-219 and models/vae_model.py:164-201, as prior_forward / encoder_forward below apply them."""
+    ptr, snd = (t.detach().cpu().long() for t in csr)
+    n_recv = ptr.numel() - 1
+    recv = torch.repeat_interleave(torch.arange(n_recv), ptr[1:] - ptr[:-1])
+    snd = snd[:int(ptr[-1])]
+    assert recv.numel() == snd.numel()
+    up = lambda t: t.detach().cpu().to(dtype)  # noqa: E731
+    sd = {k: up(v) for k, v in sd.items() if k.startswith(layer + ".fc.") or k.startswith(emb + ".")}
+    xyz_recv, xyz_snd, h_recv, h_snd = up(xyz_recv), up(xyz_snd), up(h_recv), up(h_snd)
+    r = r_sign * (xyz_snd[snd] - xyz_recv[recv])
+    x = gaussian_smearing(r.norm(dim=-1), 0.0, smear_stop, 8)
+    if emb_in == 14:
+        x = torch.cat([up(typ_recv)[recv, None], up(typ_snd)[snd, None], x.new_zeros(snd.numel(), 4), x], -1)
+    a, b = h_recv[recv, :ns], h_snd[snd, :ns]
+    attr = torch.cat([_embed_edges(sd, emb, x)] + ([a, b] if recv_first else [b, a]), -1)
+    tp = layer_tps(3, ns, nv, sh_lmax)[depth]
+    return tp_conv_layer(sd, layer, tp, h_snd, (recv, snd), attr, spherical_harmonics(sh_lmax, r), out_nodes=n_recv)
+
+
 def prior_forward(sd, cg_z, cg_xyz, cg_nbr_list, prefix="", ns=12, nv=4, cg_max_radius=26.0, sh_lmax=2):
-    """e3nnPrior.forward (reference vae_model.py:245-266) -> (H_mu, H_sigma) [n_cg, 36]."""
+    """e3nnPrior.forward (reference vae_model.py:245-266) -> (H_mu, H_sigma) [n_cg, 36], in the dtype of `sd` and
+    `cg_xyz` (float64 weights and coordinates: float64 throughout)."""
     tps = layer_tps(3, ns, nv, sh_lmax)
     (src, dst), edge_attr, sh = _graph(cg_z, cg_xyz, cg_nbr_list, cg_max_radius, 8, sh_lmax)
     h = sd[prefix + "cg_node_embedding.weight"][cg_z.long()]

@@ -179,6 +179,99 @@ def test_module_mirrors_keep_the_checkpoint_layout():
     load_decoder_state(n6_dec, n6.state_dict())              # a decoder-only model skips the encoder side of a full one
 
 
+def _old_gaussian_smearing(dist, start, stop, n):
+    """oracle/e3nn_lite.py's gaussian_smearing before it followed its input's dtype."""
+    offset = torch.linspace(start, stop, n)
+    coeff = -0.5 / (offset[1] - offset[0]).item() ** 2
+    return torch.exp(coeff * (dist.view(-1, 1) - offset.view(1, -1)) ** 2)
+
+
+def _old_graph(z, xyz, nbr_list, max_radius, n_embed, sh_lmax, in_edge_features=4):
+    """oracle/e3nn_lite.py's _graph before it followed its input's dtype."""
+    nb = e3.make_directed(nbr_list)
+    edge_attr = torch.cat([z[nb[:, 0]].unsqueeze(-1).float(), z[nb[:, 1]].unsqueeze(-1).float(),
+                           torch.zeros(nb.shape[0], in_edge_features)], -1)
+    r = xyz[nb[:, 1]] - xyz[nb[:, 0]]
+    edge_attr = torch.cat([edge_attr, _old_gaussian_smearing(r.norm(dim=-1), 0.0, max_radius, n_embed)], -1)
+    return (nb[:, 0], nb[:, 1]), edge_attr, e3.spherical_harmonics(sh_lmax, r)
+
+
+def _g15_encoder_inputs(name):
+    L, frames, wseed = cases.E3NN_ENCODER_CASES[name]
+    prot = synth.make_protein(L, 50 + L, n_frames=frames)
+    batch, atoms = synth.make_batch(prot), synth.make_atoms(prot, seed=L)
+    return synth.encoder_state_dict(wseed), (atoms["nxyz"][:, 0], atoms["nxyz"][:, 1:], batch["CG_nxyz"][:, 0].long(),
+                                             batch["CG_nxyz"][:, 1:], atoms["CG_mapping"], atoms["nbr_list"], batch["CG_nbr_list"])
+
+
+def _g15_prior_inputs(name):
+    L, frames, wseed, weights = cases.E3NN_PRIOR_CASES[name]
+    batch = synth.make_batch(synth.make_protein(L, 40 + L, n_frames=frames))
+    sd = _prior_sd() if weights == "trained_c2" else synth.prior_state_dict(wseed)
+    return sd, (batch["CG_nxyz"][:, 0].long(), batch["CG_nxyz"][:, 1:], batch["CG_nbr_list"])
+
+
+def _up(args):
+    return tuple(a.double() if a.is_floating_point() else a for a in args)
+
+
+def test_oracle_follows_the_input_dtype_and_float32_is_bit_unchanged():
+    """prior_forward / encoder_forward in float32 return the bits they returned when _graph and gaussian_smearing were
+    hard-coded to float32 (the old expressions are kept above), and with float64 weights and inputs every tensor a conv
+    layer sees is float64."""
+    psd, pargs = _g15_prior_inputs("seeded_L46x2")
+    esd, eargs = _g15_encoder_inputs("L12")
+    mu, sg = e3.prior_forward(psd, *pargs)
+    lat = e3.encoder_forward(esd, *eargs)
+    graph, smear = e3._graph, e3.gaussian_smearing
+    e3._graph, e3.gaussian_smearing = _old_graph, _old_gaussian_smearing
+    try:
+        mu_old, sg_old = e3.prior_forward(psd, *pargs)
+        lat_old = e3.encoder_forward(esd, *eargs)
+    finally:
+        e3._graph, e3.gaussian_smearing = graph, smear
+    assert mu.dtype == lat.dtype == torch.float32
+    assert torch.equal(mu, mu_old) and torch.equal(sg, sg_old) and torch.equal(lat, lat_old)
+    # float64 throughout
+    seen, orig = [], e3.tp_conv_layer
+
+    def spy(sd, prefix, tp, node_attr, edge_index, edge_attr, edge_sh, out_nodes=None):
+        out = orig(sd, prefix, tp, node_attr, edge_index, edge_attr, edge_sh, out_nodes)
+        seen.append({node_attr.dtype, edge_attr.dtype, edge_sh.dtype, out.dtype})
+        return out
+
+    e3.tp_conv_layer = spy
+    try:
+        mu64, sg64 = e3.prior_forward({k: v.double() for k, v in psd.items()}, *_up(pargs))
+        lat64 = e3.encoder_forward({k: v.double() for k, v in esd.items()}, *_up(eargs))
+    finally:
+        e3.tp_conv_layer = orig
+    assert len(seen) == 13 and all(s == {torch.float64} for s in seen)
+    assert mu64.dtype == sg64.dtype == lat64.dtype == torch.float64
+    assert rel_err(mu, mu64) < 2e-6 and rel_err(sg, sg64) < 2e-6 and rel_err(lat, lat64) < 2e-6
+
+
+def test_conv_reference_returns_what_the_references_layers_returned():
+    """e3.conv_reference - one `Encoder.conv` call restated from the oracle's parts, the reference the per-launch GPU
+    tests compare with - fed the node states the float32 oracle's layers start from, returns the ten per-layer updates the
+    reference's own TensorProductConvLayer.forward produced (g15_encoder_L12), in float32 and in float64."""
+    from tests import e3nn_parity as ep
+    gold = np.load(cases.npz_path("g15_encoder_L12"))
+    sd, args = _g15_encoder_inputs("L12")
+    G = ep.encoder_graphs(*args)
+    states, upd = ep.oracle_layer_states(sd, args)
+    done = []
+    for l, (ha, hc) in enumerate(states):
+        for call in ep.encoder_layer_calls(G, l, ha, hc):
+            key = "upd_" + call["layer"].replace(".", "_")
+            r32, r64 = ep.reference_of(sd, call, torch.float32), ep.reference_of(sd, call, torch.float64)
+            assert r32.dtype == torch.float32 and r64.dtype == torch.float64 and tuple(r32.shape) == gold[key].shape
+            assert rel_err(r32, torch.from_numpy(gold[key])) < 2e-6 and rel_err(r64, torch.from_numpy(gold[key])) < 2e-6, key
+            assert rel_err(r32, upd[key]) < 2e-6, key
+            done.append(key)
+    assert sorted(done) == sorted(k for k in gold.files if k.startswith("upd_")) and len(done) == 10
+
+
 # ------------------------------------------------------------------------------------------------ GPU: HIP vs the oracle
 DEV = "cuda:0"
 
@@ -229,6 +322,54 @@ def test_hip_encoder_matches_oracle(L, frames):
         alone = Encoder(sd, DEV).forward(one["nxyz"][:, 0], one["nxyz"][:, 1:], b1["CG_nxyz"][:, 0].long(),
                                          b1["CG_nxyz"][:, 1:], one["CG_mapping"], one["nbr_list"], b1["CG_nbr_list"])
         assert torch.equal(alone, got[L:])
+
+
+# The reference's own forward passes (g15, tools/gen_golden.py: e3nnEncoder.forward / e3nnPrior.forward /
+# TensorProductConvLayer.forward over the restated primitives) against the device directly, not through the oracle.
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(cases.E3NN_ENCODER_CASES))
+def test_hip_encoder_matches_the_references_g15_latent(name):
+    from codlad_amd.encoder import Encoder
+    sd, args = _g15_encoder_inputs(name)
+    gold = torch.from_numpy(np.load(cases.npz_path(f"g15_encoder_{name}"))["latent"])
+    got = Encoder(sd, DEV).forward(*args)
+    assert tuple(got.shape) == tuple(gold.shape)
+    assert rel_err(got, gold) < 1e-5, rel_err(got, gold)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(cases.E3NN_PRIOR_CASES))
+def test_hip_prior_matches_the_references_g15_mu_and_sigma(name):
+    from codlad_amd.encoder import Prior
+    sd, args = _g15_prior_inputs(name)
+    gold = np.load(cases.npz_path(f"g15_prior_{name}"))
+    mu, sg = Prior(sd, DEV).forward(*args)
+    assert tuple(mu.shape) == gold["mu"].shape and tuple(sg.shape) == gold["sigma"].shape
+    e_mu, e_sg = rel_err(mu, torch.from_numpy(gold["mu"])), rel_err(sg, torch.from_numpy(gold["sigma"]))
+    assert e_mu < 1e-5 and e_sg < 1e-5, (e_mu, e_sg)
+
+
+@pytest.mark.gpu
+def test_hip_conv_layers_match_the_references_g15_updates():
+    """The ten per-layer updates the reference's TensorProductConvLayer.forward returned on the small encoder case, each
+    against ONE `Encoder.conv` launch (accumulate into zeros) fed the float32 oracle's node states of that layer."""
+    from codlad_amd.encoder import Encoder
+    from tests import e3nn_parity as ep
+    gold = np.load(cases.npz_path("g15_encoder_L12"))
+    sd, args = _g15_encoder_inputs("L12")
+    G = ep.encoder_graphs(*args)
+    states, _upd = ep.oracle_layer_states(sd, args)
+    enc = Encoder(sd, DEV)
+    done = []
+    for l, (ha, hc) in enumerate(states):
+        for call in ep.encoder_layer_calls(G, l, ha, hc):
+            key = "upd_" + call["layer"].replace(".", "_")
+            got = ep.device_conv(enc, call)
+            err = rel_err(got, torch.from_numpy(gold[key]))
+            print(f"g15 {key}: {err:.2e} of the array's maximum")
+            assert tuple(got.shape) == gold[key].shape and err < 1e-5, (key, err)
+            done.append(key)
+    assert sorted(done) == sorted(k for k in gold.files if k.startswith("upd_")) and len(done) == 10
 
 
 @pytest.mark.gpu
