@@ -10,7 +10,7 @@ import os
 import torch  # noqa: F401  (must precede the dlopen below)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 18   # CODLAD_ABI_VERSION of include/codlad_hip.h this binding was written against
+ABI_VERSION = 19   # CODLAD_ABI_VERSION of include/codlad_hip.h this binding was written against
 # CODLAD_HIP_LIB: an alternative build of the same ABI (A/B measurements, tools/ablate_edge.py)
 LIB_PATH = os.environ.get("CODLAD_HIP_LIB") or os.path.join(_HERE, "libcodlad_hip.so")
 
@@ -53,6 +53,12 @@ class DenoiserWeights(C.Structure):
 
 class Workspace(C.Structure):
     _fields_ = [(n, P) for n in ("hV", "hVenc", "S", "PQ", "hE", "status", "tile_list")] + [("n_tiles", C.c_int32), ("xcd_bounds", P)]
+
+
+class JobDesc(C.Structure):
+    """codlad_job: a job's node table, its structures' graph and edge terms, its workspace."""
+    _fields_ = [("node_info", P), ("n_nodes", C.c_int), ("E_idx", P), ("h_E0", P), ("E1", P), ("n_snodes", C.c_int),
+                ("ws", C.POINTER(Workspace))]
 
 
 class DecoderWeights(C.Structure):
@@ -108,6 +114,8 @@ class OdeDopri5Bufs(C.Structure):
 ODE_METHODS = {"euler": 0, "midpoint": 1, "rk4": 2}    # CODLAD_ODE_* of include/codlad_hip.h
 ODE_NORM_WORDS = 257                                   # CODLAD_ODE_NORM_WORDS
 
+_JOB = [C.POINTER(DenoiserWeights), C.POINTER(JobDesc)]    # what every entry point that runs the denoiser starts with
+
 _SIGS = {
     "codlad_abi_version": (C.c_int, []),
     "codlad_probe_edge_launches": (C.c_int, [C.c_int]),
@@ -123,35 +131,26 @@ _SIGS = {
     "codlad_step_mods_f": (C.c_int, [C.POINTER(DenoiserWeights), P, C.c_int, P, P]),
     "codlad_ode_combine": (C.c_int, [P, P, P, C.c_int, C.c_float, C.c_size_t, P, P]),
     "codlad_ode_error_norm": (C.c_int, [P, P, P, C.c_size_t, C.c_float, C.c_float, P, P]),
-    "codlad_ode_loop": (C.c_int, [C.POINTER(DenoiserWeights), P, C.c_int, P, P, P, C.c_int, P, P, P, C.c_int, P, C.c_int,
-                                  P, C.POINTER(Workspace), P]),
-    "codlad_ode_dopri5_attempt": (C.c_int, [C.POINTER(DenoiserWeights), P, C.c_int, P, P, P, C.c_int,
-                                            C.POINTER(OdeDopri5Bufs), C.c_double, C.c_float, C.c_float,
-                                            C.POINTER(Workspace), P]),
+    "codlad_ode_loop": (C.c_int, _JOB + [P, P, P, C.c_int, P, C.c_int, P, P]),
+    "codlad_ode_dopri5_attempt": (C.c_int, _JOB + [C.POINTER(OdeDopri5Bufs), C.c_double, C.c_float, C.c_float, P]),
     "codlad_layer0_edge_terms": (C.c_int, [C.POINTER(DenoiserWeights), P, C.c_int, P, P, P]),
-    "codlad_denoiser_forward": (C.c_int, [C.POINTER(DenoiserWeights), P, C.c_int, P, P, P, C.c_int, P, P, P, P,
-                                          C.POINTER(Workspace), P]),
+    "codlad_denoiser_forward": (C.c_int, _JOB + [P, P, P, P, P]),
     "codlad_status_check": (C.c_int, [P, P]),
     "codlad_set_option": (C.c_int, [C.c_int, C.c_int]),
     "codlad_edge_plan_host": (C.c_int, [P, C.c_int, C.c_int, C.c_int, C.c_int, P, P]),
     "codlad_ddpm_update": (C.c_int, [P, P, P, P, C.c_int, P, P, P]),
     "codlad_ddpm_pred_xstart": (C.c_int, [P, P, P, C.c_int, P, P]),
     "codlad_ddpm_posterior_step": (C.c_int, [P, P, P, P, P, P, C.c_float, C.c_int, P, P, P]),
-    "codlad_sample_loop": (C.c_int, [C.POINTER(DenoiserWeights), P, C.c_int, P, P, P, C.c_int, P, P, P, P, P,
-                                     C.c_int, C.POINTER(Workspace), P]),
-    "codlad_sample_loop_pinned": (C.c_int, [C.POINTER(DenoiserWeights), P, C.c_int, P, P, P, C.c_int, P, P, P, P, P,
-                                            C.c_int, P, P, C.POINTER(Workspace), P]),
-    "codlad_ddim_loop": (C.c_int, [C.POINTER(DenoiserWeights), P, C.c_int, P, P, P, C.c_int, P, P, P, P, P, C.c_int,
-                                   C.c_int, C.c_int, P, P, C.POINTER(Workspace), P]),
+    "codlad_sample_loop": (C.c_int, _JOB + [P, P, P, P, P, C.c_int, P]),
+    "codlad_sample_loop_pinned": (C.c_int, _JOB + [P, P, P, P, P, C.c_int, P, P, P]),
+    "codlad_ddim_loop": (C.c_int, _JOB + [P, P, P, P, P, C.c_int, C.c_int, C.c_int, P, P, P]),
     "codlad_ddim_step": (C.c_int, [P, P, P, P, P, C.c_int, C.c_int, P, P, P]),
     "codlad_q_sample": (C.c_int, [P, P, P, C.c_int, P, C.c_int, P, C.c_int, P, P, P, P]),
     "codlad_q_posterior": (C.c_int, [P, P, P, C.c_int, P, C.c_int, P, C.c_int, P, P, P, P]),
     "codlad_vb_terms": (C.c_int, [P, P, P, P, P, C.c_int, P, C.c_int, P, C.c_int, C.POINTER(LossTerms), P]),
     "codlad_prior_bpd": (C.c_int, [P, P, C.c_int, P, C.c_int, P, P]),
-    "codlad_loss_forward": (C.c_int, [C.POINTER(DenoiserWeights), P, C.c_int, P, P, P, C.c_int, P, P, P, P, P, P, C.c_int,
-                                      C.c_int, P, C.c_int, P, C.POINTER(LossTerms), C.POINTER(Workspace), P]),
-    "codlad_bpd_loop": (C.c_int, [C.POINTER(DenoiserWeights), P, C.c_int, P, P, P, C.c_int, P, P, P, P, P, C.c_int, P,
-                                  C.c_int, P, P, P, P, P, C.POINTER(Workspace), P]),
+    "codlad_loss_forward": (C.c_int, _JOB + [P, P, P, P, P, P, C.c_int, C.c_int, P, C.c_int, P, C.POINTER(LossTerms), P]),
+    "codlad_bpd_loop": (C.c_int, _JOB + [P, P, P, P, P, C.c_int, P, C.c_int, P, P, P, P, P, P]),
     "codlad_vq_lookup": (C.c_int, [P, C.c_int, P, P, P, C.c_int, P, P, P, P]),
     "codlad_ic_decode": (C.c_int, [C.POINTER(DecoderWeights), P, P, P, P, P, C.c_int, P, P, P]),
     "codlad_cg_graph": (C.c_int, [P, P, C.c_int, C.c_float, P, P, P, P]),

@@ -34,12 +34,14 @@ extern "C" int codlad_abi_version(void) { return CODLAD_ABI_VERSION; }
 
 extern "C" const char *codlad_last_error(void) { return g_err; }
 
-extern "C" void codlad_struct_sizes(int *out5) {
-    out5[0] = (int)sizeof(codlad_denoiser_weights);
-    out5[1] = (int)sizeof(codlad_decoder_weights);
-    out5[2] = (int)sizeof(codlad_workspace);
-    out5[3] = (int)offsetof(codlad_denoiser_weights, precision);
-    out5[4] = (int)offsetof(codlad_denoiser_weights, enc_h);
+extern "C" void codlad_struct_sizes(int *out7) {
+    out7[0] = (int)sizeof(codlad_denoiser_weights);
+    out7[1] = (int)sizeof(codlad_decoder_weights);
+    out7[2] = (int)sizeof(codlad_workspace);
+    out7[3] = (int)offsetof(codlad_denoiser_weights, precision);
+    out7[4] = (int)offsetof(codlad_denoiser_weights, enc_h);
+    out7[5] = (int)sizeof(codlad_job);
+    out7[6] = (int)offsetof(codlad_job, ws);
 }
 
 extern "C" void codlad_pack_block_host(const float *src, int ld, float scale, float *dst) {

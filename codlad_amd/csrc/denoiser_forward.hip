@@ -87,7 +87,7 @@ static void launch_node(bool upd, const NodeArgs &na, int precision, hipStream_t
     else launch_node_stream(terms, tiles > 4 * num_cu() ? 8 : 4, upd, na, st);
 }
 
-// What every launch of one forward shares.
+// What every launch of one forward shares: the caller's descriptor and what the host derives from it.
 struct Job {
     const codlad_denoiser_weights *w;
     const int4 *ni;
@@ -97,6 +97,9 @@ struct Job {
     bool split;      // split-fp16 mode: biases are the pre-scaled copies, block exponents become scale constants (include/codlad_hip.h)
     float *PQ(int k) const { return ws->PQ + (size_t)k * n_nodes * HD; }
 };
+static Job make_job(const codlad_denoiser_weights *w, const codlad_job *d) {
+    return {w, reinterpret_cast<const int4 *>(d->node_info), d->E_idx, d->n_nodes, d->ws, w->precision != 0};
+}
 
 static EdgeArgs edge_args(const Job &j, const float *hE_in, bool in_by_src) {
     EdgeArgs ea = {};
@@ -170,11 +173,12 @@ static void add_proj_dec_q(NodeArgs &na, const Job &j, const codlad_dec_layer &D
 }
 
 // One denoiser forward up to (not including) the final layer: leaves h_V in ws->hV.
-static void enqueue_forward(const codlad_denoiser_weights *w, const int32_t *node_info,
-                            int n_nodes, const int32_t *E_idx, const float *h_E0, const float *E1,
-                            size_t n_snodes, const float *x, const float *x_self_cond, const float *mods_t,
-                            const codlad_workspace *ws, hipStream_t st) {
-    const Job j = {w, reinterpret_cast<const int4 *>(node_info), E_idx, n_nodes, ws, w->precision != 0};
+static void enqueue_forward(const codlad_denoiser_weights *w, const codlad_job *job, const float *x,
+                            const float *x_self_cond, const float *mods_t, hipStream_t st) {
+    const Job j = make_job(w, job);
+    const codlad_workspace *ws = job->ws;
+    const int n_nodes = job->n_nodes;
+    const float *h_E0 = job->h_E0, *E1 = job->E1;
     // small jobs: edge kernels per 32-edge tile, message sums per half (S[2][n_nodes][128])
     // (while every wave of the persistent grid gets at most one tile: beyond that the per-node order is as good)
     const bool tilewise = j.split && ws->tile_list && ws->n_tiles > 0 &&
@@ -217,7 +221,7 @@ static void enqueue_forward(const codlad_denoiser_weights *w, const int32_t *nod
         launch_node(true, na, w->precision, st);
 
         EdgeArgs eu = upd_args(j, L, Lh, hE_in, l == 0, m);
-        if (l == 0 && E1) eu.E1 = E1 + n_snodes * 64 * HD;
+        if (l == 0 && E1) eu.E1 = E1 + (size_t)job->n_snodes * 64 * HD;
         launch_edge(true, eu, w->precision, st, tile_list, ws->n_tiles);
     }
     for (int l = 0; l < 3; ++l) {
@@ -239,26 +243,32 @@ static int check_ws(const codlad_workspace *ws) {
     return ws && ws->hV && ws->hVenc && ws->S && ws->PQ && ws->hE;
 }
 
-static FinalArgs final_args(const codlad_denoiser_weights *w, const codlad_workspace *ws, const float *mods_t, int n_nodes) {
+// What is wrong with (w, job) for an entry point that runs the denoiser, or null.  REQUIRE_OK reports a helper's finding
+// under the name of the function it stands in.
+static const char *job_defect(const codlad_denoiser_weights *w, const codlad_job *job) {
+    if (!w || !job || !job->node_info || !job->E_idx || !job->h_E0) return "null pointer";
+    if (job->n_nodes <= 0) return "n_nodes must be positive";
+    if (!check_ws(job->ws)) return "incomplete workspace";
+    return nullptr;
+}
+#define REQUIRE_OK(defect) do { const char *msg_ = (defect); CODLAD_REQUIRE(!msg_, msg_); } while (0)
+
+static FinalArgs final_args(const codlad_denoiser_weights *w, const codlad_job *job, const float *mods_t) {
     FinalArgs fa = {};
-    fa.hV = ws->hV; fa.mods = mods_t + mods_offset(6); fa.out_w = w->out_w; fa.out_b = w->out_b;
-    fa.n_nodes = n_nodes; fa.status = ws->status; fa.n_out = w->out_dim;
+    fa.hV = job->ws->hV; fa.mods = mods_t + mods_offset(6); fa.out_w = w->out_w; fa.out_b = w->out_b;
+    fa.n_nodes = job->n_nodes; fa.status = job->ws->status; fa.n_out = w->out_dim;
     return fa;
 }
 
-extern "C" int codlad_denoiser_forward(const codlad_denoiser_weights *w, const int32_t *node_info,
-                                       int n_nodes, const int32_t *E_idx, const float *h_E0,
-                                       const float *E1, int n_snodes, const float *x,
-                                       const float *x_self_cond, const float *mods_t, float *out,
-                                       const codlad_workspace *ws, void *stream) {
-    CODLAD_REQUIRE(w && node_info && E_idx && h_E0 && x && mods_t && out, "null pointer");
-    CODLAD_REQUIRE(check_ws(ws), "incomplete workspace");
-    CODLAD_REQUIRE(n_nodes > 0, "n_nodes must be positive");
+extern "C" int codlad_denoiser_forward(const codlad_denoiser_weights *w, const codlad_job *job, const float *x,
+                                       const float *x_self_cond, const float *mods_t, float *out, void *stream) {
+    REQUIRE_OK(job_defect(w, job));
+    CODLAD_REQUIRE(x && mods_t && out, "null pointer");
     hipStream_t st = (hipStream_t)stream;
     CODLAD_REQUIRE(!x_self_cond || w->self_condition, "x_self_cond given to a model without self-conditioning");
     CODLAD_REQUIRE(w->out_dim == 6 || w->out_dim == 3, "out_dim must be 6 (diffusion) or 3 (flow matching)");
-    enqueue_forward(w, node_info, n_nodes, E_idx, h_E0, E1, (size_t)n_snodes, x, x_self_cond, mods_t, ws, st);
-    FinalArgs fa = final_args(w, ws, mods_t, n_nodes);
+    enqueue_forward(w, job, x, x_self_cond, mods_t, st);
+    FinalArgs fa = final_args(w, job, mods_t);
     fa.logits = out;
     launch_final(fa, CODLAD_STEP_DDPM, nullptr, nullptr, 0, st);
     return codlad_check_launch("codlad_denoiser_forward");
@@ -267,10 +277,9 @@ extern "C" int codlad_denoiser_forward(const codlad_denoiser_weights *w, const i
 // the loop of codlad_sample_loop / codlad_sample_loop_pinned / codlad_ddim_loop (pin_x0 == NULL: no pinning).
 // step: CODLAD_STEP_* of final_kernel; `mode` is read by the DDIM steps only.  The forward loops run i = T-1 .. 0 and
 // consume noise entry k at step k; the reverse DDIM loop runs i = 0 .. T-1 and reads no noise.
-static void sample_loop(const codlad_denoiser_weights *w, const int32_t *node_info, int n_nodes, const int32_t *E_idx,
-                        const float *h_E0, const float *E1, int n_snodes, float *x, float *x_start, const float *noise,
-                        const float *mods, const float *coef, int T, const float *pin_x0, const uint8_t *pin_mask,
-                        const codlad_workspace *ws, void *stream, int step = CODLAD_STEP_DDPM, int mode = 0) {
+static void sample_loop(const codlad_denoiser_weights *w, const codlad_job *job, float *x, float *x_start,
+                        const float *noise, const float *mods, const float *coef, int T, const float *pin_x0,
+                        const uint8_t *pin_mask, void *stream, int step = CODLAD_STEP_DDPM, int mode = 0) {
     hipStream_t st = (hipStream_t)stream;
     // self-conditioning (gaussian_diffusion.py:530-547): step k reads the pred_xstart step k-1 wrote;
     // the first step gets none, which the model treats as zeros (latent_model.py:211)
@@ -279,121 +288,111 @@ static void sample_loop(const codlad_denoiser_weights *w, const int32_t *node_in
     for (int k = 0; k < T; ++k) {
         const int i = reverse ? k : T - 1 - k;
         const float *mods_t = mods + (size_t)i * CODLAD_MODS_PER_STEP;
-        enqueue_forward(w, node_info, n_nodes, E_idx, h_E0, E1, (size_t)n_snodes, x, sc && k > 0 ? x_start : nullptr,
-                        mods_t, ws, st);
-        FinalArgs fa = final_args(w, ws, mods_t, n_nodes);
-        fa.x = x; fa.noise = reverse ? nullptr : noise + (size_t)k * n_nodes * 3;
+        enqueue_forward(w, job, x, sc && k > 0 ? x_start : nullptr, mods_t, st);
+        FinalArgs fa = final_args(w, job, mods_t);
+        fa.x = x; fa.noise = reverse ? nullptr : noise + (size_t)k * job->n_nodes * 3;
         fa.coef = coef + (size_t)i * 8; fa.x_start = x_start;
         launch_final(fa, step, pin_x0, pin_mask, mode, st);
     }
 }
 
-#define SAMPLE_LOOP_REQUIRE()                                                                                          \
-    CODLAD_REQUIRE(w && node_info && E_idx && h_E0 && x && noise && mods && coef, "null pointer");                     \
-    CODLAD_REQUIRE(check_ws(ws), "incomplete workspace");                                                             \
-    CODLAD_REQUIRE(n_nodes > 0 && T > 0, "n_nodes and T must be positive");                                           \
-    CODLAD_REQUIRE(!w->self_condition || x_start, "a self-conditioned model needs the x_start buffer");               \
-    CODLAD_REQUIRE(w->out_dim == 6 || w->out_dim == 3,                                                                \
-                   "the DDPM loop needs a model with 6 outputs (mean | variance logits) or 3 (fixed-variance samplers)")
+static const char *ddpm_loop_defect(const codlad_denoiser_weights *w, const codlad_job *job, const float *x,
+                                    const float *x_start, const float *noise, const float *mods, const float *coef, int T) {
+    if (const char *msg = job_defect(w, job)) return msg;
+    if (!x || !noise || !mods || !coef) return "null pointer";
+    if (T <= 0) return "T must be positive";
+    if (w->self_condition && !x_start) return "a self-conditioned model needs the x_start buffer";
+    if (w->out_dim != 6 && w->out_dim != 3)
+        return "the DDPM loop needs a model with 6 outputs (mean | variance logits) or 3 (fixed-variance samplers)";
+    return nullptr;
+}
 
-extern "C" int codlad_sample_loop(const codlad_denoiser_weights *w, const int32_t *node_info,
-                                  int n_nodes, const int32_t *E_idx, const float *h_E0,
-                                  const float *E1, int n_snodes, float *x, float *x_start,
-                                  const float *noise, const float *mods, const float *coef, int T,
-                                  const codlad_workspace *ws, void *stream) {
-    SAMPLE_LOOP_REQUIRE();
-    sample_loop(w, node_info, n_nodes, E_idx, h_E0, E1, n_snodes, x, x_start, noise, mods, coef, T, nullptr, nullptr, ws,
-                stream);
+extern "C" int codlad_sample_loop(const codlad_denoiser_weights *w, const codlad_job *job, float *x, float *x_start,
+                                  const float *noise, const float *mods, const float *coef, int T, void *stream) {
+    REQUIRE_OK(ddpm_loop_defect(w, job, x, x_start, noise, mods, coef, T));
+    sample_loop(w, job, x, x_start, noise, mods, coef, T, nullptr, nullptr, stream);
     return codlad_check_launch("codlad_sample_loop");
 }
 
-extern "C" int codlad_sample_loop_pinned(const codlad_denoiser_weights *w, const int32_t *node_info,
-                                         int n_nodes, const int32_t *E_idx, const float *h_E0,
-                                         const float *E1, int n_snodes, float *x, float *x_start,
-                                         const float *noise, const float *mods, const float *coef, int T,
-                                         const float *pin_x0, const uint8_t *pin_mask,
-                                         const codlad_workspace *ws, void *stream) {
-    SAMPLE_LOOP_REQUIRE();
+extern "C" int codlad_sample_loop_pinned(const codlad_denoiser_weights *w, const codlad_job *job, float *x,
+                                         float *x_start, const float *noise, const float *mods, const float *coef, int T,
+                                         const float *pin_x0, const uint8_t *pin_mask, void *stream) {
+    REQUIRE_OK(ddpm_loop_defect(w, job, x, x_start, noise, mods, coef, T));
     CODLAD_REQUIRE(pin_x0 && pin_mask, "null pointer (pin_x0 / pin_mask)");
-    sample_loop(w, node_info, n_nodes, E_idx, h_E0, E1, n_snodes, x, x_start, noise, mods, coef, T, pin_x0, pin_mask, ws,
-                stream);
+    sample_loop(w, job, x, x_start, noise, mods, coef, T, pin_x0, pin_mask, stream);
     return codlad_check_launch("codlad_sample_loop_pinned");
 }
-#undef SAMPLE_LOOP_REQUIRE
 
-extern "C" int codlad_ddim_loop(const codlad_denoiser_weights *w, const int32_t *node_info, int n_nodes,
-                                const int32_t *E_idx, const float *h_E0, const float *E1, int n_snodes, float *x,
-                                float *x_start, const float *noise, const float *mods, const float *coef, int T, int mode,
-                                int reverse, const float *pin_x0, const uint8_t *pin_mask, const codlad_workspace *ws,
-                                void *stream) {
-    CODLAD_REQUIRE(w && node_info && E_idx && h_E0 && x && mods && coef, "null pointer");
+extern "C" int codlad_ddim_loop(const codlad_denoiser_weights *w, const codlad_job *job, float *x, float *x_start,
+                                const float *noise, const float *mods, const float *coef, int T, int mode, int reverse,
+                                const float *pin_x0, const uint8_t *pin_mask, void *stream) {
+    CODLAD_REQUIRE(w && x && mods && coef, "null pointer");
     CODLAD_REQUIRE(reverse || noise, "null pointer (noise: only the reverse loop runs without it)");
     CODLAD_REQUIRE(!pin_x0 == !pin_mask, "null pointer (pin_x0 and pin_mask come together)");
-    CODLAD_REQUIRE(n_nodes > 0 && T > 0, "n_nodes and T must be positive");
+    CODLAD_REQUIRE(T > 0, "T must be positive");
     CODLAD_REQUIRE(mode >= 0 && mode <= (CODLAD_DDPM_START_X | CODLAD_DDPM_FIXED_VAR | CODLAD_DDPM_CLIP),
                    "unknown mode bits");
     CODLAD_REQUIRE(w->out_dim == ((mode & CODLAD_DDPM_FIXED_VAR) ? 3 : 6),
                    "mode and model disagree: a learned-range sampler needs a model with 6 outputs (mean | variance "
                    "logits), a fixed-variance one (mode bit 2) a model with 3");
     CODLAD_REQUIRE(!w->self_condition || x_start, "a self-conditioned model needs the x_start buffer");
-    CODLAD_REQUIRE(check_ws(ws), "incomplete workspace");
-    sample_loop(w, node_info, n_nodes, E_idx, h_E0, E1, n_snodes, x, x_start, noise, mods, coef, T, pin_x0, pin_mask, ws,
-                stream, reverse ? CODLAD_STEP_DDIM_REVERSE : CODLAD_STEP_DDIM, mode);
+    REQUIRE_OK(job_defect(w, job));     // after the sampler's own: a wrong mode is reported before the job it would run on
+    sample_loop(w, job, x, x_start, noise, mods, coef, T, pin_x0, pin_mask, stream,
+                reverse ? CODLAD_STEP_DDIM_REVERSE : CODLAD_STEP_DDIM, mode);
     return codlad_check_launch("codlad_ddim_loop");
 }
 
 // Loss evaluation around a forward (loss_kernels.hip): loss_kernel takes final_kernel's place after enqueue_forward.
-static LossArgs loss_args(const codlad_denoiser_weights *w, const codlad_workspace *ws, const float *mods_t, int n_nodes,
+static LossArgs loss_args(const codlad_denoiser_weights *w, const codlad_job *job, const float *mods_t,
                           const float *x_start, const float *x_t, const float *noise, const LossSamples &s) {
     LossArgs la = {};
-    la.head = final_args(w, ws, mods_t, n_nodes);
+    la.head = final_args(w, job, mods_t);
     la.x0 = x_start; la.xt = x_t; la.noise = noise; la.s = s;
     return la;
 }
 
-#define LOSS_MODEL_REQUIRE()                                                                                            \
-    CODLAD_REQUIRE(check_ws(ws), "incomplete workspace");                                                              \
-    CODLAD_REQUIRE(n_nodes > 0 && T > 0 && n_samples > 0, "n_nodes, T and n_samples must be positive");                \
-    CODLAD_REQUIRE(w->out_dim == 6 || w->out_dim == 3,                                                                 \
-                   "the loss needs a model with 6 outputs (mean | variance logits) or 3 (fixed-variance samplers)")
+static const char *loss_model_defect(const codlad_denoiser_weights *w, const codlad_job *job, int T, int n_samples) {
+    if (const char *msg = job_defect(w, job)) return msg;
+    if (T <= 0 || n_samples <= 0) return "T and n_samples must be positive";
+    if (w->out_dim != 6 && w->out_dim != 3)
+        return "the loss needs a model with 6 outputs (mean | variance logits) or 3 (fixed-variance samplers)";
+    return nullptr;
+}
 
-extern "C" int codlad_loss_forward(const codlad_denoiser_weights *w, const int32_t *node_info, int n_nodes,
-                                   const int32_t *E_idx, const float *h_E0, const float *E1, int n_snodes,
-                                   const float *x_start, const float *x_t, const float *noise, const float *x_self_cond,
-                                   const float *mods_t, const float *coef, int T, int t, const int32_t *sample_off,
-                                   int n_samples, float *model_out, const codlad_loss_terms *terms,
-                                   const codlad_workspace *ws, void *stream) {
-    CODLAD_REQUIRE(w && node_info && E_idx && h_E0 && x_start && x_t && mods_t && coef && sample_off && terms, "null pointer");
-    LOSS_MODEL_REQUIRE();
+extern "C" int codlad_loss_forward(const codlad_denoiser_weights *w, const codlad_job *job, const float *x_start,
+                                   const float *x_t, const float *noise, const float *x_self_cond, const float *mods_t,
+                                   const float *coef, int T, int t, const int32_t *sample_off, int n_samples,
+                                   float *model_out, const codlad_loss_terms *terms, void *stream) {
+    REQUIRE_OK(loss_model_defect(w, job, T, n_samples));
+    CODLAD_REQUIRE(x_start && x_t && mods_t && coef && sample_off && terms, "null pointer");
     CODLAD_REQUIRE(t >= 0 && t < T, "t outside [0, T)");
     CODLAD_REQUIRE(!x_self_cond || w->self_condition, "x_self_cond given to a model without self-conditioning");
     hipStream_t st = (hipStream_t)stream;
-    enqueue_forward(w, node_info, n_nodes, E_idx, h_E0, E1, (size_t)n_snodes, x_t, x_self_cond, mods_t, ws, st);
-    LossArgs la = loss_args(w, ws, mods_t, n_nodes, x_start, x_t, noise, {sample_off, nullptr, t, T, n_samples, coef});
+    enqueue_forward(w, job, x_t, x_self_cond, mods_t, st);
+    LossArgs la = loss_args(w, job, mods_t, x_start, x_t, noise, {sample_off, nullptr, t, T, n_samples, coef});
     la.head.logits = model_out;
     la.out = *terms;
     launch_loss(la, st);
     return codlad_check_launch("codlad_loss_forward");
 }
 
-extern "C" int codlad_bpd_loop(const codlad_denoiser_weights *w, const int32_t *node_info, int n_nodes,
-                               const int32_t *E_idx, const float *h_E0, const float *E1, int n_snodes, const float *x_start,
+extern "C" int codlad_bpd_loop(const codlad_denoiser_weights *w, const codlad_job *job, const float *x_start,
                                const float *noise, float *x_t, const float *mods, const float *coef, int T,
                                const int32_t *sample_off, int n_samples, float *vb, float *mse, float *xstart_mse,
-                               float *prior_bpd, float *total_bpd, const codlad_workspace *ws, void *stream) {
-    CODLAD_REQUIRE(w && node_info && E_idx && h_E0 && x_start && noise && x_t && mods && coef && sample_off, "null pointer");
+                               float *prior_bpd, float *total_bpd, void *stream) {
+    REQUIRE_OK(loss_model_defect(w, job, T, n_samples));
+    CODLAD_REQUIRE(x_start && noise && x_t && mods && coef && sample_off, "null pointer");
     CODLAD_REQUIRE(vb && mse && xstart_mse && prior_bpd && total_bpd, "null pointer (results)");
-    LOSS_MODEL_REQUIRE();
     hipStream_t st = (hipStream_t)stream;
     for (int k = 0; k < T; ++k) {
         const int i = T - 1 - k;
         const LossSamples s = {sample_off, nullptr, i, T, n_samples, coef};
-        const float *eps = noise + (size_t)k * n_nodes * 3;
+        const float *eps = noise + (size_t)k * job->n_nodes * 3;
         const float *mods_t = mods + (size_t)i * CODLAD_MODS_PER_STEP;
         launch_q_affine(x_start, eps, 8, 9, 10, 11, s, x_t, nullptr, nullptr, st);
         // x_self_cond = null: zeros, the x_self_cond=None of calc_bpd_loop's model calls (latent_model.py:211)
-        enqueue_forward(w, node_info, n_nodes, E_idx, h_E0, E1, (size_t)n_snodes, x_t, nullptr, mods_t, ws, st);
-        LossArgs la = loss_args(w, ws, mods_t, n_nodes, x_start, x_t, eps, s);
+        enqueue_forward(w, job, x_t, nullptr, mods_t, st);
+        LossArgs la = loss_args(w, job, mods_t, x_start, x_t, eps, s);
         la.out.vb = vb + (size_t)i * n_samples;
         la.out.eps_mse = mse + (size_t)i * n_samples;
         la.out.xstart_mse = xstart_mse + (size_t)i * n_samples;
@@ -402,15 +401,13 @@ extern "C" int codlad_bpd_loop(const codlad_denoiser_weights *w, const int32_t *
     launch_prior(x_start, {sample_off, nullptr, T - 1, T, n_samples, coef}, vb, prior_bpd, total_bpd, st);
     return codlad_check_launch("codlad_bpd_loop");
 }
-#undef LOSS_MODEL_REQUIRE
 
 // The fused ODE samplers of the flow-matching models (ode_kernels.hip): ode_stage_kernel takes final_kernel's place after
 // enqueue_forward.  x_self_cond = null throughout: zeros, as the reference's run_sampling calls the model.
-static OdeStageArgs ode_stage_args(const codlad_denoiser_weights *w, const codlad_workspace *ws, const float *mods_t,
-                                   int n_nodes) {
+static OdeStageArgs ode_stage_args(const codlad_denoiser_weights *w, const codlad_job *job, const float *mods_t) {
     OdeStageArgs a = {};
-    a.hV = ws->hV; a.mods = mods_t + mods_offset(6); a.out_w = w->out_w; a.out_b = w->out_b;
-    a.n_nodes = n_nodes; a.status = ws->status; a.self = -1;
+    a.hV = job->ws->hV; a.mods = mods_t + mods_offset(6); a.out_w = w->out_w; a.out_b = w->out_b;
+    a.n_nodes = job->n_nodes; a.status = job->ws->status; a.self = -1;
     return a;
 }
 
@@ -427,19 +424,18 @@ static const OdeRow ODE_RK4[4] = {{1, {0}, {1.0 / 3}},                       // 
                                   {3, {0, 1, 2}, {1.0, -1.0, 1.0}},
                                   {4, {0, 1, 2, 3}, {0.125, 0.375, 0.375, 0.125}}};
 
-extern "C" int codlad_ode_loop(const codlad_denoiser_weights *w, const int32_t *node_info, int n_nodes,
-                               const int32_t *E_idx, const float *h_E0, const float *E1, int n_snodes, const float *y,
-                               float *traj, const float *mods, int method, const float *dt_host, int n_intervals,
-                               float *scratch, const codlad_workspace *ws, void *stream) {
-    CODLAD_REQUIRE(w && node_info && E_idx && h_E0 && y && traj && mods && dt_host && scratch, "null pointer");
-    CODLAD_REQUIRE(check_ws(ws), "incomplete workspace");
-    CODLAD_REQUIRE(n_nodes > 0 && n_intervals > 0, "n_nodes and n_intervals must be positive");
+extern "C" int codlad_ode_loop(const codlad_denoiser_weights *w, const codlad_job *job, const float *y, float *traj,
+                               const float *mods, int method, const float *dt_host, int n_intervals, float *scratch,
+                               void *stream) {
+    REQUIRE_OK(job_defect(w, job));
+    CODLAD_REQUIRE(y && traj && mods && dt_host && scratch, "null pointer");
+    CODLAD_REQUIRE(n_intervals > 0, "n_intervals must be positive");
     CODLAD_REQUIRE(method >= CODLAD_ODE_EULER && method <= CODLAD_ODE_RK4, "unknown method id");
     CODLAD_REQUIRE(w->out_dim == 3, "the ODE samplers need a flow-matching model (3 outputs: the velocity)");
     hipStream_t st = (hipStream_t)stream;
     const OdeRow *rows = method == CODLAD_ODE_EULER ? ODE_EULER : (method == CODLAD_ODE_MIDPOINT ? ODE_MIDPOINT : ODE_RK4);
     const int stages = method == CODLAD_ODE_EULER ? 1 : (method == CODLAD_ODE_MIDPOINT ? 2 : 4);
-    const size_t n3 = (size_t)n_nodes * 3;
+    const size_t n3 = (size_t)job->n_nodes * 3;
     float *xin = scratch + 4 * n3;
     if (y != traj) {
         hipError_t e = hipMemcpyAsync(traj, y, n3 * sizeof(float), hipMemcpyDeviceToDevice, st);
@@ -452,9 +448,8 @@ extern "C" int codlad_ode_loop(const codlad_denoiser_weights *w, const int32_t *
         const float *y_i = traj + (size_t)i * n3;
         for (int s = 0; s < stages; ++s) {
             const float *mods_t = mods + ((size_t)i * stages + s) * CODLAD_MODS_PER_STEP;
-            enqueue_forward(w, node_info, n_nodes, E_idx, h_E0, E1, (size_t)n_snodes, s == 0 ? y_i : xin, nullptr, mods_t,
-                            ws, st);
-            OdeStageArgs a = ode_stage_args(w, ws, mods_t, n_nodes);
+            enqueue_forward(w, job, s == 0 ? y_i : xin, nullptr, mods_t, st);
+            OdeStageArgs a = ode_stage_args(w, job, mods_t);
             a.k_out = scratch + s * n3; a.y = y_i; a.h = dt_host[i];
             a.n_k = rows[s].n_k;
             for (int m = 0; m < a.n_k; ++m) {
@@ -481,26 +476,24 @@ static const double DP_C_ERR[7] = {35.0 / 384 - 1951.0 / 21600, 0.0, 500.0 / 111
                                    125.0 / 192 - 451.0 / 720, -2187.0 / 6784 - -12231.0 / 42400,
                                    11.0 / 84 - 649.0 / 6300, -1.0 / 60.0};
 
-extern "C" int codlad_ode_dopri5_attempt(const codlad_denoiser_weights *w, const int32_t *node_info, int n_nodes,
-                                         const int32_t *E_idx, const float *h_E0, const float *E1, int n_snodes,
+extern "C" int codlad_ode_dopri5_attempt(const codlad_denoiser_weights *w, const codlad_job *job,
                                          const codlad_ode_dopri5_bufs *bufs, double t_end, float rtol, float atol,
-                                         const codlad_workspace *ws, void *stream) {
-    CODLAD_REQUIRE(w && node_info && E_idx && h_E0 && bufs, "null pointer");
+                                         void *stream) {
+    REQUIRE_OK(job_defect(w, job));
+    CODLAD_REQUIRE(bufs, "null pointer");
     CODLAD_REQUIRE(bufs->y && bufs->y1 && bufs->xin && bufs->mods && bufs->state && bufs->norm, "null pointer (buffers)");
     for (int j = 0; j < 7; ++j) CODLAD_REQUIRE(bufs->k[j], "null pointer (slopes)");
-    CODLAD_REQUIRE(check_ws(ws), "incomplete workspace");
-    CODLAD_REQUIRE(n_nodes > 0, "n_nodes must be positive");
     CODLAD_REQUIRE(w->out_dim == 3, "the ODE samplers need a flow-matching model (3 outputs: the velocity)");
     hipStream_t st = (hipStream_t)stream;
-    const size_t n3 = (size_t)n_nodes * 3;
+    const size_t n3 = (size_t)job->n_nodes * 3;
     const float *hh = &bufs->state->hh_f;       // device addresses inside the state block (nothing is read here)
     launch_ode_times(bufs->state, t_end, (float)DP_BETA[0][0], bufs->y, bufs->k[0], bufs->xin, n3, st);
     const int rc = codlad_step_mods_f(w, bufs->state->tf, 6, bufs->mods, stream);    // mods_kernel, 6 workgroups
     if (rc) return rc;
     for (int i = 0; i < 6; ++i) {
         const float *mods_t = bufs->mods + (size_t)i * CODLAD_MODS_PER_STEP;
-        enqueue_forward(w, node_info, n_nodes, E_idx, h_E0, E1, (size_t)n_snodes, bufs->xin, nullptr, mods_t, ws, st);
-        OdeStageArgs a = ode_stage_args(w, ws, mods_t, n_nodes);
+        enqueue_forward(w, job, bufs->xin, nullptr, mods_t, st);
+        OdeStageArgs a = ode_stage_args(w, job, mods_t);
         a.k_out = bufs->k[i + 1]; a.y = bufs->y; a.h_dev = hh; a.self = i + 1;
         const double *coef = i < 5 ? DP_BETA[i + 1] : DP_C_SOL;      // after k7: the step's result, all seven terms
         a.n_k = i + 2;
@@ -513,7 +506,7 @@ extern "C" int codlad_ode_dopri5_attempt(const codlad_denoiser_weights *w, const
     }
     OdeNormArgs na = {};
     na.y = bufs->y; na.y1 = bufs->y1; na.h_dev = hh; na.n = n3; na.rtol = rtol; na.atol = atol; na.out = bufs->norm;
-    na.state = bufs->state; na.status = ws->status;
+    na.state = bufs->state; na.status = job->ws->status;
     for (int m = 0; m < 7; ++m) {
         na.k[m] = bufs->k[m];
         na.c_err[m] = (float)DP_C_ERR[m];
@@ -529,10 +522,11 @@ extern "C" int codlad_bench_edge_launch(const codlad_denoiser_weights *w, const 
                                         int n_nodes, const int32_t *E_idx, const float *h_E0,
                                         const float *mods_t, const codlad_workspace *ws, int which,
                                         int layer, void *stream) {
-    CODLAD_REQUIRE(w && node_info && E_idx && h_E0 && mods_t, "null pointer");
-    CODLAD_REQUIRE(check_ws(ws), "incomplete workspace");
-    CODLAD_REQUIRE(n_nodes > 0 && (which == 0 || which == 1) && (layer == 0 || layer == 1), "bad arguments");
-    const Job j = {w, reinterpret_cast<const int4 *>(node_info), E_idx, n_nodes, ws, w->precision != 0};
+    const codlad_job desc = {node_info, n_nodes, E_idx, h_E0, nullptr, 0, ws}, *job = &desc;
+    REQUIRE_OK(job_defect(w, job));
+    CODLAD_REQUIRE(mods_t, "null pointer");
+    CODLAD_REQUIRE((which == 0 || which == 1) && (layer == 0 || layer == 1), "bad arguments");
+    const Job j = make_job(w, job);
     const codlad_enc_layer &L = w->enc[layer];
     const codlad_enc_layer_h &Lh = w->enc_h[layer];
     // layer 0 reads the shared structure-edge state, layer 1 the per-sample edge state (in place)

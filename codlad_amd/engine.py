@@ -120,20 +120,36 @@ class Job:
     def workspace_bytes(self):
         return 4 * (self.hV.numel() * 2 + self.S.numel() + self.PQ.numel() + self.hE.numel())
 
+    def desc(self):
+        """The codlad_job of this job on its structures as they are now (new_structures allocates E_idx / h_E0 / E1 after
+        Structures.__init__): build it per engine call.  Every pointer in it belongs to a tensor that this job or its
+        structures hold, and it holds the workspace; the caller holds it until the foreign call has returned."""
+        st = self.structures
+        d = _lib.JobDesc()
+        d.node_info, d.n_nodes = _lib.ptr(self.node_info), self.n_nodes
+        d.E_idx, d.h_E0, d.E1, d.n_snodes = _lib.ptr(st.E_idx), _lib.ptr(st.h_E0), _lib.ptr(st.E1), st.n_snodes
+        d.ws = C.pointer(self.ws)
+        return d
+
+    def sub_job(self, members, start):
+        """The ragged sub-job of the samples `members` -> (job, node indices of its samples in this job).  It keeps its edge
+        state in this job's buffer, from node `start` (32 KB per node: nothing else of a workspace is large; the small
+        tables are its own), so a job and its sub-jobs are never in flight together, and sub-jobs that are occupy
+        disjoint ranges."""
+        n = int(sum(self.sample_lens[m] for m in members))
+        sub = Job(self.structures, [self.sample_struct[m] for m in members], self.device,
+                  edge_state=self.hE[start:start + n])
+        idx = np.concatenate([np.arange(self.sample_off[m], self.sample_off[m + 1]) for m in members])
+        return sub, torch.from_numpy(idx).to(self.device)
+
     def parts(self, k=2):
         """This job's samples dealt alternately into k independent jobs (the same mix of lengths in each) -> [(job, node
-        indices of its samples in this job)].  The parts keep their edge state in slices of this job's buffer (32 KB per
-        node: nothing else of a workspace is large), so a job and its parts are never in flight together."""
+        indices of its samples in this job)], sub-jobs side by side in this job's edge state."""
         if k not in self._parts:
             subs, start = [], 0
             for p in range(k):
-                members = list(range(p, len(self.sample_struct), k))
-                n = int(sum(self.sample_lens[m] for m in members))
-                sub = Job(self.structures, [self.sample_struct[m] for m in members], self.device,
-                          edge_state=self.hE[start:start + n])
-                idx = np.concatenate([np.arange(self.sample_off[m], self.sample_off[m + 1]) for m in members])
-                subs.append((sub, torch.from_numpy(idx).to(self.device)))
-                start += n
+                subs.append(self.sub_job(range(p, len(self.sample_struct), k), start))
+                start += subs[-1][0].n_nodes
             self._parts[k] = subs
         return self._parts[k]
 
@@ -239,6 +255,17 @@ class Denoiser:
     def self_condition(self):
         return self.weights.self_condition
 
+    def _run(self, name, desc, *args):
+        """lib.<name>(the weights, a Job.desc(), *args, the current stream), its return code checked under that name."""
+        rc = getattr(self.lib, name)(C.byref(self.weights.struct), C.byref(desc), *args, _lib.stream_ptr(self.device))
+        _lib.check(rc, name)
+
+    def _n_streams(self, job, streams):
+        """`streams` of sample / sample_ode / bpd: None = 2 from SPLIT_MIN_NODES nodes and two samples up, else 1."""
+        if streams is not None:
+            return streams
+        return 2 if job.n_nodes >= self.SPLIT_MIN_NODES and len(job.sample_struct) >= 2 else 1
+
     def check_status(self, job):
         """Wait for the job's stream and raise if a forward produced inf / NaN (in the split-fp16 modes:
         also if an operand left the fp16 range, include/codlad_hip.h CODLAD_STATUS_NONFINITE)."""
@@ -260,14 +287,8 @@ class Denoiser:
             assert x_self_cond.shape == x.shape
         mods = self.step_mods([t_value])
         out = torch.empty(job.n_nodes, self.weights.out_dim, dtype=torch.float32, device=self.device)
-        st = job.structures
-        self._fresh_features(st)
-        rc = self.lib.codlad_denoiser_forward(C.byref(self.weights.struct), _lib.ptr(job.node_info),
-                                              job.n_nodes, _lib.ptr(st.E_idx), _lib.ptr(st.h_E0),
-                                              _lib.ptr(st.E1), st.n_snodes, _lib.ptr(x), _lib.ptr(x_self_cond),
-                                              _lib.ptr(mods), _lib.ptr(out), C.byref(job.ws),
-                                              _lib.stream_ptr(self.device))
-        _lib.check(rc, "codlad_denoiser_forward")
+        self._fresh_features(job.structures)
+        self._run("codlad_denoiser_forward", job.desc(), _lib.ptr(x), _lib.ptr(x_self_cond), _lib.ptr(mods), _lib.ptr(out))
         if check:
             self.check_status(job)
         return out
@@ -307,8 +328,7 @@ class Denoiser:
         assert x_T.shape == (job.n_nodes, 3)
         if pin is not None:
             pin = self._pin_arrays(pin, job.n_nodes)
-        if streams is None:
-            streams = 2 if job.n_nodes >= self.SPLIT_MIN_NODES and len(job.sample_struct) >= 2 else 1
+        streams = self._n_streams(job, streams)
         if streams > 1:
             parts = job.parts(streams)
             pins = None if pin is None else [(pin[0][i], pin[1][i]) for _p, i in parts]
@@ -331,33 +351,16 @@ class Denoiser:
         mods = self.step_mods(tables.timestep_map)
         mode = int(coef[0, 7])                                  # the host's mode word (codlad_ddim_loop checks it)
         coef = torch.from_numpy(coef).to(self.device)
-        st = job.structures
-        self._fresh_features(st)
+        self._fresh_features(job.structures)
         x_start = torch.empty_like(x) if self.self_condition else None   # pred_xstart, step to step
+        loop = [_lib.ptr(t) for t in (x, x_start, noise, mods, coef)] + [T]
+        pin_ptrs = [_lib.ptr(t) for t in (pin or (None, None))]
         if kind != "ddpm":
-            rc = self.lib.codlad_ddim_loop(C.byref(self.weights.struct), _lib.ptr(job.node_info), job.n_nodes,
-                                           _lib.ptr(st.E_idx), _lib.ptr(st.h_E0), _lib.ptr(st.E1), st.n_snodes,
-                                           _lib.ptr(x), _lib.ptr(x_start), _lib.ptr(noise), _lib.ptr(mods),
-                                           _lib.ptr(coef), T, mode, int(reverse),
-                                           _lib.ptr(None if pin is None else pin[0]),
-                                           _lib.ptr(None if pin is None else pin[1]), C.byref(job.ws),
-                                           _lib.stream_ptr(self.device))
-            _lib.check(rc, "codlad_ddim_loop")
+            self._run("codlad_ddim_loop", job.desc(), *loop, mode, int(reverse), *pin_ptrs)
         elif pin is None:
-            rc = self.lib.codlad_sample_loop(C.byref(self.weights.struct), _lib.ptr(job.node_info),
-                                             job.n_nodes, _lib.ptr(st.E_idx), _lib.ptr(st.h_E0),
-                                             _lib.ptr(st.E1), st.n_snodes, _lib.ptr(x), _lib.ptr(x_start),
-                                             _lib.ptr(noise), _lib.ptr(mods), _lib.ptr(coef), T, C.byref(job.ws),
-                                             _lib.stream_ptr(self.device))
-            _lib.check(rc, "codlad_sample_loop")
+            self._run("codlad_sample_loop", job.desc(), *loop)
         else:
-            rc = self.lib.codlad_sample_loop_pinned(C.byref(self.weights.struct), _lib.ptr(job.node_info),
-                                                    job.n_nodes, _lib.ptr(st.E_idx), _lib.ptr(st.h_E0),
-                                                    _lib.ptr(st.E1), st.n_snodes, _lib.ptr(x), _lib.ptr(x_start),
-                                                    _lib.ptr(noise), _lib.ptr(mods), _lib.ptr(coef), T,
-                                                    _lib.ptr(pin[0]), _lib.ptr(pin[1]), C.byref(job.ws),
-                                                    _lib.stream_ptr(self.device))
-            _lib.check(rc, "codlad_sample_loop_pinned")
+            self._run("codlad_sample_loop_pinned", job.desc(), *loop, *pin_ptrs)
         if check:
             self.check_status(job)
         return x
@@ -371,23 +374,17 @@ class Denoiser:
         "ddim_reverse")."""
         pins = [None] * len(jobs) if pins is None else list(pins)
         assert len(pins) == len(jobs)
-        if not hasattr(self, "_streams"):
-            self._streams = []
-        while len(self._streams) < len(jobs):
-            self._streams.append(torch.cuda.Stream(device=self.device))
-        cur = torch.cuda.current_stream(self.device)
         for job in jobs:                                  # features and the step tables once, on the caller's stream
             self._fresh_features(job.structures)
         self.step_mods(tables.timestep_map)
-        outs = []
-        for job, x_T, noise, pin, st in zip(jobs, x_Ts, noises, pins, self._streams):
-            if pin is not None:
-                pin = self._pin_arrays(pin, job.n_nodes)         # (copies on the caller's stream)
-            st.wait_stream(cur)
-            with torch.cuda.stream(st):
-                outs.append(self.sample(job, x_T, noise, tables, check=False, coef=coef, streams=1, pin=pin, kind=kind))
-        for st in self._streams[:len(jobs)]:
-            cur.wait_stream(st)
+        # the pin arrays too: copies on the caller's stream, which the side streams wait for - and held until those have been
+        # joined: the block of a mask released earlier goes to the next job's mask while a side stream still reads it
+        pins = [None if pin is None else self._pin_arrays(pin, job.n_nodes) for job, pin in zip(jobs, pins)]
+
+        def one(job, x_T, noise, pin):
+            return self.sample(job, x_T, noise, tables, check=False, coef=coef, streams=1, pin=pin, kind=kind)
+
+        outs = self._on_streams([lambda a=a: one(*a) for a in zip(jobs, x_Ts, noises, pins)], len(jobs))
         if check:
             for job in jobs:
                 self.check_status(job)
@@ -398,17 +395,13 @@ class Denoiser:
 
     def _ode_fixed(self, job, y0, method, dts, mods):
         """One codlad_ode_loop call on the current stream -> traj [len(dts) + 1, n_nodes, 3]."""
-        st = job.structures
         f32 = dict(dtype=torch.float32, device=self.device)
         y0 = y0.contiguous().float()
         traj = torch.empty(len(dts) + 1, job.n_nodes, 3, **f32)
         scratch = torch.empty(5, job.n_nodes, 3, **f32)
         dt = (C.c_float * len(dts))(*dts)
-        rc = self.lib.codlad_ode_loop(C.byref(self.weights.struct), _lib.ptr(job.node_info), job.n_nodes,
-                                      _lib.ptr(st.E_idx), _lib.ptr(st.h_E0), _lib.ptr(st.E1), st.n_snodes, _lib.ptr(y0),
-                                      _lib.ptr(traj), _lib.ptr(mods), _lib.ODE_METHODS[method], dt, len(dts),
-                                      _lib.ptr(scratch), C.byref(job.ws), _lib.stream_ptr(self.device))
-        _lib.check(rc, "codlad_ode_loop")
+        self._run("codlad_ode_loop", job.desc(), _lib.ptr(y0), _lib.ptr(traj), _lib.ptr(mods), _lib.ODE_METHODS[method], dt,
+                  len(dts), _lib.ptr(scratch))
         return traj
 
     def sample_ode(self, job, y0, ts, method="dopri5", rtol=1e-7, atol=1e-9, check=True, streams=None, max_steps=100000,
@@ -440,8 +433,7 @@ class Denoiser:
         mods = self.step_mods(ode.stage_times(method, ts))
         dts = [b - a for a, b in zip(ts, ts[1:])]
         stats = {"n_eval": stages * len(dts), "n_accept": len(dts), "n_reject": 0}
-        if streams is None:
-            streams = 2 if job.n_nodes >= self.SPLIT_MIN_NODES and len(job.sample_struct) >= 2 else 1
+        streams = self._n_streams(job, streams)
         if streams <= 1:
             traj = self._ode_fixed(job, y0, method, dts, mods)
             if check:
@@ -484,7 +476,7 @@ class Denoiser:
             _lib.ptr(t_) for t_ in (y, y1, xin, mods, state, norm))
         for j in range(7):
             bufs.k[j] = k[j].data_ptr()
-        st = job.structures
+        desc = job.desc()
         traj = torch.empty(len(ts), n, 3, **f32)
         traj[0] = y
         nxt, attempts = 1, 0
@@ -493,11 +485,7 @@ class Denoiser:
             if attempts > max_steps:
                 raise RuntimeError("dopri5: max_steps exceeded")
             t_before = host.t
-            rc = self.lib.codlad_ode_dopri5_attempt(C.byref(self.weights.struct), _lib.ptr(job.node_info), n,
-                                                    _lib.ptr(st.E_idx), _lib.ptr(st.h_E0), _lib.ptr(st.E1), st.n_snodes,
-                                                    C.byref(bufs), C.c_double(ts[nxt]), C.c_float(rtol), C.c_float(atol),
-                                                    C.byref(job.ws), _lib.stream_ptr(self.device))
-            _lib.check(rc, "codlad_ode_dopri5_attempt")
+            self._run("codlad_ode_dopri5_attempt", desc, C.byref(bufs), C.c_double(ts[nxt]), C.c_float(rtol), C.c_float(atol))
             host = _lib.OdeState.from_buffer_copy(state.cpu().numpy().tobytes())   # the one readback: copy + synchronise
             if host.nonfinite or (check and host.status):
                 job.status.zero_()
@@ -614,21 +602,15 @@ class Denoiser:
         return self.q_affine("q_sample", x_start, noise, job.sample_lens, t, self.loss_table(tables, coef))[0]
 
     def _t_group_job(self, job, members, start):
-        """The ragged sub-job of the samples `members` of `job` -> (job, node indices of its samples in `job`).  Like
-        Job.parts, it keeps its edge state in a slice of the parent's buffer, from node `start` (the groups of a call are
-        disjoint, and a job and its sub-jobs are never in flight together); the small tables are its own.  Cached on the
-        job, which keeps the tensors alive: that pays when a grouping recurs (a fixed evaluation schedule, a shared
-        timestep pattern per batch); with random timesteps it rarely does, so the cache is kept small."""
+        """Job.sub_job of the samples `members` from node `start`, cached on the job, which keeps the tensors alive: that
+        pays when a grouping recurs (a fixed evaluation schedule, a shared timestep pattern per batch); with random
+        timesteps it rarely does, so the cache is kept small."""
         cache = job.__dict__.setdefault("_t_groups", {})
         key = (start, tuple(members))
         if key not in cache:
             if len(cache) >= 64:
                 cache.clear()
-            n = int(sum(job.sample_lens[m] for m in members))
-            sub = Job(job.structures, [job.sample_struct[m] for m in members], self.device,
-                      edge_state=job.hE[start:start + n])
-            idx = np.concatenate([np.arange(job.sample_off[m], job.sample_off[m + 1]) for m in members])
-            cache[key] = (sub, torch.from_numpy(idx).to(self.device))
+            cache[key] = job.sub_job(members, start)
         return cache[key]
 
     def _check_all(self, jobs):
@@ -643,7 +625,8 @@ class Denoiser:
             raise first
 
     def _on_streams(self, tasks, n_streams=2):
-        """Runs the callables round-robin on up to n_streams side streams (sample_many's arrangement) -> their results."""
+        """Runs the callables round-robin on up to n_streams side streams -> their results.  The side streams first wait for
+        the caller's, so they see what it has enqueued (features, step tables, pin arrays); the caller's then waits for them."""
         if not hasattr(self, "_streams"):
             self._streams = []
         n_streams = min(n_streams, len(tasks))
@@ -661,17 +644,12 @@ class Denoiser:
         return outs
 
     def _loss_forward(self, job, x_start, x_t, noise, t, coef_dev, T, mods, x_self_cond, want_model_out):
-        st = job.structures
         res, terms = self._loss_outputs(len(job.sample_struct), job.n_nodes, self.device, noise)
         if want_model_out:
             res["model_out"] = torch.empty(job.n_nodes, self.weights.out_dim, dtype=torch.float32, device=self.device)
-        rc = self.lib.codlad_loss_forward(C.byref(self.weights.struct), _lib.ptr(job.node_info), job.n_nodes,
-                                          _lib.ptr(st.E_idx), _lib.ptr(st.h_E0), _lib.ptr(st.E1), st.n_snodes,
-                                          _lib.ptr(x_start), _lib.ptr(x_t), _lib.ptr(noise), _lib.ptr(x_self_cond),
-                                          _lib.ptr(mods[t]), _lib.ptr(coef_dev), T, t, _lib.ptr(self._job_offsets(job)),
-                                          len(job.sample_struct), _lib.ptr(res.get("model_out")), C.byref(terms),
-                                          C.byref(job.ws), _lib.stream_ptr(self.device))
-        _lib.check(rc, "codlad_loss_forward")
+        self._run("codlad_loss_forward", job.desc(), _lib.ptr(x_start), _lib.ptr(x_t), _lib.ptr(noise), _lib.ptr(x_self_cond),
+                  _lib.ptr(mods[t]), _lib.ptr(coef_dev), T, t, _lib.ptr(self._job_offsets(job)), len(job.sample_struct),
+                  _lib.ptr(res.get("model_out")), C.byref(terms))
         return res
 
     def _check_loss_model(self, coef):
@@ -756,8 +734,7 @@ class Denoiser:
         _require_cuda(x_start, "x_start")
         _require_cuda(noise, "noise")
         assert x_start.shape == (job.n_nodes, 3) and noise.shape == (T, job.n_nodes, 3)
-        if streams is None:
-            streams = 2 if job.n_nodes >= self.SPLIT_MIN_NODES and S >= 2 else 1
+        streams = self._n_streams(job, streams)
         self._fresh_features(job.structures)
         mods = self.step_mods(tables.timestep_map)
         coef_dev = torch.from_numpy(coef).to(self.device)
@@ -769,14 +746,9 @@ class Denoiser:
             out = {k: torch.empty(T, n, **f32) for k in ("vb", "mse", "xstart_mse")}
             out.update({k: torch.empty(n, **f32) for k in ("prior_bpd", "total_bpd")})
             x_t = torch.empty_like(x0)
-            st = jb.structures
-            rc = self.lib.codlad_bpd_loop(C.byref(self.weights.struct), _lib.ptr(jb.node_info), jb.n_nodes,
-                                          _lib.ptr(st.E_idx), _lib.ptr(st.h_E0), _lib.ptr(st.E1), st.n_snodes, _lib.ptr(x0),
-                                          _lib.ptr(eps), _lib.ptr(x_t), _lib.ptr(mods), _lib.ptr(coef_dev), T,
-                                          _lib.ptr(self._job_offsets(jb)), n, _lib.ptr(out["vb"]), _lib.ptr(out["mse"]),
-                                          _lib.ptr(out["xstart_mse"]), _lib.ptr(out["prior_bpd"]),
-                                          _lib.ptr(out["total_bpd"]), C.byref(jb.ws), _lib.stream_ptr(self.device))
-            _lib.check(rc, "codlad_bpd_loop")
+            self._run("codlad_bpd_loop", jb.desc(), _lib.ptr(x0), _lib.ptr(eps), _lib.ptr(x_t), _lib.ptr(mods), _lib.ptr(coef_dev),
+                      T, _lib.ptr(self._job_offsets(jb)), n,
+                      *(_lib.ptr(out[k]) for k in ("vb", "mse", "xstart_mse", "prior_bpd", "total_bpd")))
             return out
 
         if streams <= 1:

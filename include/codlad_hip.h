@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define CODLAD_ABI_VERSION 18
+#define CODLAD_ABI_VERSION 19
 #define CODLAD_H 128          /* hidden width of the denoiser                          */
 #define CODLAD_KNN 64         /* k_neighbors (reference models/latent_model.py:86)      */
 #define CODLAD_MODS_PER_STEP 6016 /* 3*9*128 (enc) + 3*6*128 (dec) + 2*128 (final)      */
@@ -42,9 +42,9 @@ extern "C" {
 int codlad_abi_version(void);
 const char *codlad_last_error(void);
 /* sizeof(codlad_denoiser_weights), sizeof(codlad_decoder_weights), sizeof(codlad_workspace),
- * offsetof(codlad_denoiser_weights, precision), offsetof(.., enc_h): lets a binding verify its
- * struct mirrors. */
-void codlad_struct_sizes(int *out5);
+ * offsetof(codlad_denoiser_weights, precision), offsetof(.., enc_h), sizeof(codlad_job), offsetof(codlad_job, ws):
+ * lets a binding verify its struct mirrors. */
+void codlad_struct_sizes(int *out7);
 
 /* 128x128 weight block -> MFMA A-operand order (host helper; src/dst are HOST pointers).
  * dst[(16*b + r)*256 + lane*4 + bo] = src[(32*bo + (lane&31))*ld + 32*b + (r&3) + 8*(r>>2) + 4*(lane>>5)]
@@ -208,6 +208,16 @@ typedef struct {
     const int32_t *xcd_bounds;
 } codlad_workspace;
 
+/* "This job on these structures": what every entry point that runs the denoiser takes after the weights.  The caller
+ * owns everything it points to, until the call has returned. */
+typedef struct {
+    const int32_t *node_info; int n_nodes;       /* per sample node {src, base, K, z} (ragged layout above); n_nodes > 0 */
+    const int32_t *E_idx; const float *h_E0;     /* of the structures (codlad_features_prepass) */
+    const float *E1;                             /* may be NULL (codlad_layer0_edge_terms): the layer-0 kernels then contract h_E0 */
+    int n_snodes;                                /* structure-node count of E_idx / h_E0 / E1 */
+    const codlad_workspace *ws;                  /* hV, hVenc, S, PQ and hE are required */
+} codlad_job;
+
 /* HOST helper (every pointer is a HOST pointer): the walk of the per-node edge kernels over a job, from the helpers the
  * kernels themselves decide with.  K_host[n] = node_info[n].K; n_workgroups x waves_per_workgroup = the persistent grid
  * (one 8-wave workgroup per CU: 256, 8 on MI355X).  pair != 0: paired last tiles (CODLAD_OPT_EDGE_PAIR) - a node whose
@@ -245,13 +255,10 @@ int codlad_layer0_edge_terms(const codlad_denoiser_weights *w, const int32_t *sn
 
 /* Rows 5-7: one denoiser forward (latent_model.py:175-268): x [n_nodes][3] -> out [n_nodes][6].
  * (out [n_nodes][3] for a flow-matching model, out_dim 3).
- * mods_t = the 6016 modulation floats of this timestep.  E1 (may be NULL) from
- * codlad_layer0_edge_terms, n_snodes = its structure-node count.  x_self_cond [n_nodes][3]: only for
+ * mods_t = the 6016 modulation floats of this timestep.  x_self_cond [n_nodes][3]: only for
  * a self_condition model, NULL = zeros (latent_model.py:211). */
-int codlad_denoiser_forward(const codlad_denoiser_weights *w, const int32_t *node_info,
-                            int n_nodes, const int32_t *E_idx, const float *h_E0,
-                            const float *E1, int n_snodes, const float *x, const float *x_self_cond,
-                            const float *mods_t, float *out, const codlad_workspace *ws, void *stream);
+int codlad_denoiser_forward(const codlad_denoiser_weights *w, const codlad_job *job, const float *x,
+                            const float *x_self_cond, const float *mods_t, float *out, void *stream);
 
 /* Row 2: one reverse step given the model output (gaussian_diffusion.py:404-449, 262-360).
  * coef_host[8] = {sqrt_recip_acp, sqrt_recipm1_acp, post_coef1, post_coef2,
@@ -292,21 +299,17 @@ int codlad_ddpm_posterior_step(const float *x, const float *pred_xstart, const f
  * loop order (entry 0 at step T-1).  mods [T][6016] and coef [T][8] (device) are indexed by
  * respaced step i; the loop runs i = T-1 .. 0.  x_start [n_nodes][3] (may be NULL unless the model
  * is self-conditioned) receives every step's pred_xstart and is what the next step is conditioned on. */
-int codlad_sample_loop(const codlad_denoiser_weights *w, const int32_t *node_info, int n_nodes,
-                       const int32_t *E_idx, const float *h_E0, const float *E1, int n_snodes,
-                       float *x, float *x_start, const float *noise, const float *mods, const float *coef,
-                       int T, const codlad_workspace *ws, void *stream);
+int codlad_sample_loop(const codlad_denoiser_weights *w, const codlad_job *job, float *x, float *x_start,
+                       const float *noise, const float *mods, const float *coef, int T, void *stream);
 
 /* codlad_sample_loop with residue pinning: the denoised_fn `x0 -> where(pin_mask, pin_x0, x0)` fused into every step.
  * pin_x0 [n_nodes][3] holds the known (normalised) latents, pin_mask [n_nodes] uint8 (0 = sampled, else pinned).  At a
  * pinned node each step's raw pred_xstart is replaced by pin_x0 before the clamp (mode bit 4), so x_start and the
  * posterior mean see the pinned value; with the last step's post_coef1 = 1, post_coef2 = 0 and no noise a pinned node
  * ends on pin_x0 exactly (clamped when bit 4 is set).  The other arguments as for codlad_sample_loop. */
-int codlad_sample_loop_pinned(const codlad_denoiser_weights *w, const int32_t *node_info, int n_nodes,
-                              const int32_t *E_idx, const float *h_E0, const float *E1, int n_snodes,
-                              float *x, float *x_start, const float *noise, const float *mods, const float *coef,
-                              int T, const float *pin_x0, const uint8_t *pin_mask, const codlad_workspace *ws,
-                              void *stream);
+int codlad_sample_loop_pinned(const codlad_denoiser_weights *w, const codlad_job *job, float *x, float *x_start,
+                              const float *noise, const float *mods, const float *coef, int T, const float *pin_x0,
+                              const uint8_t *pin_mask, void *stream);
 
 /* DDIM (Song et al. 2021; the IDDPM release's ddim_sample_loop / ddim_reverse_sample_loop over the same respaced tables).
  * coef [T][8] (device) and coef_host[8] are rows of Tables.ddim_coefficients, every schedule factor in fp32 as the
@@ -323,11 +326,10 @@ int codlad_sample_loop_pinned(const codlad_denoiser_weights *w, const int32_t *n
  *   the model (6 outputs without bit 2, 3 with it); column 7 of coef is not read.  pin_x0 / pin_mask (both NULL, or
  *   both given) as for codlad_sample_loop_pinned.  x_start [n_nodes][3] carries pred_xstart step to step (required for a
  *   self-conditioned model; step k reads step k-1's, the first step none). */
-int codlad_ddim_loop(const codlad_denoiser_weights *w, const int32_t *node_info, int n_nodes, const int32_t *E_idx,
-                     const float *h_E0, const float *E1, int n_snodes, float *x, float *x_start,
+int codlad_ddim_loop(const codlad_denoiser_weights *w, const codlad_job *job, float *x, float *x_start,
                      const float *noise /* NULL iff reverse */, const float *mods, const float *coef, int T, int mode,
                      int reverse, const float *pin_x0 /* may be NULL */, const uint8_t *pin_mask /* may be NULL */,
-                     const codlad_workspace *ws, void *stream);
+                     void *stream);
 
 /* codlad_ddim_step: one DDIM update after a caller's denoised_fn / cond_fn, given the processed pred_xstart
  *   [n_nodes][3] (codlad_ddpm_pred_xstart gives the raw one; the two round like one fused step): bit 4 of
@@ -392,12 +394,10 @@ int codlad_prior_bpd(const float *x_start, const float *coef, int T, const int32
  * the final layer fused into their kernel: its head gives the bits of codlad_denoiser_forward's output.  model_out
  * [n_nodes][out_dim] (may be NULL) receives that output.  x_self_cond as for codlad_denoiser_forward.  The workspace's
  * status word is set as by every forward. */
-int codlad_loss_forward(const codlad_denoiser_weights *w, const int32_t *node_info, int n_nodes, const int32_t *E_idx,
-                        const float *h_E0, const float *E1, int n_snodes, const float *x_start, const float *x_t,
+int codlad_loss_forward(const codlad_denoiser_weights *w, const codlad_job *job, const float *x_start, const float *x_t,
                         const float *noise /* may be NULL */, const float *x_self_cond /* may be NULL */,
                         const float *mods_t, const float *coef, int T, int t, const int32_t *sample_off, int n_samples,
-                        float *model_out /* may be NULL */, const codlad_loss_terms *terms, const codlad_workspace *ws,
-                        void *stream);
+                        float *model_out /* may be NULL */, const codlad_loss_terms *terms, void *stream);
 
 /* The variational bound over all T steps, fused (calc_bpd_loop): for i = T-1 .. 0, x_t = q_sample of x_start with noise
  * entry T-1-i (loop order, as the sampling loops consume theirs) at step i, one forward with mods row i, then the terms
@@ -405,11 +405,9 @@ int codlad_loss_forward(const codlad_denoiser_weights *w, const int32_t *node_in
  * [n_samples] and total_bpd [n_samples] = vb summed in loop order, + prior_bpd.  x_t [n_nodes][3] is scratch.  No host
  * synchronisation; the sticky status word as in the sampling loops.  A self-conditioned model is conditioned on zeros
  * (calc_bpd_loop has no self-conditioning). */
-int codlad_bpd_loop(const codlad_denoiser_weights *w, const int32_t *node_info, int n_nodes, const int32_t *E_idx,
-                    const float *h_E0, const float *E1, int n_snodes, const float *x_start, const float *noise,
+int codlad_bpd_loop(const codlad_denoiser_weights *w, const codlad_job *job, const float *x_start, const float *noise,
                     float *x_t, const float *mods, const float *coef, int T, const int32_t *sample_off, int n_samples,
-                    float *vb, float *mse, float *xstart_mse, float *prior_bpd, float *total_bpd,
-                    const codlad_workspace *ws, void *stream);
+                    float *vb, float *mse, float *xstart_mse, float *prior_bpd, float *total_bpd, void *stream);
 
 /* Next row 8f-4, fused: the ODE samplers of the flow-matching models as one call per fixed grid / per attempted adaptive
  * step.  ode_stage_kernel takes final_kernel's place after a forward: the final layer's 3-row velocity head (the bits of
@@ -427,10 +425,8 @@ int codlad_bpd_loop(const codlad_denoiser_weights *w, const int32_t *node_info, 
 #define CODLAD_ODE_EULER 0
 #define CODLAD_ODE_MIDPOINT 1
 #define CODLAD_ODE_RK4 2
-int codlad_ode_loop(const codlad_denoiser_weights *w, const int32_t *node_info, int n_nodes, const int32_t *E_idx,
-                    const float *h_E0, const float *E1, int n_snodes, const float *y, float *traj, const float *mods,
-                    int method, const float *dt_host, int n_intervals, float *scratch, const codlad_workspace *ws,
-                    void *stream);
+int codlad_ode_loop(const codlad_denoiser_weights *w, const codlad_job *job, const float *y, float *traj,
+                    const float *mods, int method, const float *dt_host, int n_intervals, float *scratch, void *stream);
 
 /* State of the adaptive method (Dormand-Prince 5(4), torchdiffeq's controller) on the DEVICE; the host writes t and h
  * once and reads the block back after every attempt. */
@@ -462,10 +458,8 @@ typedef struct {
  * ode_stage_kernel, the error norm with the controller in its second pass (accept: ratio <= 1; factor: safety 0.9,
  * growth in [0.2, 10], 1 at least when accepted, 10 at ratio 0; after an accepted clipped step h = max(h, hh * factor)
  * and t = t_end exactly), and the commit (accepted: y1 -> y, k[6] -> k[0]).  t_end is stored into the state first. */
-int codlad_ode_dopri5_attempt(const codlad_denoiser_weights *w, const int32_t *node_info, int n_nodes,
-                              const int32_t *E_idx, const float *h_E0, const float *E1, int n_snodes,
-                              const codlad_ode_dopri5_bufs *bufs, double t_end, float rtol, float atol,
-                              const codlad_workspace *ws, void *stream);
+int codlad_ode_dopri5_attempt(const codlad_denoiser_weights *w, const codlad_job *job,
+                              const codlad_ode_dopri5_bufs *bufs, double t_end, float rtol, float atol, void *stream);
 
 /* Row 8: get_norm_feature(norm_in=False) + nearest code
  * (utils/dataset_module.py:253; utils/vq_module.py:61-68 / VectorQuantize eval lookup).

@@ -145,8 +145,8 @@ def test_ddim_entry_points_validate_their_arguments():
     wp = ctypes.byref(w)
 
     def loop(w=wp, node_info=p, T=10, mode=0, reverse=0, noise=p, x_start=None, pin_x0=None, pin_mask=None, x=p):
-        return lib.codlad_ddim_loop(w, node_info, 4, p, p, None, 1, x, x_start, noise, p, p, T, mode, reverse, pin_x0,
-                                    pin_mask, None, None)
+        job = _lib.JobDesc(node_info, 4, p, p, None, 1, None)
+        return lib.codlad_ddim_loop(w, ctypes.byref(job), x, x_start, noise, p, p, T, mode, reverse, pin_x0, pin_mask, None)
 
     assert loop(w=None) == -1 and b"codlad_ddim_loop: null pointer" in lib.codlad_last_error()
     assert loop(x=None) == -1 and b"null pointer" in lib.codlad_last_error()

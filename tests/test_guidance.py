@@ -3,6 +3,7 @@ respace.py:99-100, 117-129) on the HIP path - residue pinning fused into the loo
 callable between the halves of the split step (codlad_ddpm_pred_xstart / codlad_ddpm_posterior_step) - against the
 reference's own loops (g17 goldens, tests/guidance_cases.py), and `test.py --fix_residues` end to end.  The CPU part
 checks argument validation: PinLatents, the residue spec and the new C entry points."""
+import ctypes
 import importlib.util
 import os
 import subprocess
@@ -135,7 +136,8 @@ def test_new_entry_points_validate_their_arguments():
     assert b"codlad_ddpm_posterior_step: null pointer" in lib.codlad_last_error()
     assert lib.codlad_ddpm_posterior_step(p, p, p, p, None, coef, 0.0, -1, p, None, None) == -1
     assert b"n_nodes must be positive" in lib.codlad_last_error()
-    assert lib.codlad_sample_loop_pinned(None, p, 4, p, p, None, 1, p, None, p, p, p, 10, p, p, None, None) == -1
+    job = _lib.JobDesc(p, 4, p, p, None, 1, None)
+    assert lib.codlad_sample_loop_pinned(None, ctypes.byref(job), p, None, p, p, p, 10, p, p, None) == -1
     assert b"codlad_sample_loop_pinned: null pointer" in lib.codlad_last_error()
 
 
@@ -246,6 +248,32 @@ def test_two_streams_equal_one_stream_pinned_and_unpinned():
         assert torch.equal(one, two) and torch.equal(one, default)
         if pin is not None:
             assert torch.equal(one[mask], x0[mask])
+
+
+@gpu
+def test_sample_many_keeps_every_jobs_pin_arrays_until_the_streams_are_joined():
+    """Two pinned jobs with boolean masks through Denoiser.sample_many: each result is that of `sample` on the job alone, bit
+    for bit.  The masks are converted to uint8 - new tensors, on the caller's stream - before the jobs go to their side
+    streams, and stay referenced until those have been joined; released after each job's enqueue, the first job's mask
+    would be handed to the second job's conversion while the first loop still reads it."""
+    eng = guided_model("eps").engine()
+    prots = [synth.make_protein(L, 100 + L, n_frames=1) for L in (33, 65)]
+    st = eng.prepare_structures([torch.from_numpy(p["xyz_full"])[0, 1:-1] for p in prots],
+                                [torch.from_numpy(p["z_full"])[1:-1] for p in prots])
+    jobs = [eng.make_job(st, [0, 1, 0]), eng.make_job(st, [1, 0])]
+    T = 10
+    tables = create_diffusion(str(T))
+    gen = torch.Generator(device=DEV).manual_seed(23)
+    x_Ts = [torch.randn(j.n_nodes, 3, device=DEV, generator=gen) for j in jobs]
+    noises = [torch.randn(T, j.n_nodes, 3, device=DEV, generator=gen) for j in jobs]
+    pins = [(torch.randn(j.n_nodes, 3, device=DEV, generator=gen), torch.rand(j.n_nodes, device=DEV, generator=gen) < 0.3)
+            for j in jobs]
+    for kind in ("ddpm", "ddim"):
+        alone = [eng.sample(j, x, nz, tables, streams=1, pin=p, kind=kind) for j, x, nz, p in zip(jobs, x_Ts, noises, pins)]
+        together = eng.sample_many(jobs, x_Ts, noises, tables, pins=pins, kind=kind)
+        for a, b, (x0, mask) in zip(alone, together, pins):
+            assert torch.equal(a, b)
+            assert kind != "ddpm" or torch.equal(b[mask], x0[mask])
 
 
 def _cli(extra, cwd, timeout=600):

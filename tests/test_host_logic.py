@@ -32,13 +32,15 @@ def test_library_exports_every_declared_symbol():
 
 def test_struct_layouts_match_header():
     # the ctypes mirrors must have exactly the C structs' sizes and field offsets
-    out = (C.c_int * 5)()
+    out = (C.c_int * 7)()
     _lib.lib().codlad_struct_sizes(out)
     assert C.sizeof(_lib.DenoiserWeights) == out[0]
     assert C.sizeof(_lib.DecoderWeights) == out[1]
     assert C.sizeof(_lib.Workspace) == out[2]
     assert _lib.DenoiserWeights.precision.offset == out[3]
     assert _lib.DenoiserWeights.enc_h.offset == out[4]
+    assert C.sizeof(_lib.JobDesc) == out[5]
+    assert _lib.JobDesc.ws.offset == out[6]
     assert C.sizeof(_lib.EncLayer) == 26 * 8 and C.sizeof(_lib.DecLayer) == 19 * 8
     assert C.sizeof(_lib.EncLayerH) == 26 * 8 + 8 * 4 and C.sizeof(_lib.DecLayerH) == 19 * 8 + 5 * 4 + 4
 

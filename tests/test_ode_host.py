@@ -1,5 +1,6 @@
 """CPU-only checks of the fused ODE sampler's host side: the stage-time table the fused loop's modulation rows are computed
 from equals the times the step-wise `_fixed_step` evaluates the model at, the grid rules, and the C ABI's declarations."""
+import ctypes as C
 import os
 
 import pytest
@@ -64,8 +65,7 @@ def test_new_entry_points_are_declared():
         assert name in names
         assert hasattr(_lib.lib(), name)
     header = open(os.path.join(ROOT, "include", "codlad_hip.h")).read()
-    assert "#define CODLAD_ABI_VERSION 18\n" in header and _lib.ABI_VERSION == 18
-    import ctypes as C
+    assert "#define CODLAD_ABI_VERSION 19\n" in header and _lib.ABI_VERSION == 19
     assert C.sizeof(_lib.OdeState) == 96 and _lib.OdeState.hh_f.offset == 64 and _lib.OdeState.tf.offset == 68
     assert C.sizeof(_lib.OdeDopri5Bufs) == 13 * 8
     assert _lib.ODE_NORM_WORDS == int(header.split("#define CODLAD_ODE_NORM_BLOCKS ")[1].split()[0]) + 1
@@ -75,7 +75,43 @@ def test_argument_errors_are_reported_not_crashed():
     lib = _lib.lib()
     assert lib.codlad_ode_error_norm(None, None, None, 4, 1e-5, 1e-5, None, None) < 0
     assert b"null pointer" in lib.codlad_last_error()
-    assert lib.codlad_ode_loop(None, None, 1, None, None, None, 1, None, None, None, 0, None, 1, None, None, None) < 0
+    job = C.byref(_lib.JobDesc(None, 1, None, None, None, 1, None))
+    assert lib.codlad_ode_loop(None, job, None, None, None, 0, None, 1, None, None) < 0
     assert b"null pointer" in lib.codlad_last_error()
-    assert lib.codlad_ode_dopri5_attempt(None, None, 1, None, None, None, 1, None, 1.0, 1e-5, 1e-5, None, None) < 0
+    assert lib.codlad_ode_dopri5_attempt(None, job, None, 1.0, 1e-5, 1e-5, None) < 0
     assert b"null pointer" in lib.codlad_last_error()
+
+
+# every entry point that runs the denoiser: the out_dim it wants, and its own arguments between the job and the stream
+# (p = a dummy host pointer: no call below gets as far as reading one)
+JOB_ENTRY_POINTS = {
+    "codlad_denoiser_forward": (6, lambda p, bufs, terms: (p, None, p, p)),
+    "codlad_sample_loop": (6, lambda p, bufs, terms: (p, None, p, p, p, 10)),
+    "codlad_sample_loop_pinned": (6, lambda p, bufs, terms: (p, None, p, p, p, 10, p, p)),
+    "codlad_ddim_loop": (6, lambda p, bufs, terms: (p, None, p, p, p, 10, 0, 0, None, None)),
+    "codlad_loss_forward": (6, lambda p, bufs, terms: (p, p, p, None, p, p, 10, 3, p, 2, None, C.byref(terms))),
+    "codlad_bpd_loop": (6, lambda p, bufs, terms: (p, p, p, p, p, 10, p, 2, p, p, p, p, p)),
+    "codlad_ode_loop": (3, lambda p, bufs, terms: (p, p, p, 0, p, 1, p)),
+    "codlad_ode_dopri5_attempt": (3, lambda p, bufs, terms: (C.byref(bufs), 1.0, 1e-5, 1e-5)),
+}
+
+
+@pytest.mark.parametrize("name", list(JOB_ENTRY_POINTS))
+def test_a_defective_job_is_refused_under_the_callers_name(name):
+    lib = _lib.lib()
+    one = torch.zeros(12)
+    p = _lib.ptr(one)
+    out_dim, own = JOB_ENTRY_POINTS[name]
+    w = _lib.DenoiserWeights()
+    w.out_dim = out_dim
+    ws = _lib.Workspace()
+    ws.hV = ws.hVenc = ws.S = ws.PQ = ws.hE = p
+    bufs, terms = _lib.OdeDopri5Bufs(), _lib.LossTerms()
+    bufs.y = bufs.y1 = bufs.xin = bufs.mods = bufs.state = bufs.norm = p
+    for j in range(7):
+        bufs.k[j] = one.data_ptr()
+    good = dict(node_info=p, n_nodes=4, E_idx=p, h_E0=p, E1=None, n_snodes=1, ws=C.pointer(ws))
+    jobs = [None] + [C.byref(_lib.JobDesc(**dict(good, **bad))) for bad in (dict(ws=None), dict(node_info=None), dict(n_nodes=0))]
+    for job in jobs:
+        assert getattr(lib, name)(C.byref(w), job, *own(p, bufs, terms), None) == -1
+        assert lib.codlad_last_error().startswith(name.encode() + b": ")
