@@ -19,8 +19,8 @@ SOURCES = ["api.hip", "host_util.hip", "edge_plan.hip", "denoiser_forward.hip", 
 # and code indices): no implicit FMA contraction there; intended FMAs are written as fmaf().
 EXTRA_FLAGS = {"features_kernels.hip": ["-ffp-contract=off"], "ode_kernels.hip": ["-ffp-contract=off"], "decode_kernels.hip": ["-ffp-contract=off"],
                "ic_decoder_kernels.hip": ["-ffp-contract=off"],
-               # the loss terms round as the reference's unfused tensor ops; final_kernel's head, repeated there, asks for
-               # contraction itself (loss_kernels.hip)
+               # the loss terms round as the reference's unfused tensor ops; the head it shares with final_kernel asks for
+               # contraction itself (final_head.h)
                "loss_kernels.hip": ["-ffp-contract=off"],
                "metrics_kernels.hip": ["-ffp-contract=off"], "encoder_kernels.hip": ["-ffp-contract=off"],
                # the SLP vectoriser pairs multiply-adds of different result blocks into v_pk_fma_f32 and pays for it in register

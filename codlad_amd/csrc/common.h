@@ -717,29 +717,11 @@ DEV void tile_modulate(Tile &t, const float *shift, const float *scale, const fl
 // *x0_out (optional) receives pred_xstart, the self-conditioning input of the next step.
 // *pin (optional): residue pinning, the denoised_fn `where(mask, x0_known, x)` fused - the raw pred_xstart is replaced
 // by *pin before the clamp (gaussian_diffusion.py:335-340: denoised_fn first, then clip_denoised).
+// ddpm_step is its three pieces in a row; the split step around a caller's denoised_fn / cond_fn (codlad_ddpm_pred_xstart /
+// codlad_ddpm_posterior_step) and the loss terms call the same pieces, so all of them round alike.
 #define CODLAD_DDPM_START_X 1
 #define CODLAD_DDPM_FIXED_VAR 2
 #define CODLAD_DDPM_CLIP 4
-DEV float ddpm_step(float xt, float out, float v, const float *cf, float noise, float *x0_out = nullptr,
-                    const float *pin = nullptr) {
-#pragma clang fp contract(off)
-    const int mode = (int)cf[7];
-    float logvar = cf[4];
-    if (!(mode & CODLAD_DDPM_FIXED_VAR)) {
-        const float frac = (v + 1.0f) / 2.0f;
-        logvar = frac * cf[5] + (1.0f - frac) * cf[4];
-    }
-    float x0 = (mode & CODLAD_DDPM_START_X) ? out : cf[0] * xt - cf[1] * out;
-    if (pin) x0 = *pin;
-    if (mode & CODLAD_DDPM_CLIP) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-    const float mean = cf[2] * x0 + cf[3] * xt;
-    if (x0_out) *x0_out = x0;
-    return mean + (cf[6] * expf(0.5f * logvar)) * noise;
-}
-
-// ddpm_step split in two around a caller's denoised_fn / cond_fn (codlad_ddpm_pred_xstart / codlad_ddpm_posterior_step).
-// Its expressions, written out again (folding ddpm_step onto these pieces reschedules final_kernel's code): a pin applied
-// between the halves rounds exactly as the fused one.  Keep the three in step with ddpm_step.
 // The raw pred_xstart, before denoised_fn and the clamp (gaussian_diffusion.py:343-349).
 DEV float ddpm_raw_x0(float xt, float out, const float *cf) {
 #pragma clang fp contract(off)
@@ -756,8 +738,8 @@ DEV float ddpm_log_variance(float v, const float *cf) {
     return logvar;
 }
 
-// clamp, posterior mean, optional classifier guidance mean += variance * grad (gaussian_diffusion.py:374-384, 436-446),
-// then the noise term
+// x0 = pred_xstart after denoised_fn: clamp, posterior mean, optional classifier guidance mean += variance * grad
+// (gaussian_diffusion.py:374-384, 436-446), then the noise term
 DEV float ddpm_posterior(float xt, float x0, float logvar, const float *cf, float noise, float *x0_out,
                          const float *grad, float variance) {
 #pragma clang fp contract(off)
@@ -766,6 +748,12 @@ DEV float ddpm_posterior(float xt, float x0, float logvar, const float *cf, floa
     if (x0_out) *x0_out = x0;
     if (grad) mean = mean + variance * *grad;
     return mean + (cf[6] * expf(0.5f * logvar)) * noise;
+}
+
+DEV float ddpm_step(float xt, float out, float v, const float *cf, float noise, float *x0_out = nullptr,
+                    const float *pin = nullptr) {
+    return ddpm_posterior(xt, pin ? *pin : ddpm_raw_x0(xt, out, cf), ddpm_log_variance(v, cf), cf, noise, x0_out, nullptr,
+                          0.f);
 }
 
 // One DDIM update of a scalar (Song et al. 2021, the IDDPM release's ddim_sample / ddim_reverse_sample), every product,

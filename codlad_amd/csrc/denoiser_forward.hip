@@ -253,10 +253,14 @@ static const char *job_defect(const codlad_denoiser_weights *w, const codlad_job
 }
 #define REQUIRE_OK(defect) do { const char *msg_ = (defect); CODLAD_REQUIRE(!msg_, msg_); } while (0)
 
+// the final layer's head on the forward's hV (final_head.h), for final_kernel, loss_kernel and ode_stage_kernel
+static HeadArgs head_args(const codlad_denoiser_weights *w, const codlad_job *job, const float *mods_t) {
+    return {job->ws->hV, mods_t + mods_offset(6), w->out_w, w->out_b, job->n_nodes};
+}
+
 static FinalArgs final_args(const codlad_denoiser_weights *w, const codlad_job *job, const float *mods_t) {
-    FinalArgs fa = {};
-    fa.hV = job->ws->hV; fa.mods = mods_t + mods_offset(6); fa.out_w = w->out_w; fa.out_b = w->out_b;
-    fa.n_nodes = job->n_nodes; fa.status = job->ws->status; fa.n_out = w->out_dim;
+    FinalArgs fa = {head_args(w, job, mods_t)};
+    fa.status = job->ws->status; fa.n_out = w->out_dim;
     return fa;
 }
 
@@ -405,9 +409,8 @@ extern "C" int codlad_bpd_loop(const codlad_denoiser_weights *w, const codlad_jo
 // The fused ODE samplers of the flow-matching models (ode_kernels.hip): ode_stage_kernel takes final_kernel's place after
 // enqueue_forward.  x_self_cond = null throughout: zeros, as the reference's run_sampling calls the model.
 static OdeStageArgs ode_stage_args(const codlad_denoiser_weights *w, const codlad_job *job, const float *mods_t) {
-    OdeStageArgs a = {};
-    a.hV = job->ws->hV; a.mods = mods_t + mods_offset(6); a.out_w = w->out_w; a.out_b = w->out_b;
-    a.n_nodes = job->n_nodes; a.status = job->ws->status; a.self = -1;
+    OdeStageArgs a = {head_args(w, job, mods_t)};
+    a.status = job->ws->status; a.self = -1;
     return a;
 }
 

@@ -4,42 +4,15 @@
 // diffusion_utils.py:10-88; the bound loop is the IDDPM release's calc_bpd_loop.
 //
 // Built with -ffp-contract=off: every product, sum and quotient below rounds separately, as the reference's elementwise
-// tensor ops do.  The one exception is final_head, which has to give the bits of final_kernel (sampler_kernels.hip, a
-// unit built with contraction on): it carries that kernel's expressions under `#pragma clang fp contract(fast)`.
+// tensor ops do.  The one exception is final_head (final_head.h), shared with final_kernel (sampler_kernels.hip, a unit
+// built with contraction on): it asks for contraction itself.
 //
 // Reductions: one workgroup per sample.  Half wave w of the eight takes the sample's nodes w, w + 8, ... in order, lane k
 // < 3 of it adds component k's value to its running sum; then (lane 0 + lane 1) + lane 2 per half wave, then half waves
 // 0 .. 7 in order.  The order depends on the sample's length alone: not on the grid, not on what else shares the job,
 // and no floating-point atomic is involved.
 #include "loss_args.h"
-
-DEV float half_wave_allsum(float v) {
-#pragma unroll
-    for (int m = 16; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
-// final_kernel's head: LayerNorm, modulation, Linear 128 -> n_out, for node nc, on the 32 lanes of a half wave.
-// Keep in step with final_kernel (tests hold the two to each other bit for bit).
-DEV void final_head(const FinalArgs &a, int nc, int l, float (&o)[6]) {
-#pragma clang fp contract(fast)
-    const float4 v = reinterpret_cast<const float4 *>(a.hV + (size_t)nc * HD)[l];
-    const float mean = half_wave_allsum((v.x + v.y) + (v.z + v.w)) * (1.0f / 128.0f);
-    const float d0 = v.x - mean, d1 = v.y - mean, d2 = v.z - mean, d3 = v.w - mean;
-    const float var = half_wave_allsum((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3));
-    const float rstd = 1.0f / sqrtf(var * (1.0f / 128.0f) + 1e-6f);
-    const float4 sh = reinterpret_cast<const float4 *>(a.mods)[l], sc = reinterpret_cast<const float4 *>(a.mods + HD)[l];
-    const float m0 = (d0 * rstd) * (1.0f + sc.x) + sh.x, m1 = (d1 * rstd) * (1.0f + sc.y) + sh.y,
-                m2 = (d2 * rstd) * (1.0f + sc.z) + sh.z, m3 = (d3 * rstd) * (1.0f + sc.w) + sh.w;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        o[k] = 0.f;
-        if (k < a.n_out) {
-            const float4 w = reinterpret_cast<const float4 *>(a.out_w + k * HD)[l];
-            o[k] = half_wave_allsum(fmaf(m3, w.w, fmaf(m2, w.z, fmaf(m1, w.y, m0 * w.x)))) + a.out_b[k];
-        }
-    }
-}
+#include "final_head.h"
 
 // diffusion_utils.py:10-36, the sum in the reference's order
 DEV float normal_kl(float mean1, float logvar1, float mean2, float logvar2) {
@@ -74,12 +47,8 @@ DEV float discretized_gaussian_log_likelihood(float x, float mean, float log_sca
 // (not read under the fixed-variance bit), cf = the step's row of Tables.loss_coefficients.  Returns pred_xstart.
 DEV float loss_element(float o, float v, float x0, float xt, float noise, const float *cf, float (&term)[5]) {
     const int mode = (int)cf[7];
-    float logvar = cf[4];
-    if (!(mode & CODLAD_DDPM_FIXED_VAR)) {
-        const float frac = (v + 1.0f) / 2.0f;
-        logvar = frac * cf[5] + (1.0f - frac) * cf[4];
-    }
-    float pred = (mode & CODLAD_DDPM_START_X) ? o : cf[0] * xt - cf[1] * o;
+    const float logvar = ddpm_log_variance(v, cf);
+    float pred = ddpm_raw_x0(xt, o, cf);
     if (mode & CODLAD_DDPM_CLIP) pred = fminf(fmaxf(pred, -1.0f), 1.0f);
     const float mean = cf[2] * pred + cf[3] * xt;
     const float true_mean = cf[2] * x0 + cf[3] * xt;
@@ -140,24 +109,9 @@ __global__ __launch_bounds__(256) void loss_kernel(LossArgs a) {
         const int nc = live ? n : end - 1;                 // whole half waves stay converged for the shuffles
         float o[6];
         if constexpr (HEAD) {
-            final_head(a.head, nc, l, o);
-            if (live && a.head.status && l == 0) {
-                // final_kernel's test: inf / NaN by exponent bits, on bits the compiler cannot reason about as floats
-                bool bad = false;
-#pragma unroll
-                for (int k = 0; k < 6; ++k) {
-                    unsigned u = __float_as_uint(o[k]);
-                    asm volatile("" : "+v"(u));
-                    bad |= (u & 0x7f800000u) == 0x7f800000u;
-                }
-                if (bad) atomicOr(a.head.status, CODLAD_STATUS_NONFINITE);
-            }
-            if (live && a.head.logits && l < a.head.n_out) {
-                float mine = o[0];
-#pragma unroll
-                for (int k = 1; k < 6; ++k) mine = l == k ? o[k] : mine;
-                a.head.logits[(size_t)n * a.head.n_out + l] = mine;
-            }
+            final_head(a.head, a.head.n_out, nc, l, o);
+            if (live && a.head.status && l == 0 && any_nonfinite(o)) atomicOr(a.head.status, CODLAD_STATUS_NONFINITE);
+            if (live && a.head.logits) store_logits(a.head.logits, a.head.n_out, n, l, o);
         } else {
 #pragma unroll
             for (int k = 0; k < 6; ++k) o[k] = k < width ? a.model_out[(size_t)nc * width + k] : 0.f;

@@ -7,11 +7,7 @@ static_assert(sizeof(codlad_ode_state) == 96 && sizeof(codlad_ode_dopri5_bufs) =
               "codlad_ode_state / codlad_ode_dopri5_bufs: the ctypes mirrors of _lib.py assume this layout");
 
 // ode_stage_kernel: the final layer's velocity head on hV, then out = y + sum_m k[m] * (coef[m] * h), m < n_k in order.
-struct OdeStageArgs {
-    const float *hV;
-    const float *mods;      // shift, scale (2 x 128) of the stage's time
-    const float *out_w, *out_b;
-    int n_nodes;
+struct OdeStageArgs : HeadArgs {     // mods: of the stage's time
     int *status;            // sticky status word or null (CODLAD_STATUS_NONFINITE)
     float *k_out;           // [n][3]: this stage's slope
     const float *y;         // [n][3]

@@ -4,10 +4,11 @@
 // and the commit.
 //
 // Built with -ffp-contract=off: every product and sum of the updates rounds separately, as torchdiffeq's tensor ops do.
-// The one exception is ode_head, which has to give the bits of final_kernel (sampler_kernels.hip, a unit built with
-// contraction on): it carries that kernel's expressions under `#pragma clang fp contract(fast)`, as loss_kernels.hip does.
+// The one exception is final_head (final_head.h), shared with final_kernel (sampler_kernels.hip, a unit built with
+// contraction on): it asks for contraction itself.
 #include "common.h"
 #include "ode_args.h"
+#include "final_head.h"
 
 // out = y + h * sum_i coef[i] * k[i]: the stage / step update of an explicit Runge-Kutta method
 struct OdeCombineArgs {
@@ -47,31 +48,6 @@ extern "C" int codlad_ode_combine(const float *y, const float *const *k_host, co
 // ---------------------------------------------------------------------------------------------
 // The fused path.
 // ---------------------------------------------------------------------------------------------
-DEV float half_wave_allsum(float v) {
-#pragma unroll
-    for (int m = 16; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
-// final_kernel's head for a 3-row model: LayerNorm, modulation, Linear 128 -> 3, for node nc, on the 32 lanes of a half
-// wave.  Keep in step with final_kernel (tests hold the two to each other bit for bit).
-DEV void ode_head(const OdeStageArgs &a, int nc, int l, float (&o)[3]) {
-#pragma clang fp contract(fast)
-    const float4 v = reinterpret_cast<const float4 *>(a.hV + (size_t)nc * HD)[l];
-    const float mean = half_wave_allsum((v.x + v.y) + (v.z + v.w)) * (1.0f / 128.0f);
-    const float d0 = v.x - mean, d1 = v.y - mean, d2 = v.z - mean, d3 = v.w - mean;
-    const float var = half_wave_allsum((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3));
-    const float rstd = 1.0f / sqrtf(var * (1.0f / 128.0f) + 1e-6f);
-    const float4 sh = reinterpret_cast<const float4 *>(a.mods)[l], sc = reinterpret_cast<const float4 *>(a.mods + HD)[l];
-    const float m0 = (d0 * rstd) * (1.0f + sc.x) + sh.x, m1 = (d1 * rstd) * (1.0f + sc.y) + sh.y,
-                m2 = (d2 * rstd) * (1.0f + sc.z) + sh.z, m3 = (d3 * rstd) * (1.0f + sc.w) + sh.w;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float4 w = reinterpret_cast<const float4 *>(a.out_w + k * HD)[l];
-        o[k] = half_wave_allsum(fmaf(m3, w.w, fmaf(m2, w.z, fmaf(m1, w.y, m0 * w.x)))) + a.out_b[k];
-    }
-}
-
 // 32 lanes per node, 8 nodes per 256-thread block, as final_kernel.  Lane c < 3 of a node owns component c: it stores the
 // slope and forms the stage's sum with the slopes of earlier stages, which earlier launches wrote.
 __global__ __launch_bounds__(256) void ode_stage_kernel(OdeStageArgs a) {
@@ -80,19 +56,9 @@ __global__ __launch_bounds__(256) void ode_stage_kernel(OdeStageArgs a) {
     const bool live = n < a.n_nodes;
     const int nc = live ? n : a.n_nodes - 1;           // whole half waves stay converged for the shuffles
     float o[3];
-    ode_head(a, nc, l, o);
+    final_head(a, 3, nc, l, o);
     if (!live) return;
-    if (a.status && l == 0) {
-        // final_kernel's test: inf / NaN by exponent bits, on bits the compiler cannot reason about as floats
-        bool bad = false;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            unsigned u = __float_as_uint(o[k]);
-            asm volatile("" : "+v"(u));
-            bad |= (u & 0x7f800000u) == 0x7f800000u;
-        }
-        if (bad) atomicOr(a.status, CODLAD_STATUS_NONFINITE);
-    }
+    if (a.status && l == 0 && any_nonfinite(o)) atomicOr(a.status, CODLAD_STATUS_NONFINITE);
     if (l < 3) {
         const float mine = l == 0 ? o[0] : (l == 1 ? o[1] : o[2]);
         const size_t i = (size_t)n * 3 + l;

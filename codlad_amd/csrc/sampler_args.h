@@ -1,13 +1,9 @@
 // Arguments of final_kernel (sampler_kernels.hip), filled by the loops of denoiser_forward.hip.
 #pragma once
-#include "edge_args.h"     // HD, host_util.h
+#include "final_head.h"    // HeadArgs; HD, host_util.h
 
 // FinalLayer (latent_model.py:31-35) + ancestral DDPM update (gaussian_diffusion.py:303-367,446).
-struct FinalArgs {
-    const float *hV;
-    const float *mods;  // shift, scale (2 x 128)
-    const float *out_w, *out_b;
-    int n_nodes;
+struct FinalArgs : HeadArgs {
     float *logits;      // [n][6] or null
     float *x;           // in/out [n][3] (update mode)
     const float *noise; // [n][3]

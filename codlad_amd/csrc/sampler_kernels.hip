@@ -1,66 +1,25 @@
 // The sampler's tail of a denoiser step: the final layer fused with the step's update (final_kernel), the stand-alone DDPM /
 // DDIM updates around a caller's guidance functions, the timestep embedding with every adaLN head (mods_kernel) and the status
-// word.  Built with -fno-honor-nans like the other denoiser units: final_kernel's non-finite test says why that matters here.
+// word.  Built with -fno-honor-nans like the other denoiser units: any_nonfinite (final_head.h) says why that matters here.
 #include "sampler_args.h"
-
-// 32 lanes per node (one 16-byte word of the row each: coalesced 512-byte row reads, the reductions are
-// butterflies inside the half wave), 8 nodes per 256-thread block.
-DEV float half_wave_allsum(float v) {
-#pragma unroll
-    for (int m = 16; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
+#include "final_head.h"
 
 // PIN: residue pinning fused into the update (codlad_sample_loop_pinned): at a node with pin_mask[n] != 0 the step's
 // raw pred_xstart is replaced by pin_x0[n] before the clamp.  A template parameter, so that final_kernel<false> (the
-// logits mode and the plain loop) is instruction for instruction the kernel it was before pinning existed; only its
-// argument block grows by the two unused pointers.
-// STEP: the update of the loop, CODLAD_STEP_* (sampler_args.h).  The DDPM instantiations are instruction for instruction
-// what they were before DDIM existed (they do not read `mode`, which follows the other arguments).
+// logits mode and the plain loop) carries none of it; the two pointers are then unused arguments.
+// STEP: the update of the loop, CODLAD_STEP_* (sampler_args.h).  The DDPM instantiations do not read `mode`.
 template <bool PIN, int STEP = CODLAD_STEP_DDPM>
 __global__ __launch_bounds__(256) void final_kernel(FinalArgs a, const float *pin_x0, const uint8_t *pin_mask, int mode) {
     const int l = threadIdx.x & 31;
     const int n = blockIdx.x * 8 + (threadIdx.x >> 5);
     const bool live = n < a.n_nodes;
     const int nc = live ? n : a.n_nodes - 1;           // whole half waves stay converged for the shuffles
-    const float4 v = reinterpret_cast<const float4 *>(a.hV + (size_t)nc * HD)[l];
-    const float mean = half_wave_allsum((v.x + v.y) + (v.z + v.w)) * (1.0f / 128.0f);
-    const float d0 = v.x - mean, d1 = v.y - mean, d2 = v.z - mean, d3 = v.w - mean;
-    const float var = half_wave_allsum((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3));
-    const float rstd = 1.0f / sqrtf(var * (1.0f / 128.0f) + 1e-6f);
-    const float4 sh = reinterpret_cast<const float4 *>(a.mods)[l], sc = reinterpret_cast<const float4 *>(a.mods + HD)[l];
-    const float m0 = (d0 * rstd) * (1.0f + sc.x) + sh.x, m1 = (d1 * rstd) * (1.0f + sc.y) + sh.y,
-                m2 = (d2 * rstd) * (1.0f + sc.z) + sh.z, m3 = (d3 * rstd) * (1.0f + sc.w) + sh.w;
     float o[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        o[k] = 0.f;
-        if (k < a.n_out) {
-            const float4 w = reinterpret_cast<const float4 *>(a.out_w + k * HD)[l];
-            o[k] = half_wave_allsum(fmaf(m3, w.w, fmaf(m2, w.z, fmaf(m1, w.y, m0 * w.x)))) + a.out_b[k];
-        }
-    }
+    final_head(a, a.n_out, nc, l, o);
     if (!live) return;
-    if (a.status && l == 0) {
-        // inf / NaN by exponent bits.  This file is built with -fno-honor-nans: the compiler folds x != x away and
-        // even turns the bit test on a float's bits into |x| == inf (false for NaN), so the bits are laundered
-        // through an empty asm and tested as the integers they then are.
-        bool bad = false;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-            unsigned u = __float_as_uint(o[k]);
-            asm volatile("" : "+v"(u));
-            bad |= (u & 0x7f800000u) == 0x7f800000u;
-        }
-        if (bad) atomicOr(a.status, CODLAD_STATUS_NONFINITE);
-    }
+    if (a.status && l == 0 && any_nonfinite(o)) atomicOr(a.status, CODLAD_STATUS_NONFINITE);
     if (a.logits) {
-        if (l < a.n_out) {
-            float mine = o[0];
-#pragma unroll
-            for (int k = 1; k < 6; ++k) mine = l == k ? o[k] : mine;
-            a.logits[(size_t)n * a.n_out + l] = mine;
-        }
+        store_logits(a.logits, a.n_out, n, l, o);
         return;
     }
     if (l < 3) {                                        // lane k updates component k
