@@ -145,6 +145,8 @@ _SIGS = {
     "codlad_sample_loop_pinned": (C.c_int, _JOB + [P, P, P, P, P, C.c_int, P, P, P]),
     "codlad_ddim_loop": (C.c_int, _JOB + [P, P, P, P, P, C.c_int, C.c_int, C.c_int, P, P, P]),
     "codlad_ddim_step": (C.c_int, [P, P, P, P, P, C.c_int, C.c_int, P, P, P]),
+    "codlad_dpm_loop": (C.c_int, _JOB + [P, P, P, P, C.c_int, C.c_int, P, P, P]),
+    "codlad_dpm_step": (C.c_int, [P, P, P, P, P, C.c_int, P, P, P]),
     "codlad_q_sample": (C.c_int, [P, P, P, C.c_int, P, C.c_int, P, C.c_int, P, P, P, P]),
     "codlad_q_posterior": (C.c_int, [P, P, P, C.c_int, P, C.c_int, P, C.c_int, P, P, P, P]),
     "codlad_vb_terms": (C.c_int, [P, P, P, P, P, C.c_int, P, C.c_int, P, C.c_int, C.POINTER(LossTerms), P]),

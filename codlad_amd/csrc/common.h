@@ -792,6 +792,38 @@ DEV float ddim_step(float xt, float out, const float *cf, int mode, float noise,
     return ddim_update<REVERSE>(xt, x0, cf, mode, noise, x0_out, nullptr);
 }
 
+// One DPM-Solver++(2M) update of a scalar (Lu et al. 2022, data-prediction form, Algorithm 2; order 1 is DDIM at eta 0).
+// cf = one row of Tables.dpm_solver_coefficients(): {sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod, A, B, C,
+// sqrt(1 - acp), -, mode}; `mode` (the clamp bit) is the caller's as for ddim_step, and equals cf[7], which ddpm_raw_x0 reads.
+// dpm_update: the clamp and the optional condition_score exactly as ddim_update, then
+//     x <- (A * x + B * x0) + C * x0_prev,
+// the three products and the two sums rounded one by one, in this order, in the fused and the stand-alone kernel alike.
+// A row whose C is exactly 0 (the first step: no history; the last: x <- x0; every row of order 1) is A * x + B * x0 and
+// does not read *x0_prev, which is uninitialised memory in the first step.  *x0_prev is read before *x0_out is written: in
+// the fused loop both are the x_start entry of the node, which so stays the self-conditioning input of the next step.
+// dpm_step: the raw pred_xstart (ddpm_raw_x0), the pin, then dpm_update - the pieces and the order of ddim_step; the split
+// step (codlad_ddpm_pred_xstart, the caller's denoised_fn, codlad_dpm_step) runs the same expressions around the hook.
+DEV float dpm_update(float xt, float x0, const float *cf, int mode, const float *x0_prev, float *x0_out, const float *grad) {
+#pragma clang fp contract(off)
+    if (mode & CODLAD_DDPM_CLIP) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    if (grad) {
+        float e = (cf[0] * xt - x0) / cf[1];
+        e = e - cf[5] * *grad;
+        x0 = cf[0] * xt - cf[1] * e;
+    }
+    const bool history = cf[4] != 0.f;
+    const float prev = history ? *x0_prev : 0.f;
+    if (x0_out) *x0_out = x0;
+    const float first = cf[2] * xt + cf[3] * x0;
+    return history ? first + cf[4] * prev : first;
+}
+
+DEV float dpm_step(float xt, float out, const float *cf, int mode, float *x0_io, const float *pin = nullptr) {
+    float x0 = ddpm_raw_x0(xt, out, cf);
+    if (pin) x0 = *pin;
+    return dpm_update(xt, x0, cf, mode, x0_io, x0_io, nullptr);
+}
+
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------

@@ -278,9 +278,10 @@ extern "C" int codlad_denoiser_forward(const codlad_denoiser_weights *w, const c
     return codlad_check_launch("codlad_denoiser_forward");
 }
 
-// the loop of codlad_sample_loop / codlad_sample_loop_pinned / codlad_ddim_loop (pin_x0 == NULL: no pinning).
-// step: CODLAD_STEP_* of final_kernel; `mode` is read by the DDIM steps only.  The forward loops run i = T-1 .. 0 and
-// consume noise entry k at step k; the reverse DDIM loop runs i = 0 .. T-1 and reads no noise.
+// the loop of codlad_sample_loop / codlad_sample_loop_pinned / codlad_ddim_loop / codlad_dpm_loop (pin_x0 == NULL: no
+// pinning).  step: CODLAD_STEP_* of final_kernel; `mode` is read by the DDIM and DPM steps only.  The forward loops run
+// i = T-1 .. 0 and consume noise entry k at step k (the DPM loop has no noise: null); the reverse DDIM loop runs
+// i = 0 .. T-1 and reads no noise.
 static void sample_loop(const codlad_denoiser_weights *w, const codlad_job *job, float *x, float *x_start,
                         const float *noise, const float *mods, const float *coef, int T, const float *pin_x0,
                         const uint8_t *pin_mask, void *stream, int step = CODLAD_STEP_DDPM, int mode = 0) {
@@ -294,7 +295,7 @@ static void sample_loop(const codlad_denoiser_weights *w, const codlad_job *job,
         const float *mods_t = mods + (size_t)i * CODLAD_MODS_PER_STEP;
         enqueue_forward(w, job, x, sc && k > 0 ? x_start : nullptr, mods_t, st);
         FinalArgs fa = final_args(w, job, mods_t);
-        fa.x = x; fa.noise = reverse ? nullptr : noise + (size_t)k * job->n_nodes * 3;
+        fa.x = x; fa.noise = noise ? noise + (size_t)k * job->n_nodes * 3 : nullptr;
         fa.coef = coef + (size_t)i * 8; fa.x_start = x_start;
         launch_final(fa, step, pin_x0, pin_mask, mode, st);
     }
@@ -344,6 +345,23 @@ extern "C" int codlad_ddim_loop(const codlad_denoiser_weights *w, const codlad_j
     sample_loop(w, job, x, x_start, noise, mods, coef, T, pin_x0, pin_mask, stream,
                 reverse ? CODLAD_STEP_DDIM_REVERSE : CODLAD_STEP_DDIM, mode);
     return codlad_check_launch("codlad_ddim_loop");
+}
+
+extern "C" int codlad_dpm_loop(const codlad_denoiser_weights *w, const codlad_job *job, float *x, float *x_start,
+                               const float *mods, const float *coef, int T, int mode, const float *pin_x0,
+                               const uint8_t *pin_mask, void *stream) {
+    CODLAD_REQUIRE(w && x && mods && coef, "null pointer");
+    CODLAD_REQUIRE(x_start, "null pointer (x_start: the multistep update reads the previous step's pred_xstart from it)");
+    CODLAD_REQUIRE(!pin_x0 == !pin_mask, "null pointer (pin_x0 and pin_mask come together)");
+    CODLAD_REQUIRE(T > 0, "T must be positive");
+    CODLAD_REQUIRE(mode >= 0 && mode <= (CODLAD_DDPM_START_X | CODLAD_DDPM_FIXED_VAR | CODLAD_DDPM_CLIP),
+                   "unknown mode bits");
+    CODLAD_REQUIRE(w->out_dim == ((mode & CODLAD_DDPM_FIXED_VAR) ? 3 : 6),
+                   "mode and model disagree: a learned-range sampler needs a model with 6 outputs (mean | variance "
+                   "logits), a fixed-variance one (mode bit 2) a model with 3");
+    REQUIRE_OK(job_defect(w, job));     // after the sampler's own, as in codlad_ddim_loop
+    sample_loop(w, job, x, x_start, nullptr, mods, coef, T, pin_x0, pin_mask, stream, CODLAD_STEP_DPM, mode);
+    return codlad_check_launch("codlad_dpm_loop");
 }
 
 // Loss evaluation around a forward (loss_kernels.hip): loss_kernel takes final_kernel's place after enqueue_forward.

@@ -1,5 +1,5 @@
 // The sampler's tail of a denoiser step: the final layer fused with the step's update (final_kernel), the stand-alone DDPM /
-// DDIM updates around a caller's guidance functions, the timestep embedding with every adaLN head (mods_kernel) and the status
+// DDIM / DPM-Solver++ updates around a caller's guidance functions, the timestep embedding with every adaLN head (mods_kernel) and the status
 // word.  Built with -fno-honor-nans like the other denoiser units: any_nonfinite (final_head.h) says why that matters here.
 #include "sampler_args.h"
 #include "final_head.h"
@@ -31,17 +31,20 @@ __global__ __launch_bounds__(256) void final_kernel(FinalArgs a, const float *pi
             a.x[i] = ddpm_step(a.x[i], eps, vv, a.coef, a.noise[i], a.x_start ? a.x_start + i : nullptr, pin);
         else if constexpr (STEP == CODLAD_STEP_DDIM)
             a.x[i] = ddim_step<false>(a.x[i], eps, a.coef, mode, a.noise[i], a.x_start ? a.x_start + i : nullptr, pin);
-        else
+        else if constexpr (STEP == CODLAD_STEP_DDIM_REVERSE)
             a.x[i] = ddim_step<true>(a.x[i], eps, a.coef, mode, 0.f, a.x_start ? a.x_start + i : nullptr, pin);
+        else
+            a.x[i] = dpm_step(a.x[i], eps, a.coef, mode, a.x_start + i, pin);
     }
 }
 
 void launch_final(const FinalArgs &fa, int step, const float *pin_x0, const uint8_t *pin_mask, int mode, hipStream_t st) {
-    static void (*const kernels[3][2])(FinalArgs, const float *, const uint8_t *, int) = {    // [CODLAD_STEP_*][pinned]
+    static void (*const kernels[4][2])(FinalArgs, const float *, const uint8_t *, int) = {    // [CODLAD_STEP_*][pinned]
         {final_kernel<false, CODLAD_STEP_DDPM>, final_kernel<true, CODLAD_STEP_DDPM>},
         {final_kernel<false, CODLAD_STEP_DDIM>, final_kernel<true, CODLAD_STEP_DDIM>},
-        {final_kernel<false, CODLAD_STEP_DDIM_REVERSE>, final_kernel<true, CODLAD_STEP_DDIM_REVERSE>}};
-    if (step < CODLAD_STEP_DDPM || step > CODLAD_STEP_DDIM_REVERSE) __builtin_trap();    // not a CODLAD_STEP_*: a caller's bug
+        {final_kernel<false, CODLAD_STEP_DDIM_REVERSE>, final_kernel<true, CODLAD_STEP_DDIM_REVERSE>},
+        {final_kernel<false, CODLAD_STEP_DPM>, final_kernel<true, CODLAD_STEP_DPM>}};
+    if (step < CODLAD_STEP_DDPM || step > CODLAD_STEP_DPM) __builtin_trap();    // not a CODLAD_STEP_*: a caller's bug
     hipLaunchKernelGGL(kernels[step][pin_x0 != nullptr], dim3((fa.n_nodes + 7) / 8), dim3(256), 0, st, fa, pin_x0, pin_mask, mode);
 }
 
@@ -100,6 +103,16 @@ __global__ void ddim_update_kernel(const float *x, const float *x0, const float 
     if (i >= n_nodes * 3) return;
     x_out[i] = ddim_update<REVERSE>(x[i], x0[i], cf.c, mode, REVERSE ? 0.f : noise[i], x_start ? x_start + i : nullptr,
                                     grad ? grad + i : nullptr);
+}
+
+// The DPM-Solver++(2M) update after a caller's denoised_fn / cond_fn (codlad_dpm_step): dpm_update on the processed
+// pred_xstart, as ddim_update_kernel is ddim_update.  x0_prev is null for a row whose C is 0, which does not read it.
+__global__ void dpm_update_kernel(const float *x, const float *x0, const float *x0_prev, const float *grad, DdpmCoef cf,
+                                  int mode, int n_nodes, float *x_out, float *x_start) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_nodes * 3) return;
+    x_out[i] = dpm_update(x[i], x0[i], cf.c, mode, x0_prev ? x0_prev + i : nullptr, x_start ? x_start + i : nullptr,
+                          grad ? grad + i : nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -205,6 +218,19 @@ extern "C" int codlad_ddim_step(const float *x, const float *pred_xstart, const 
     hipLaunchKernelGGL(reverse ? ddim_update_kernel<true> : ddim_update_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream,
                        x, pred_xstart, reverse ? nullptr : noise, grad, ddpm_coef(coef_host), mode, n_nodes, x_out, x_start_out);
     return codlad_check_launch("codlad_ddim_step");
+}
+
+extern "C" int codlad_dpm_step(const float *x, const float *pred_xstart, const float *prev_xstart, const float *grad,
+                               const float *coef_host, int n_nodes, float *x_out, float *x_start_out, void *stream) {
+    CODLAD_REQUIRE(x && pred_xstart && coef_host && x_out, "null pointer");
+    CODLAD_REQUIRE(n_nodes > 0, "n_nodes must be positive");
+    CODLAD_REQUIRE((coef_host[4] != 0.f) == (prev_xstart != nullptr),
+                   "prev_xstart is given exactly when the row's C (column 4) is not 0: a second-order row needs the previous "
+                   "step's pred_xstart, a first-order row reads none");
+    const int mode = (int)coef_host[7];
+    hipLaunchKernelGGL(dpm_update_kernel, dim3((n_nodes * 3 + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, pred_xstart,
+                       prev_xstart, grad, ddpm_coef(coef_host), mode, n_nodes, x_out, x_start_out);
+    return codlad_check_launch("codlad_dpm_step");
 }
 
 extern "C" int codlad_status_check(int32_t *status, void *stream) {

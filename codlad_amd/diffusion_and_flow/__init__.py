@@ -12,7 +12,10 @@ other callable runs between the two halves of the split step (`codlad_ddpm_pred_
 `codlad_ddpm_posterior_step`).  DDIM (the IDDPM release's `ddim_sample`, `ddim_reverse_sample`, `ddim_sample_loop`,
 `ddim_sample_loop_progressive`, with `eta`; `ddim_reverse_sample_loop` returns x_T) follows the same rule: the loop is
 one `codlad_ddim_loop` call for the HIP model with no hook or only a `PinLatents`, any other case steps through the
-model and `codlad_ddpm_pred_xstart` / `codlad_ddim_step`.  The forward process and the losses (`q_mean_variance`,
+model and `codlad_ddpm_pred_xstart` / `codlad_ddim_step`.  DPM-Solver++(2M) (`dpm_solver_sample_loop`,
+`dpm_solver_sample_loop_progressive`, `order` 1 or 2; Lu et al. 2022 - not in the reference) follows it too:
+`codlad_dpm_loop`, or the model and `codlad_ddpm_pred_xstart` / `codlad_dpm_step` per step; the respacing spec "logsnrN"
+(steps uniform in log-SNR) is the spacing it is meant for.  The forward process and the losses (`q_mean_variance`,
 `q_sample`, `q_posterior_mean_variance`, `_vb_terms_bpd`, `training_losses`, and the IDDPM release's `calc_bpd_loop`) are
 evaluated forward-only: the HIP model runs `codlad_loss_forward` per group of equal timesteps and `codlad_bpd_loop` for the
 whole bound, any other CUDA callable is followed by `codlad_vb_terms`.  Gradients and training are out of scope; forward-only
@@ -23,7 +26,7 @@ import random
 
 import torch
 
-from .schedule import Tables, named_betas, space_timesteps
+from .schedule import Tables, logsnr_timesteps, named_betas, space_timesteps
 
 
 class ModelMeanType(enum.Enum):
@@ -586,6 +589,105 @@ class SpacedDiffusion(_LossEvaluation, Tables):
             x_start = out["pred_xstart"]
 
 
+    # -- DPM-Solver++(2M) ----------------------------------------------------------------------
+    def dpm_solver_coefs(self, clip_denoised, order=2):
+        """The [T, 8] DPM-Solver++ table of the kernels for this sampler's branches (Tables.dpm_solver_coefficients)."""
+        self._check_order(order)
+        key = (bool(clip_denoised), int(order))
+        cache = self.__dict__.setdefault("_dpm_tables", {})
+        if key not in cache:
+            var = {ModelVarType.FIXED_SMALL: "fixed_small",
+                   ModelVarType.FIXED_LARGE: "fixed_large"}.get(self.model_var_type, "learned_range")
+            cache[key] = self.dpm_solver_coefficients(order=int(order),
+                                                      predict_xstart=self.model_mean_type is ModelMeanType.START_X,
+                                                      var_type=var, clip_denoised=bool(clip_denoised))
+        return cache[key]
+
+    @staticmethod
+    def _check_order(order):
+        if isinstance(order, bool) or not isinstance(order, int):
+            raise TypeError(f"order must be an int, got {type(order).__name__}")
+        if order not in (1, 2):
+            raise ValueError(f"DPM-Solver++ order must be 1 or 2, got {order}")
+
+    def dpm_solver_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
+                               model_kwargs=None, device=None, progress=False, order=2):
+        """Returns x_0 with `shape`, sampled by DPM-Solver++(2M) (order=1: DDIM at eta 0): deterministic given `noise`
+        (x_T), one model evaluation per step.  Meant for 10-25 steps on the "logsnrN" respacing.  The HIP model with no
+        hook or only a PinLatents runs fused (codlad_dpm_loop); anything else step by step."""
+        self._check_args(clip_denoised, denoised_fn, cond_fn)
+        self._check_order(order)
+        model_kwargs = model_kwargs or {}
+        mod = self._hip_module(model)
+        if not self._ddim_fusable(mod, denoised_fn, cond_fn):
+            final = None
+            for final in self.dpm_solver_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
+                                                                 denoised_fn=denoised_fn, cond_fn=cond_fn,
+                                                                 model_kwargs=model_kwargs, device=device, order=order):
+                pass
+            return final["sample"]
+        if device is None:
+            device = next(mod.parameters()).device
+        img = noise if noise is not None else torch.randn(*shape, device=device)
+        if not img.is_cuda:
+            raise RuntimeError("dpm_solver_sample_loop (codlad_amd) runs on the MI355X only")
+        job, pin = self._fused_job(mod, img, model_kwargs, denoised_fn)
+        x0 = mod.engine().sample(job, img.reshape(-1, img.shape[-1]), None, self,
+                                 coef=self.dpm_solver_coefs(clip_denoised, order), pin=pin, kind="dpmpp")
+        return x0.view(img.shape)
+
+    def dpm_solver_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
+                                           cond_fn=None, model_kwargs=None, device=None, progress=False, order=2):
+        """Generic DPM-Solver++ stepping for any CUDA model callable; yields each step's {"sample", "pred_xstart"}: the
+        model, the raw pred_xstart (codlad_ddpm_pred_xstart), denoised_fn, cond_fn's gradient, then codlad_dpm_step with
+        the previous step's pred_xstart."""
+        self._check_args(clip_denoised, denoised_fn, cond_fn)
+        self._check_order(order)
+        import numpy as np
+        from ..engine import Denoiser
+        model_kwargs = model_kwargs or {}
+        img = noise if noise is not None else torch.randn(*shape, device=device)
+        if not img.is_cuda:
+            raise RuntimeError("dpm_solver_sample_loop (codlad_amd) runs on the MI355X only")
+        table = self.dpm_solver_coefs(clip_denoised, order)
+        x_start = None
+        for i in range(self.num_timesteps - 1, -1, -1):
+            t = torch.tensor([i] * shape[0], device=img.device)
+            map_t = torch.tensor(self.timestep_map, device=t.device, dtype=t.dtype)[t]   # respace.py:124-129
+            kwargs = dict(model_kwargs)
+            if self.self_condition and x_start is not None:
+                kwargs["x_self_cond"] = x_start
+            model_out = model(img, map_t, **kwargs)
+            C = img.shape[-1]
+            assert C == 3 and model_out.shape[-1] == (C if self.fixed_variance else 2 * C), \
+                "latent_size 3 only; a fixed-variance sampler takes a model without variance channels " \
+                "(gaussian_diffusion.py:303-306, 321-334)"
+            coef = np.ascontiguousarray(table[i])
+            pred = Denoiser.ddpm_pred_xstart(img, model_out, coef).view(img.shape)
+            if denoised_fn is not None:
+                pred = denoised_fn(pred)
+                _check_hook_output(pred, img, "denoised_fn")
+            grad = None
+            if cond_fn is not None:
+                grad = cond_fn(img, map_t, **model_kwargs)
+                _check_hook_output(grad, img, "cond_fn")
+            sample, used = Denoiser.dpm_step(img, pred, x_start if coef[4] != 0 else None, coef, grad=grad)
+            img, x_start = sample.view(img.shape), used.view(img.shape)
+            yield {"sample": img, "pred_xstart": x_start}
+
+
+def _use_timesteps(diffusion_steps, timestep_respacing, betas):
+    """The base steps a respacing spec keeps: "logsnrN" is N steps uniform in log-SNR on this schedule
+    (schedule.logsnr_timesteps), every other spec is the reference's (space_timesteps)."""
+    if isinstance(timestep_respacing, str) and timestep_respacing.startswith("logsnr"):
+        try:
+            n = int(timestep_respacing[len("logsnr"):])
+        except ValueError:
+            raise ValueError(f"respacing spec {timestep_respacing!r}: logsnr takes a step count, as in \"logsnr20\"") from None
+        return logsnr_timesteps(betas, n)
+    return space_timesteps(diffusion_steps, timestep_respacing)
+
+
 def create_diffusion(timestep_respacing, noise_schedule="linear", use_kl=False, rescale_learned_sigmas=False,
                      sigma_small=False, predict_xstart=False, learn_sigma=True, diffusion_steps=1000,
                      self_condition=False):
@@ -597,7 +699,7 @@ def create_diffusion(timestep_respacing, noise_schedule="linear", use_kl=False, 
                                                                else ModelVarType.FIXED_LARGE)
     # reference diffusion_and_flow/__init__.py:44-50
     loss_type = LossType.RESCALED_KL if use_kl else (LossType.RESCALED_MSE if rescale_learned_sigmas else LossType.MSE)
-    return SpacedDiffusion(use_timesteps=space_timesteps(diffusion_steps, timestep_respacing),
-                           betas=named_betas(noise_schedule, diffusion_steps),
+    betas = named_betas(noise_schedule, diffusion_steps)
+    return SpacedDiffusion(use_timesteps=_use_timesteps(diffusion_steps, timestep_respacing, betas), betas=betas,
                            model_mean_type=mean_type, model_var_type=var_type,
                            loss_type=loss_type, self_condition=self_condition)

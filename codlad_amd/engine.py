@@ -301,7 +301,7 @@ class Denoiser:
     # 8 700 +9.6 % (each half then takes the small-job node kernel), 5 220 -1.9 %, 3 480 +5.5 %, 1 740 -8 %.
     SPLIT_MIN_NODES = int(os.environ.get("CODLAD_SAMPLE_SPLIT_MIN_NODES", 8192))
 
-    SAMPLE_KINDS = ("ddpm", "ddim", "ddim_reverse")
+    SAMPLE_KINDS = ("ddpm", "ddim", "ddim_reverse", "dpmpp")
 
     def sample(self, job, x_T, noise, tables, check=True, coef=None, streams=None, pin=None, kind="ddpm"):
         """Full ancestral loop.  x_T [n_nodes,3]; noise [T,n_nodes,3] in loop order (first entry
@@ -313,15 +313,19 @@ class Denoiser:
         pin: (x0 [n_nodes,3], mask [n_nodes] bool / uint8 / int32) - residue pinning: at every step the pred_xstart of a
         masked node is replaced by its x0 before the clamp (codlad_sample_loop_pinned).
         kind: "ddpm" (the ancestral loop above), "ddim" (the DDIM loop, codlad_ddim_loop; coef = a Tables.ddim_coefficients
-        table, default eta = 0) or "ddim_reverse" (DDIM inversion: x_T holds x_0, the result is x_T; noise must be None)."""
+        table, default eta = 0), "ddim_reverse" (DDIM inversion: x_T holds x_0, the result is x_T; noise must be None) or
+        "dpmpp" (DPM-Solver++(2M), codlad_dpm_loop; coef = a Tables.dpm_solver_coefficients table, default order 2;
+        deterministic: noise must be None)."""
         if kind not in self.SAMPLE_KINDS:
             raise ValueError(f"kind must be one of {self.SAMPLE_KINDS}, got {kind!r}")
         reverse = kind == "ddim_reverse"
+        noiseless = reverse or kind == "dpmpp"
         T = tables.num_timesteps
         _require_cuda(x_T, "x_T")
-        if reverse:
+        if noiseless:
             if noise is not None:
-                raise ValueError("the reverse DDIM loop is deterministic: noise must be None")
+                raise ValueError(("the reverse DDIM loop" if reverse else "the DPM-Solver++ loop") +
+                                 " is deterministic: noise must be None")
         else:
             _require_cuda(noise, "noise")
             assert noise.shape == (T, job.n_nodes, 3)
@@ -332,7 +336,7 @@ class Denoiser:
         if streams > 1:
             parts = job.parts(streams)
             pins = None if pin is None else [(pin[0][i], pin[1][i]) for _p, i in parts]
-            noises = [None if reverse else noise[:, i] for _p, i in parts]
+            noises = [None if noiseless else noise[:, i] for _p, i in parts]
             outs = self.sample_many([p for p, _i in parts], [x_T[i] for _p, i in parts], noises,
                                     tables, check=check, coef=coef, pins=pins, kind=kind)
             x0 = torch.empty(job.n_nodes, 3, dtype=torch.float32, device=self.device)
@@ -340,22 +344,26 @@ class Denoiser:
                 x0[i] = o
             return x0
         if coef is None:
-            coef = tables.step_coefficients() if kind == "ddpm" else tables.ddim_coefficients(reverse=reverse)
+            coef = (tables.step_coefficients() if kind == "ddpm" else tables.dpm_solver_coefficients() if kind == "dpmpp"
+                    else tables.ddim_coefficients(reverse=reverse))
         fixed_var = bool(int(coef[0, 7]) & 2)
         if self.weights.out_dim != (3 if fixed_var else 6):
             raise ValueError(f"the {kind.upper()} loop needs a model with 6 outputs (mean | variance logits), or 3 with a "
                              "fixed-variance sampler (create_diffusion(learn_sigma=False)); a flow-matching model is sampled "
                              "with codlad_amd.diffusion_and_flow.ode.odeint")
         x = x_T.detach().clone().contiguous().float()
-        noise = None if reverse else noise.contiguous().float()
+        noise = None if noiseless else noise.contiguous().float()
         mods = self.step_mods(tables.timestep_map)
         mode = int(coef[0, 7])                                  # the host's mode word (codlad_ddim_loop checks it)
         coef = torch.from_numpy(coef).to(self.device)
         self._fresh_features(job.structures)
-        x_start = torch.empty_like(x) if self.self_condition else None   # pred_xstart, step to step
+        # pred_xstart, step to step: the self-conditioning input, and the history of the multistep solver
+        x_start = torch.empty_like(x) if self.self_condition or kind == "dpmpp" else None
         loop = [_lib.ptr(t) for t in (x, x_start, noise, mods, coef)] + [T]
         pin_ptrs = [_lib.ptr(t) for t in (pin or (None, None))]
-        if kind != "ddpm":
+        if kind == "dpmpp":
+            self._run("codlad_dpm_loop", job.desc(), *(_lib.ptr(t) for t in (x, x_start, mods, coef)), T, mode, *pin_ptrs)
+        elif kind != "ddpm":
             self._run("codlad_ddim_loop", job.desc(), *loop, mode, int(reverse), *pin_ptrs)
         elif pin is None:
             self._run("codlad_sample_loop", job.desc(), *loop)
@@ -371,7 +379,7 @@ class Denoiser:
         half-jobs of BASELINE configuration 2: 1.03 x; more than two parts lose).  Every job carries its
         own workspace and the library keeps no state between jobs, so the results are those of `sample` job by job.
         pins: None, or one `pin` of `sample` (or None) per job.  kind as for `sample` (noises: None per job for
-        "ddim_reverse")."""
+        "ddim_reverse" and "dpmpp")."""
         pins = [None] * len(jobs) if pins is None else list(pins)
         assert len(pins) == len(jobs)
         for job in jobs:                                  # features and the step tables once, on the caller's stream
@@ -854,6 +862,28 @@ class Denoiser:
                                          _lib.ptr(g), coef.ctypes.data_as(C.c_void_p), int(bool(reverse)),
                                          x.numel() // 3, _lib.ptr(out), _lib.ptr(x_start), _lib.stream_ptr(x.device))
         _lib.check(rc, "codlad_ddim_step")
+        return out, x_start
+
+    @staticmethod
+    def dpm_step(x, pred_xstart, prev_xstart, coef, grad=None):
+        """One DPM-Solver++(2M) update given this step's (processed) pred_xstart and the previous step's: clamp (mode
+        bit 4), condition_score with grad (cond_fn), then x <- (A x + B pred_xstart) + C prev_xstart -> (sample, the
+        pred_xstart the step used) (codlad_dpm_step).  coef = one [8] row of Tables.dpm_solver_coefficients; prev_xstart
+        is None exactly when its C (column 4) is 0: the first and the last step, and every step of order 1."""
+        _require_cuda(x, "x")
+        x = x.contiguous().float()
+        out = torch.empty_like(x)
+        x_start = torch.empty_like(x)
+        coef = np.ascontiguousarray(coef, dtype=np.float32)
+        g = None if grad is None else grad.contiguous().float()
+        prev = None if prev_xstart is None else prev_xstart.contiguous().float()
+        _check_step_operands(x, None, coef, pred_xstart=pred_xstart, prev_xstart=prev, grad=g)
+        if (coef[4] != 0) != (prev is not None):
+            raise ValueError("prev_xstart is given exactly when the row's C (column 4) is not 0")
+        rc = _lib.lib().codlad_dpm_step(_lib.ptr(x), _lib.ptr(pred_xstart.contiguous().float()), _lib.ptr(prev), _lib.ptr(g),
+                                        coef.ctypes.data_as(C.c_void_p), x.numel() // 3, _lib.ptr(out), _lib.ptr(x_start),
+                                        _lib.stream_ptr(x.device))
+        _lib.check(rc, "codlad_dpm_step")
         return out, x_start
 
 

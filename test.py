@@ -15,6 +15,9 @@ them) or `--synthetic` (no PED/PDB/Atlas files ship with the reference).
 Addition: `--fix_residues SPEC` keeps the VQ-VAE encoder's latents of the chosen residues (residue pinning, a
 `PinLatents` denoised_fn) and samples the rest of each structure conditioned on them.
 Addition: `--sampler ddim [--eta E]` samples the latents with DDIM (ddim_sample_loop) instead of the ancestral DDPM loop.
+Addition: `--sampler dpmpp` samples them with DPM-Solver++(2M) (dpm_solver_sample_loop: deterministic, multistep, meant for
+10-25 steps); `--timestep_spacing logsnr` spaces the --num_sampling_steps steps uniformly in log-SNR (the spec "logsnrN";
+steps that fall on the same base step merge, the run prints how many are kept) instead of uniformly in t.
 Flow matching (`--model fm ...`): the ODE sampler runs fused on the device; `--compute_nfe` prints the model evaluations of
 every batch; addition: `--ode_stepwise` integrates with one model call per stage from the host instead (same numbers).
 Addition: `--experiment bpd` scores the checkpoint instead of sampling from it: the variational bound in bits per dimension
@@ -110,22 +113,37 @@ def check_fix_residues(args):
 
 
 def check_sampler(args):
-    """--sampler / --eta: DDIM applies to latent sampling with the diffusion model; a nonzero eta is a DDIM setting."""
+    """--sampler / --eta / --timestep_spacing: DDIM and DPM-Solver++ apply to latent sampling with the diffusion model; a
+    nonzero eta is a DDIM setting; the log-SNR spacing is a respacing of the diffusion model's steps."""
     sampler, eta = getattr(args, "sampler", "ddpm"), getattr(args, "eta", 0.0)
-    if sampler not in ("ddpm", "ddim"):
-        raise SystemExit(f"--sampler must be ddpm or ddim, not {sampler!r}")
+    spacing = getattr(args, "timestep_spacing", "uniform")
+    if sampler not in ("ddpm", "ddim", "dpmpp"):
+        raise SystemExit(f"--sampler must be ddpm or ddim (or dpmpp), not {sampler!r}")
     if eta < 0:
         raise SystemExit(f"--eta must be >= 0, got {eta}")
+    if spacing not in ("uniform", "logsnr"):
+        raise SystemExit(f"--timestep_spacing must be uniform or logsnr, not {spacing!r}")
+    if spacing == "logsnr":
+        if args.model != "diffusion":
+            raise SystemExit(f"--timestep_spacing logsnr needs --model diffusion: {args.model!r} is a flow-matching model, "
+                             "whose ODE solver chooses its own steps")
+        if getattr(args, "num_sampling_steps", 2) < 2:
+            raise SystemExit("--timestep_spacing logsnr needs --num_sampling_steps >= 2 (the first and the last base step)")
+    if sampler != "ddim" and eta != 0:
+        raise SystemExit("--eta applies to --sampler ddim only (the DDPM sampler and DPM-Solver++ have no eta)")
     if sampler == "ddpm":
-        if eta != 0:
-            raise SystemExit("--eta applies to --sampler ddim only (the DDPM sampler has no eta)")
         return
     if args.experiment != "latent":
-        raise SystemExit(f"--sampler ddim samples latents: it needs --experiment latent, not {args.experiment!r} "
+        raise SystemExit(f"--sampler {sampler} samples latents: it needs --experiment latent, not {args.experiment!r} "
                          "(recon encodes the input, genzprot samples the conditional prior)")
     if args.model != "diffusion":
-        raise SystemExit(f"--sampler ddim needs --model diffusion: {args.model!r} is a flow-matching model, sampled by "
+        raise SystemExit(f"--sampler {sampler} needs --model diffusion: {args.model!r} is a flow-matching model, sampled by "
                          "its ODE solver")
+
+
+def respacing_spec(args):
+    """The create_diffusion respacing spec of --num_sampling_steps under --timestep_spacing."""
+    return ("logsnr" if getattr(args, "timestep_spacing", "uniform") == "logsnr" else "") + str(args.num_sampling_steps)
 
 
 def check_bpd(args, world):
@@ -347,11 +365,14 @@ def main(args):
         cvae = load_cvae(args, device, load=rank == 0)
     if args.experiment in ("latent", "bpd"):
         model = load_denoiser(args, device, load=rank == 0)
-        diffusion = None if args.model != "diffusion" else create_diffusion(str(args.num_sampling_steps), noise_schedule=args.noise_schedule,
+        diffusion = None if args.model != "diffusion" else create_diffusion(respacing_spec(args), noise_schedule=args.noise_schedule,
                                      predict_xstart=args.predict_xstart,
                                      rescale_learned_sigmas=args.rescale_learned_sigmas,
                                      # reference test.py:297-303
                                      self_condition=hasattr(model, "self_condition") and args.self_condition)
+        if diffusion is not None and getattr(args, "timestep_spacing", "uniform") == "logsnr" and rank == 0:
+            print(f"--timestep_spacing logsnr: {diffusion.num_timesteps} of {args.num_sampling_steps} requested steps kept "
+                  "(steps on the same base step merge)", flush=True)
     elif args.experiment not in ("recon", "genzprot"):
         raise NotImplementedError(f"experiment {args.experiment!r}: latent, recon, genzprot and bpd are built")
     if world > 1:
@@ -410,7 +431,11 @@ def main(args):
                     known = get_norm_feature(vae.get_latent_wovq(batch)[0], args.vae_type, norm_channel=args.norm,
                                              norm_single=args.norm_single, norm_in=True, dataname=args.data_type)
                     pin = PinLatents(known.repeat(E, 1, 1).contiguous(), fix_residue_mask(fixed, L, B * E, device))
-                if args.sampler == "ddim":
+                if args.sampler == "dpmpp":
+                    samples = diffusion.dpm_solver_sample_loop(model.forward, z.shape, z, clip_denoised=False,
+                                                               denoised_fn=pin, device=device,
+                                                               model_kwargs=dict(y=None, mask=mask, batch=rep))
+                elif args.sampler == "ddim":
                     samples = diffusion.ddim_sample_loop(model.forward, z.shape, z, clip_denoised=False, denoised_fn=pin,
                                                          model_kwargs=dict(y=None, mask=mask, batch=rep), device=device,
                                                          eta=args.eta, step_noise=diffusion._draw_noise(z, generator=gen))
@@ -431,6 +456,10 @@ def main(args):
             # --experiment genzprot (reference test.py:495-498, 559): a sample of the conditional prior per member
             samples = torch.cat([cvae.get_latent_cg(batch, generator=gen)[0] for _ in range(E)], 0)
         decoder_model = cvae if args.experiment == "genzprot" else vae
+        if getattr(args, "save_codes", False) and getattr(decoder_model, "quantize", None) is not None:
+            # the VQ code of every residue of every member, [B * E, L]: what the decoder is handed (latent_decode quantizes)
+            codes = decoder_model.quantize(samples, mask=mask)[1]
+            np.save(os.path.join(save_dir, f"{name}_codes.npy"), codes.reshape(B * E, L).cpu().numpy())
         nres = L + 2
         og = batch["OG_CG_nxyz"].reshape(-1, nres, 4)
         xyz_all = []
@@ -515,6 +544,7 @@ if __name__ == "__main__":
     p.add_argument("--ode_stepwise", action="store_true",
                    help="ODE sampling: one model call per stage from the host instead of the fused loop (same numbers)")
     p.add_argument("--save_pdb", action="store_true", help="also write the generated ensemble as a multi-model PDB and an .xtc trajectory")
+    p.add_argument("--save_codes", action="store_true", help="also save the VQ code index of every residue, [structures, L] (VQ-VAE decoders)")
     p.add_argument("--pdb_files", nargs="*", default=None,
                    help="multi-model PDB ensembles to build the test set from (the reference's load_dataset, without mdtraj)")
     p.add_argument("--atom_cutoff", type=float, default=9.0)
@@ -524,9 +554,13 @@ if __name__ == "__main__":
                    help="keep the latents of these residues (1-based CG positions, flanking caps excluded, e.g. 3-20,41) "
                         "as the VQ-VAE encodes them from the input's atoms and sample the rest conditioned on them "
                         "(--experiment latent --model diffusion, VQ-VAE N6 / K3 / K4)")
-    p.add_argument("--sampler", default="ddpm", choices=["ddpm", "ddim"],
-                   help="latent sampler of --model diffusion: the ancestral DDPM loop (default) or DDIM over the same "
-                        "--num_sampling_steps respacing")
+    p.add_argument("--sampler", default="ddpm", choices=["ddpm", "ddim", "dpmpp"],
+                   help="latent sampler of --model diffusion: the ancestral DDPM loop (default), DDIM or DPM-Solver++(2M) "
+                        "(deterministic, multistep; use it with --timestep_spacing logsnr) over the same --num_sampling_steps "
+                        "respacing")
+    p.add_argument("--timestep_spacing", default="uniform", choices=["uniform", "logsnr"],
+                   help="how --num_sampling_steps steps are placed among the base steps: uniformly in t (default, the "
+                        "reference's respacing) or uniformly in log-SNR (steps on the same base step merge); --model diffusion only")
     p.add_argument("--eta", type=float, default=0.0,
                    help="DDIM noise scale (0 = the deterministic sampler, 1 = the DDPM posterior variance); --sampler ddim only")
     main(p.parse_args())
