@@ -99,6 +99,11 @@ class LossTerms(C.Structure):
     _fields_ = [(n, P) for n in ("kl", "nll", "vb", "mse", "xstart_mse", "eps_mse", "pred_xstart")]
 
 
+class FmLossOut(C.Structure):
+    """codlad_fm_loss_out: the per-sample means of the flow-matching loss kernel, each may be NULL."""
+    _fields_ = [(n, P) for n in ("l2", "l1", "huber", "smooth_l1", "log_cosh")]
+
+
 class OdeState(C.Structure):
     """codlad_ode_state: the adaptive ODE method's device state block (read back after every attempt)."""
     _fields_ = [(n, C.c_double) for n in ("t", "h", "t_end", "ratio", "hh")] + \
@@ -111,6 +116,8 @@ class OdeDopri5Bufs(C.Structure):
     _fields_ = [("y", P), ("y1", P), ("xin", P), ("k", P * 7), ("mods", P), ("state", P), ("norm", P)]
 
 
+FM_KINDS = {"icfm": 0, "target": 1, "vp": 2}           # CODLAD_FM_* of include/codlad_hip.h
+FM_TARGET_FLOW = 3                                     # CODLAD_FM_TARGET_FLOW: the target matcher's flow of a given xt
 ODE_METHODS = {"euler": 0, "midpoint": 1, "rk4": 2}    # CODLAD_ODE_* of include/codlad_hip.h
 ODE_NORM_WORDS = 257                                   # CODLAD_ODE_NORM_WORDS
 
@@ -153,6 +160,11 @@ _SIGS = {
     "codlad_prior_bpd": (C.c_int, [P, P, C.c_int, P, C.c_int, P, P]),
     "codlad_loss_forward": (C.c_int, _JOB + [P, P, P, P, P, P, C.c_int, C.c_int, P, C.c_int, P, C.POINTER(LossTerms), P]),
     "codlad_bpd_loop": (C.c_int, _JOB + [P, P, P, P, P, C.c_int, P, C.c_int, P, P, P, P, P, P]),
+    "codlad_fm_path": (C.c_int, [P, P, P, P, C.c_int, P, C.c_float, C.c_int, C.c_double, P, P, P]),
+    "codlad_fm_terms": (C.c_int, [P, P, P, C.c_int, C.POINTER(FmLossOut), P]),
+    "codlad_fm_loss_forward": (C.c_int, _JOB + [P, P, P, P, C.c_int, P, C.POINTER(FmLossOut), P]),
+    "codlad_fm_loss_loop": (C.c_int, _JOB + [P, P, P, C.c_int, C.c_double, P, C.c_int, P, P, C.c_int, P, P,
+                                             C.POINTER(FmLossOut), P]),
     "codlad_vq_lookup": (C.c_int, [P, C.c_int, P, P, P, C.c_int, P, P, P, P]),
     "codlad_ic_decode": (C.c_int, [C.POINTER(DecoderWeights), P, P, P, P, P, C.c_int, P, P, P]),
     "codlad_cg_graph": (C.c_int, [P, P, C.c_int, C.c_float, P, P, P, P]),

@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcodlad_hip.so")
 SOURCES = ["api.hip", "host_util.hip", "edge_plan.hip", "denoiser_forward.hip", "denoiser_f32_kernels.hip", "node_stream_kernel.hip",
-           "sampler_kernels.hip", "loss_kernels.hip", "edge_msg_kernel.hip", "edge_upd_kernel.hip", "edge_upd1_kernel.hip", "edge_tile_kernels.hip",
+           "sampler_kernels.hip", "loss_kernels.hip", "flow_loss_kernels.hip", "edge_msg_kernel.hip", "edge_upd_kernel.hip", "edge_upd1_kernel.hip", "edge_tile_kernels.hip",
            "edge_wide_kernels.hip",
            "node_wide_kernels.hip", "node_quad_kernels.hip", "ode_kernels.hip", "features_kernels.hip", "decode_kernels.hip",
            "ic_decoder_kernels.hip", "encoder_kernels.hip", "encoder_mfma_kernel.hip", "metrics_kernels.hip"]
@@ -22,6 +22,7 @@ EXTRA_FLAGS = {"features_kernels.hip": ["-ffp-contract=off"], "ode_kernels.hip":
                # the loss terms round as the reference's unfused tensor ops; the head it shares with final_kernel asks for
                # contraction itself (final_head.h)
                "loss_kernels.hip": ["-ffp-contract=off"],
+               "flow_loss_kernels.hip": ["-ffp-contract=off"],      # as loss_kernels.hip; the division stays the correctly rounded one
                "metrics_kernels.hip": ["-ffp-contract=off"], "encoder_kernels.hip": ["-ffp-contract=off"],
                # the SLP vectoriser pairs multiply-adds of different result blocks into v_pk_fma_f32 and pays for it in register
                # moves (337 -> 80 v_mov at depth 0, 14 scratch accesses -> 0 at depth 2 without it)

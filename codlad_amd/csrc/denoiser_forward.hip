@@ -3,6 +3,7 @@
 #include "node_args.h"
 #include "sampler_args.h"
 #include "loss_args.h"
+#include "flow_loss_args.h"
 #include "ode_args.h"
 
 // precision: 0 = fp32 MFMA, 1 = f16x4, 2 = f16x3 (include/codlad_hip.h); terms = 4 or 3 products per split contraction, 0 = fp32
@@ -422,6 +423,65 @@ extern "C" int codlad_bpd_loop(const codlad_denoiser_weights *w, const codlad_jo
     }
     launch_prior(x_start, {sample_off, nullptr, T - 1, T, n_samples, coef}, vb, prior_bpd, total_bpd, st);
     return codlad_check_launch("codlad_bpd_loop");
+}
+
+// Loss evaluation of the flow-matching models (flow_loss_kernels.hip): fm_loss_kernel takes final_kernel's place after
+// enqueue_forward.  x_self_cond = null throughout: zeros, as on the ODE path.
+static FmLossArgs fm_loss_args(const codlad_denoiser_weights *w, const codlad_job *job, const float *mods_t, const float *ut,
+                               const int32_t *sample_off, int n_samples) {
+    FmLossArgs la = {};
+    la.head = final_args(w, job, mods_t);
+    la.ut = ut; la.sample_off = sample_off; la.n_samples = n_samples;
+    return la;
+}
+
+static const char *fm_model_defect(const codlad_denoiser_weights *w, const codlad_job *job, int n_samples) {
+    if (const char *msg = job_defect(w, job)) return msg;
+    if (n_samples <= 0) return "n_samples must be positive";
+    if (w->out_dim != 3) return "the flow-matching losses need a flow-matching model (3 outputs: the velocity)";
+    return nullptr;
+}
+
+extern "C" int codlad_fm_loss_forward(const codlad_denoiser_weights *w, const codlad_job *job, const float *xt,
+                                      const float *ut, const float *mods_t, const int32_t *sample_off, int n_samples,
+                                      float *model_out, const codlad_fm_loss_out *terms, void *stream) {
+    REQUIRE_OK(fm_model_defect(w, job, n_samples));
+    CODLAD_REQUIRE(xt && ut && mods_t && sample_off && terms, "null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    enqueue_forward(w, job, xt, nullptr, mods_t, st);
+    FmLossArgs la = fm_loss_args(w, job, mods_t, ut, sample_off, n_samples);
+    la.head.logits = model_out;
+    la.out = *terms;
+    launch_fm_loss(la, st);
+    return codlad_check_launch("codlad_fm_loss_forward");
+}
+
+extern "C" int codlad_fm_loss_loop(const codlad_denoiser_weights *w, const codlad_job *job, const float *x0, const float *x1,
+                                   const float *eps, int kind, double sigma, const float *t_host, int K, const float *mods,
+                                   const int32_t *sample_off, int n_samples, float *xt, float *ut,
+                                   const codlad_fm_loss_out *tables, void *stream) {
+    REQUIRE_OK(fm_model_defect(w, job, n_samples));
+    CODLAD_REQUIRE(t_host && mods && sample_off && xt && ut && tables, "null pointer");
+    CODLAD_REQUIRE(K > 0, "K must be positive");
+    CODLAD_REQUIRE(kind != CODLAD_FM_TARGET_FLOW, "unknown matcher kind (the loop draws its own locations)");
+    for (int k = 0; k < K; ++k) REQUIRE_OK(fm_path_defect(x0, x1, eps, nullptr, t_host[k], kind, sigma));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n3 = (size_t)job->n_nodes * 3;
+    for (int k = 0; k < K; ++k) {
+        const float *mods_t = mods + (size_t)k * CODLAD_MODS_PER_STEP;
+        launch_fm_path(fm_path_args(x0, x1, eps ? eps + (size_t)k * n3 : nullptr, {sample_off, nullptr, t_host[k], n_samples},
+                                    kind, sigma, xt, ut), st);
+        enqueue_forward(w, job, xt, nullptr, mods_t, st);
+        FmLossArgs la = fm_loss_args(w, job, mods_t, ut, sample_off, n_samples);
+        const size_t row = (size_t)k * n_samples;
+        la.out.l2 = tables->l2 ? tables->l2 + row : nullptr;
+        la.out.l1 = tables->l1 ? tables->l1 + row : nullptr;
+        la.out.huber = tables->huber ? tables->huber + row : nullptr;
+        la.out.smooth_l1 = tables->smooth_l1 ? tables->smooth_l1 + row : nullptr;
+        la.out.log_cosh = tables->log_cosh ? tables->log_cosh + row : nullptr;
+        launch_fm_loss(la, st);
+    }
+    return codlad_check_launch("codlad_fm_loss_loop");
 }
 
 // The fused ODE samplers of the flow-matching models (ode_kernels.hip): ode_stage_kernel takes final_kernel's place after

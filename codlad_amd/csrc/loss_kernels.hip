@@ -7,12 +7,12 @@
 // tensor ops do.  The one exception is final_head (final_head.h), shared with final_kernel (sampler_kernels.hip, a unit
 // built with contraction on): it asks for contraction itself.
 //
-// Reductions: one workgroup per sample.  Half wave w of the eight takes the sample's nodes w, w + 8, ... in order, lane k
-// < 3 of it adds component k's value to its running sum; then (lane 0 + lane 1) + lane 2 per half wave, then half waves
-// 0 .. 7 in order.  The order depends on the sample's length alone: not on the grid, not on what else shares the job,
-// and no floating-point atomic is involved.
+// Reductions: one workgroup per sample, in the fixed order of sample_sum.h (shared with flow_loss_kernels.hip): it
+// depends on the sample's length alone, not on the grid, not on what else shares the job, and no floating-point atomic
+// is involved.
 #include "loss_args.h"
 #include "final_head.h"
+#include "sample_sum.h"
 
 // diffusion_utils.py:10-36, the sum in the reference's order
 DEV float normal_kl(float mean1, float logvar1, float mean2, float logvar2) {
@@ -68,28 +68,6 @@ DEV const float *sample_coef(const LossSamples &s, int sample, int *t_out = null
     t = t < 0 ? 0 : (t >= s.T ? s.T - 1 : t);                 // the host checks the range; never index outside the table
     if (t_out) *t_out = t;
     return s.coef + (size_t)t * CODLAD_LOSS_COLS;
-}
-
-// Sum over the sample of per-lane running sums (lanes 0-2 of every half wave), in the fixed order of the header.
-// part: LDS [NQ][8].  Every thread of the workgroup calls it; the totals are valid in thread 0.
-template <int NQ>
-DEV void sample_sum(float (&acc)[NQ], float (*part)[8]) {
-    const int l = threadIdx.x & 31, hw = threadIdx.x >> 5;
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-        const int base = threadIdx.x & 32;
-        const float s = (__shfl(acc[q], base, 64) + __shfl(acc[q], base + 1, 64)) + __shfl(acc[q], base + 2, 64);
-        if (l == 0) part[q][hw] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            float s = part[q][0];
-            for (int w = 1; w < 8; ++w) s = s + part[q][w];
-            acc[q] = s;
-        }
-    }
 }
 
 template <bool HEAD>

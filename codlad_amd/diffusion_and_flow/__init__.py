@@ -19,7 +19,8 @@ model and `codlad_ddpm_pred_xstart` / `codlad_ddim_step`.  DPM-Solver++(2M) (`dp
 `q_sample`, `q_posterior_mean_variance`, `_vb_terms_bpd`, `training_losses`, and the IDDPM release's `calc_bpd_loop`) are
 evaluated forward-only: the HIP model runs `codlad_loss_forward` per group of equal timesteps and `codlad_bpd_loop` for the
 whole bound, any other CUDA callable is followed by `codlad_vb_terms`.  Gradients and training are out of scope; forward-only
-loss evaluation is built.
+loss evaluation is built - for the flow-matching models in `flow.py` (the reference's matchers, `training_losses`,
+`loss_sweep`), which takes the same two paths.
 """
 import enum
 import random

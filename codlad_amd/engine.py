@@ -225,11 +225,12 @@ class Denoiser:
     def make_job(self, structures, sample_struct):
         return Job(structures, sample_struct, self.device)
 
-    def step_mods(self, t_values, refresh=False):
+    def step_mods(self, t_values, refresh=False, as_float=False):
         """[len(t_values), 6016] adaLN modulation vectors; cached per timestep list (refresh: run the
         kernel again even if cached).  Integer timesteps (diffusion) or fractional ones (flow matching: any
-        non-integer value switches the whole list to the float entry point)."""
-        fractional = any(float(t) != int(t) for t in t_values)
+        non-integer value switches the whole list to the float entry point; as_float: take it in any case - the rows of
+        whole numbers are the same bits through either)."""
+        fractional = as_float or any(float(t) != int(t) for t in t_values)
         key = tuple(float(t) for t in t_values) if fractional else tuple(int(t) for t in t_values)
         if self._mods_generation != self.weights.generation:      # the weights changed under the cache (broadcast)
             self._mods_cache.clear()
@@ -769,6 +770,208 @@ class Denoiser:
         f32 = dict(dtype=torch.float32, device=self.device)
         res = {k: torch.empty(T, S, **f32) for k in ("vb", "mse", "xstart_mse")}
         res.update({k: torch.empty(S, **f32) for k in ("prior_bpd", "total_bpd")})
+        for p, o in enumerate(outs):
+            for k, v in o.items():
+                res[k][..., p::streams] = v
+        if check:
+            self._check_all([p for p, _i in parts])
+        return res
+
+    # -- forward-only loss evaluation of the flow-matching models ---------------------------------
+    FM_LOSS_KEYS = ("l2", "l1", "huber", "smooth_l1", "log_cosh")
+
+    @staticmethod
+    def _fm_kind(kind, sigma):
+        if kind not in _lib.FM_KINDS:
+            raise ValueError(f"kind must be one of {tuple(_lib.FM_KINDS)}, got {kind!r}")
+        if isinstance(sigma, bool) or not isinstance(sigma, (int, float)):
+            raise TypeError(f"sigma must be a number, got {type(sigma).__name__}")
+        if not sigma >= 0:
+            raise ValueError(f"sigma must be >= 0, got {sigma}")
+        return _lib.FM_KINDS[kind], float(sigma)
+
+    @staticmethod
+    def _fm_times(t, n_samples, device):
+        """t in [0, 1]: one value or one per sample -> (list of floats as fp32 holds them, shared value or None, device
+        float32 [n_samples] or None)."""
+        if isinstance(t, torch.Tensor):
+            t = t.reshape(-1).tolist()
+        ts = [t] * n_samples if np.ndim(t) == 0 else list(t)
+        ts = [float(np.float32(v)) for v in ts]
+        if len(ts) != n_samples:
+            raise ValueError(f"t must be one value or one per sample ({n_samples}), got {len(ts)}")
+        if not all(0.0 <= v <= 1.0 for v in ts):
+            raise ValueError(f"t must lie in [0, 1], got {min(ts)} .. {max(ts)}")
+        if len(set(ts)) == 1:
+            return ts, ts[0], None
+        return ts, None, torch.tensor(ts, dtype=torch.float32, device=device)
+
+    @staticmethod
+    def _fm_operand(a, name, like):
+        if a is None:
+            return None
+        _require_cuda(a, name)
+        a = a.contiguous().float()
+        if like is not None and a.shape != like.shape:
+            raise ValueError(f"{name} {tuple(a.shape)} does not match x1 {tuple(like.shape)}")
+        return a
+
+    @staticmethod
+    def fm_path(kind, sigma, x0, x1, eps, lens, t):
+        """The probability path of a conditional flow matcher on flat [n, 3] latents (codlad_fm_path), samples of `lens`
+        nodes, t in [0, 1] one value or one per sample -> (xt, ut).  kind "icfm" (ConditionalFlowMatcher), "target"
+        (TargetConditionalFlowMatcher; x0 is not read, may be None) or "vp" (VariancePreservingConditionalFlowMatcher);
+        eps may be None for icfm / vp at sigma = 0."""
+        kind_id, sigma = Denoiser._fm_kind(kind, sigma)
+        x1 = Denoiser._fm_operand(x1, "x1", None)
+        n = int(sum(lens))
+        if x1.numel() != 3 * n:
+            raise ValueError(f"fm_path: {x1.numel()} values for {n} nodes of 3 channels")
+        x0, eps = Denoiser._fm_operand(x0, "x0", x1), Denoiser._fm_operand(eps, "eps", x1)
+        if kind != "target" and x0 is None:
+            raise ValueError(f"fm_path: the {kind} matcher needs x0")
+        if eps is None and (kind == "target" or sigma != 0):
+            raise ValueError("fm_path: eps may be None only for icfm / vp at sigma = 0")
+        _ts, shared, t_dev = Denoiser._fm_times(t, len(lens), x1.device)
+        off = Denoiser.sample_offsets(lens, x1.device)
+        xt, ut = torch.empty_like(x1), torch.empty_like(x1)
+        rc = _lib.lib().codlad_fm_path(_lib.ptr(x0), _lib.ptr(x1), _lib.ptr(eps), _lib.ptr(off), len(lens), _lib.ptr(t_dev),
+                                       0.0 if shared is None else shared, kind_id, sigma, _lib.ptr(xt), _lib.ptr(ut),
+                                       _lib.stream_ptr(x1.device))
+        _lib.check(rc, "codlad_fm_path")
+        return xt, ut
+
+    @staticmethod
+    def _fm_outputs(shape, device):
+        res = {k: torch.empty(*shape, dtype=torch.float32, device=device) for k in Denoiser.FM_LOSS_KEYS}
+        out = _lib.FmLossOut()
+        for k, v in res.items():
+            setattr(out, k, v.data_ptr())
+        return res, out
+
+    @staticmethod
+    def fm_terms(model_out, ut, lens):
+        """loss_fn's five regression losses per sample from a given model output (codlad_fm_terms): flat [n, 3] model_out
+        and ut, samples of `lens` nodes -> {l2, l1, huber, smooth_l1, log_cosh [n_samples]}, each the mean over the
+        sample's elements."""
+        _require_cuda(model_out, "model_out")
+        _require_cuda(ut, "ut")
+        model_out, ut = model_out.contiguous().float(), ut.contiguous().float()
+        n = int(sum(lens))
+        if tuple(model_out.shape) != (n, 3) or tuple(ut.shape) != (n, 3):
+            raise ValueError(f"fm_terms: model_out and ut must be [{n}, 3], got {tuple(model_out.shape)} and {tuple(ut.shape)}")
+        off = Denoiser.sample_offsets(lens, ut.device)
+        res, out = Denoiser._fm_outputs((len(lens),), ut.device)
+        rc = _lib.lib().codlad_fm_terms(_lib.ptr(model_out), _lib.ptr(ut), _lib.ptr(off), len(lens), C.byref(out),
+                                        _lib.stream_ptr(ut.device))
+        _lib.check(rc, "codlad_fm_terms")
+        return res
+
+    def _check_fm_model(self):
+        if self.weights.out_dim != 3:
+            raise ValueError("the flow-matching losses need a flow-matching model (3 outputs: the velocity); a diffusion "
+                             "model is scored with Denoiser.loss_terms / Denoiser.bpd")
+
+    def _fm_loss_forward(self, job, xt, ut, mods_t, want_model_out):
+        res, out = self._fm_outputs((len(job.sample_struct),), self.device)
+        if want_model_out:
+            res["model_out"] = torch.empty(job.n_nodes, 3, dtype=torch.float32, device=self.device)
+        self._run("codlad_fm_loss_forward", job.desc(), _lib.ptr(xt), _lib.ptr(ut), _lib.ptr(mods_t),
+                  _lib.ptr(self._job_offsets(job)), len(job.sample_struct), _lib.ptr(res.get("model_out")), C.byref(out))
+        return res
+
+    def fm_loss_terms(self, job, x1, t, kind="icfm", sigma=0.0, x0=None, eps=None, check=True, want_model_out=False):
+        """The path of the matcher (`fm_path`) at time t, one denoiser forward on xt and loss_fn's five losses per sample
+        (codlad_fm_loss_forward): {l2, l1, huber, smooth_l1, log_cosh [n_samples], xt, ut [n_nodes, 3] (, model_out)}.
+        t: one time in [0, 1], or one per sample: the samples are then grouped by equal time and every group runs as a
+        ragged sub-job at its time, on two streams, as `loss_terms` groups by timestep; a sample's result does not depend
+        on what shares its job, so the result is, bit for bit, that of calling each group alone.  All distinct times go
+        through one codlad_step_mods_f call.  A batch of N distinct random times therefore costs N small forwards: for a
+        loss over time, `fm_loss_sweep` (one time shared by all samples per forward) is the fast path.  A self-conditioned
+        model is conditioned on zeros."""
+        self._check_fm_model()
+        S = len(job.sample_struct)
+        xt, ut = self.fm_path(kind, sigma, x0, x1, eps, job.sample_lens, t)
+        ts, shared, _t_dev = self._fm_times(t, S, self.device)
+        self._fresh_features(job.structures)
+        distinct = sorted(set(ts))
+        mods = self.step_mods(distinct, as_float=True)
+        if shared is not None:
+            res = self._fm_loss_forward(job, xt, ut, mods[0], want_model_out)
+            res.update(xt=xt, ut=ut)
+            if check:
+                self.check_status(job)
+            return res
+        groups = [(tv, [m for m in range(S) if ts[m] == tv]) for tv in distinct]
+        subs, start = [], 0
+        for _tv, members in groups:
+            subs.append(self._t_group_job(job, members, start))
+            start += subs[-1][0].n_nodes
+        tasks = [lambda g=g, sub=sub, i=i: self._fm_loss_forward(sub, xt[i], ut[i], mods[g], want_model_out)
+                 for g, (sub, i) in enumerate(subs)]
+        outs = self._on_streams(tasks)
+        res = {"xt": xt, "ut": ut}
+        for (_tv, members), (sub, i), o in zip(groups, subs, outs):
+            m = torch.tensor(members, dtype=torch.int64, device=self.device)
+            for k, v in o.items():
+                per_node = k == "model_out"
+                if k not in res:
+                    res[k] = torch.empty((job.n_nodes if per_node else S,) + tuple(v.shape[1:]), dtype=v.dtype,
+                                         device=self.device)
+                res[k][i if per_node else m] = v
+        if check:
+            self._check_all([sub for sub, _i in subs])
+        return res
+
+    def fm_loss_sweep(self, job, x1, ts, kind="icfm", sigma=0.0, x0=None, eps=None, streams=None, check=True):
+        """loss_fn's five losses over a sweep of times, fused (codlad_fm_loss_loop): for every ts[k] in [0, 1], shared by all
+        samples, the path with eps[k] (eps [K, n_nodes, 3]; None for icfm / vp at sigma = 0), one forward and the terms ->
+        {l2, l1, huber, smooth_l1, log_cosh [K, n_samples]}.  Row k is, bit for bit, `fm_loss_terms` at ts[k] with eps[k].
+        streams as for `bpd`: None = two half-jobs on two streams from SPLIT_MIN_NODES nodes up."""
+        self._check_fm_model()
+        kind_id, sigma = self._fm_kind(kind, sigma)
+        ts = [float(np.float32(v)) for v in ts]
+        K, S = len(ts), len(job.sample_struct)
+        if K < 1 or not all(0.0 <= v <= 1.0 for v in ts):
+            raise ValueError("fm_loss_sweep: ts must be a non-empty list of times in [0, 1]")
+        x1 = self._fm_operand(x1, "x1", None)
+        assert x1.shape == (job.n_nodes, 3)
+        x0 = self._fm_operand(x0, "x0", x1)
+        if kind != "target" and x0 is None:
+            raise ValueError(f"fm_loss_sweep: the {kind} matcher needs x0")
+        if eps is None:
+            if kind == "target" or sigma != 0:
+                raise ValueError("fm_loss_sweep: eps may be None only for icfm / vp at sigma = 0")
+        else:
+            _require_cuda(eps, "eps")
+            if tuple(eps.shape) != (K, job.n_nodes, 3):
+                raise ValueError(f"eps must be [K, n_nodes, 3] = {(K, job.n_nodes, 3)}, got {tuple(eps.shape)}")
+        streams = self._n_streams(job, streams)
+        self._fresh_features(job.structures)
+        mods = self.step_mods(ts, as_float=True)
+        t_host = (C.c_float * K)(*ts)
+
+        def run(jb, a0, a1, ae):
+            a1 = a1.contiguous().float()
+            a0 = None if a0 is None else a0.contiguous().float()
+            ae = None if ae is None else ae.contiguous().float()
+            n = len(jb.sample_struct)
+            res, out = self._fm_outputs((K, n), self.device)
+            xt, ut = torch.empty_like(a1), torch.empty_like(a1)
+            self._run("codlad_fm_loss_loop", jb.desc(), _lib.ptr(a0), _lib.ptr(a1), _lib.ptr(ae), kind_id, sigma, t_host, K,
+                      _lib.ptr(mods), _lib.ptr(self._job_offsets(jb)), n, _lib.ptr(xt), _lib.ptr(ut), C.byref(out))
+            return res
+
+        pick = lambda a, i: None if a is None else a[i]                    # noqa: E731
+        if streams <= 1:
+            res = run(job, x0, x1, eps)
+            if check:
+                self.check_status(job)
+            return res
+        parts = job.parts(streams)
+        outs = self._on_streams([lambda p=p, i=i: run(p, pick(x0, i), x1[i], None if eps is None else eps[:, i])
+                                 for p, i in parts], streams)
+        res = {k: torch.empty(K, S, dtype=torch.float32, device=self.device) for k in self.FM_LOSS_KEYS}
         for p, o in enumerate(outs):
             for k, v in o.items():
                 res[k][..., p::streams] = v

@@ -443,6 +443,56 @@ int codlad_bpd_loop(const codlad_denoiser_weights *w, const codlad_job *job, con
                     float *x_t, const float *mods, const float *coef, int T, const int32_t *sample_off, int n_samples,
                     float *vb, float *mse, float *xstart_mse, float *prior_bpd, float *total_bpd, void *stream);
 
+/* Forward-only loss evaluation of the flow-matching models (diffusion_and_flow/flow.py, utils/train_module.py loss_fn):
+ * the probability path of a conditional flow matcher and the regression losses per sample.  Samples and sample_off as
+ * above; a sample's time is t_of_sample[s] (DEVICE float [n_samples]), or `t` for all when t_of_sample is NULL.
+ *
+ * The matchers, every operation rounded separately in the reference's order (sigma_f = (float)sigma):
+ *   CODLAD_FM_ICFM    ConditionalFlowMatcher: xt = (t x1 + (1 - t) x0) + sigma_f eps, ut = x1 - x0
+ *   CODLAD_FM_TARGET  TargetConditionalFlowMatcher, with c = (float)(1.0 - sigma): xt = t x1 + (1 - c t) eps,
+ *                     ut = (x1 - c xt) / (1 - c t); x0 is not read (may be NULL)
+ *   CODLAD_FM_VP      VariancePreservingConditionalFlowMatcher, with h = (float)(pi / 2):
+ *                     xt = (cos(h t) x0 + sin(h t) x1) + sigma_f eps, ut = h (cos(h t) x1 - sin(h t) x0)
+ *   CODLAD_FM_TARGET_FLOW  the target matcher's compute_conditional_flow alone: xt is an INPUT (a given location), ut is
+ *                     written from it as above; x0 and eps are not read.  Not a kind of the fused loop.
+ * eps may be NULL for ICFM and VP when sigma == 0: the noise term is then skipped.  x0, x1, eps, xt, ut: [n_nodes][3]. */
+#define CODLAD_FM_ICFM 0
+#define CODLAD_FM_TARGET 1
+#define CODLAD_FM_VP 2
+#define CODLAD_FM_TARGET_FLOW 3
+int codlad_fm_path(const float *x0 /* may be NULL */, const float *x1, const float *eps /* may be NULL */,
+                   const int32_t *sample_off, int n_samples, const float *t_of_sample /* may be NULL */, float t, int kind,
+                   double sigma, float *xt, float *ut, void *stream);
+
+/* Per-sample means over the sample's 3 L elements of, with d = model output - ut:
+ *   l2 d^2, l1 |d|, huber (|d| < 1 ? 0.5 d^2 : |d| - 0.5), smooth_l1 (beta 1: huber's values), log_cosh log(cosh(d)).
+ * Each may be NULL.  The sums run in the fixed order of the terms above (the sample's length alone decides the bits). */
+typedef struct {
+    float *l2, *l1, *huber, *smooth_l1, *log_cosh;       /* [n_samples] each */
+} codlad_fm_loss_out;
+
+/* The five terms from a given model output [n_nodes][3] and ut.  Stand-alone, as codlad_vb_terms is. */
+int codlad_fm_terms(const float *model_out, const float *ut, const int32_t *sample_off, int n_samples,
+                    const codlad_fm_loss_out *terms, void *stream);
+
+/* One denoiser forward on xt with the modulation row of its time (mods_t, from codlad_step_mods_f) followed by the five
+ * terms, the final layer's velocity head fused into their kernel: it gives the bits of codlad_denoiser_forward's output.
+ * model_out [n_nodes][3] (may be NULL) receives that output.  The model must have 3 outputs; a self-conditioned model is
+ * conditioned on zeros, as on the ODE path.  The workspace's status word is set as by every forward. */
+int codlad_fm_loss_forward(const codlad_denoiser_weights *w, const codlad_job *job, const float *xt, const float *ut,
+                           const float *mods_t, const int32_t *sample_off, int n_samples,
+                           float *model_out /* may be NULL */, const codlad_fm_loss_out *terms, void *stream);
+
+/* The loss over a sweep of times, fused: for k = 0 .. K-1 the path at time t_host[k] (HOST float [K], each in [0, 1],
+ * shared by every sample) with noise entry k of eps [K][n_nodes][3] (may be NULL where the kind allows), one forward with
+ * mods row k (mods: DEVICE [K][6016], one codlad_step_mods_f call over t_host), then the terms into row k of the five
+ * [K][n_samples] tables (each may be NULL).  xt and ut [n_nodes][3] are scratch.  No host synchronisation; the sticky
+ * status word as in the sampling loops. */
+int codlad_fm_loss_loop(const codlad_denoiser_weights *w, const codlad_job *job, const float *x0 /* may be NULL */,
+                        const float *x1, const float *eps /* may be NULL */, int kind, double sigma, const float *t_host,
+                        int K, const float *mods, const int32_t *sample_off, int n_samples, float *xt, float *ut,
+                        const codlad_fm_loss_out *tables, void *stream);
+
 /* Next row 8f-4, fused: the ODE samplers of the flow-matching models as one call per fixed grid / per attempted adaptive
  * step.  ode_stage_kernel takes final_kernel's place after a forward: the final layer's 3-row velocity head (the bits of
  * final_kernel's logits mode), the slope stored, and in the same kernel the next stage's input (after the last stage:

@@ -23,6 +23,10 @@ every batch; addition: `--ode_stepwise` integrates with one model call per stage
 Addition: `--experiment bpd` scores the checkpoint instead of sampling from it: the variational bound in bits per dimension
 (calc_bpd_loop over --num_sampling_steps respaced steps, one fused loop per batch) of the batch's own VQ-VAE latents; prints
 the mean total_bpd / prior_bpd per file and saves vb / mse / xstart_mse [N, T] as .npy.  One rank only.
+Addition: `--experiment fmloss` scores a flow-matching checkpoint (--model fm / icfm / vpfm) the way the reference's
+validation pass does (train_latent.py:338-350: the matcher's path, the model, loss_fn), at the K = --num_steps times
+(k + 0.5) / K, one fused sweep per batch: x1 = the batch's own VQ-VAE latents, x0 and the path's noise from the run's seed;
+prints the mean --loss per file and per time and saves the per-sample table [N, K] as .npy.  One rank only.
 """
 import argparse
 import os
@@ -162,10 +166,41 @@ def check_bpd(args, world):
         raise SystemExit("--experiment bpd needs input with atoms: --pdb_files, --data_process --data_files or --synthetic")
 
 
+FMLOSS_MODELS = ("fm", "icfm", "vpfm")
+
+
+def check_fmloss(args, world):
+    """--experiment fmloss: the flow-matching regression loss of the batch's own latents, per time."""
+    if args.experiment != "fmloss":
+        return
+    if world > 1:
+        raise SystemExit("--experiment fmloss runs on one rank: gathering its per-time tables across ranks is not built "
+                         f"(WORLD_SIZE={world})")
+    if args.model == "diffusion":
+        raise SystemExit("--experiment fmloss needs a flow-matching model (--model fm / icfm / vpfm): 'diffusion' is a "
+                         "diffusion model, which is scored with --experiment bpd")
+    if args.model not in FMLOSS_MODELS:
+        raise SystemExit(f"--experiment fmloss needs --model fm / icfm / vpfm: the matcher of {args.model!r} is not built "
+                         "(otcfm needs the POT package's exact transport plan, sbcfm a score head the model does not have)")
+    if args.vae_type not in ("N6", "K3", "K4"):
+        raise SystemExit(f"--experiment fmloss needs a VQ-VAE (N6 / K3 / K4) to encode the structures, not {args.vae_type!r}")
+    if not (args.synthetic or getattr(args, "pdb_files", None) or args.data_process):
+        raise SystemExit("--experiment fmloss needs input with atoms: --pdb_files, --data_process --data_files or --synthetic")
+    if fmloss_steps(args) < 1:
+        raise SystemExit(f"--experiment fmloss needs --num_steps >= 1, got {fmloss_steps(args)}")
+    if getattr(args, "fm_sigma", 0.0) < 0:
+        raise SystemExit(f"--fm_sigma must be >= 0, got {args.fm_sigma}")
+
+
+def fmloss_steps(args):
+    """K of --experiment fmloss: --num_steps (the reference's flag of that name, default 40)."""
+    return int(args.num_steps)
+
+
 def load_vae(args, device, load=True):
     """The VQ-VAE; with its e3nn encoder when the run needs it (`--experiment recon` encodes the batch's atoms, so does
     --fix_residues for the latents it pins and `--experiment bpd` for the latents it scores)."""
-    enc = args.experiment in ("recon", "bpd") or getattr(args, "fix_residues", None) is not None
+    enc = args.experiment in ("recon", "bpd", "fmloss") or getattr(args, "fix_residues", None) is not None
     if not load:
         return build_vae(args.vae_type, with_encoder=enc).to(device).eval()
     if args.synthetic_weights:
@@ -228,7 +263,7 @@ def iter_batches(args):
                 _TOPOLOGY[out] = (names, [synth.PDB_ATOM_ORDER[nm] for nm in names])
                 batch = synth.make_batch(prot, range(a, b))
                 # the encoder reads the all-atom side of the batch (recon; the known latents of --fix_residues)
-                if getattr(args, "experiment", "latent") in ("recon", "bpd") or getattr(args, "fix_residues", None) is not None:
+                if getattr(args, "experiment", "latent") in ("recon", "bpd", "fmloss") or getattr(args, "fix_residues", None) is not None:
                     batch.update(synth.make_atoms(prot, range(a, b), seed=1000 + i))
                 yield out, batch, prot["info"]
         return
@@ -336,6 +371,7 @@ def main(args):
     # ranks longest-first, every rank samples and decodes its own, rank 0 reports the totals
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     check_bpd(args, world)
+    check_fmloss(args, world)
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     backend = os.environ.get("CODLAD_DIST_BACKEND", "nccl")   # "gloo": rehearsal of N > 1 on a one-GPU box
     dev_index = local_rank if backend == "nccl" else local_rank % torch.cuda.device_count()
@@ -363,7 +399,7 @@ def main(args):
     model, cvae = None, None
     if args.experiment == "genzprot":
         cvae = load_cvae(args, device, load=rank == 0)
-    if args.experiment in ("latent", "bpd"):
+    if args.experiment in ("latent", "bpd", "fmloss"):
         model = load_denoiser(args, device, load=rank == 0)
         diffusion = None if args.model != "diffusion" else create_diffusion(respacing_spec(args), noise_schedule=args.noise_schedule,
                                      predict_xstart=args.predict_xstart,
@@ -374,7 +410,7 @@ def main(args):
             print(f"--timestep_spacing logsnr: {diffusion.num_timesteps} of {args.num_sampling_steps} requested steps kept "
                   "(steps on the same base step merge)", flush=True)
     elif args.experiment not in ("recon", "genzprot"):
-        raise NotImplementedError(f"experiment {args.experiment!r}: latent, recon, genzprot and bpd are built")
+        raise NotImplementedError(f"experiment {args.experiment!r}: latent, recon, genzprot, bpd and fmloss are built")
     if world > 1:
         from codlad_amd import parallel
         mods = [m for m in (model, vae, cvae) if m is not None]
@@ -420,6 +456,28 @@ def main(args):
                 np.save(os.path.join(save_dir, f"{name}_bpd_{key}.npy"), r[key].cpu().numpy())
             print(f"{name}: {B} frames, L={L}, T={diffusion.num_timesteps}: total_bpd {float(r['total_bpd'].mean()):.6f} "
                   f"prior_bpd {float(r['prior_bpd'].mean()):.6e}: {dt:.2f}s ({B / dt:.1f} structures/s)", flush=True)
+            continue
+        if args.experiment == "fmloss":
+            # the frames' own latents (as --experiment bpd obtains them) are the data end x1 of the path; the source end x0
+            # and the path's noise per time come from the batch's generator; times are the midpoints (k + 0.5) / K, never 0
+            # or 1, where the target matcher's flow divides by 1 - t
+            from codlad_amd.diffusion_and_flow.flow import create_flow_matcher
+            K = fmloss_steps(args)
+            ts = [(k + 0.5) / K for k in range(K)]
+            x1 = get_norm_feature(vae.get_latent_wovq(batch)[0], args.vae_type, norm_channel=args.norm,
+                                  norm_single=args.norm_single, norm_in=True, dataname=args.data_type).contiguous()
+            x0 = torch.randn(x1.shape, device=device, dtype=x1.dtype, generator=gen)
+            eps = torch.stack([torch.randn(x1.shape, device=device, dtype=x1.dtype, generator=gen) for _ in range(K)])
+            r = create_flow_matcher(args.model, args.fm_sigma).loss_sweep(
+                model.forward, x0, x1, ts, step_noise=eps, loss_type=args.loss, model_kwargs=dict(y=None, mask=mask[:B], batch=rep))
+            torch.cuda.synchronize()
+            dt = time.time() - st
+            total += B
+            np.save(os.path.join(save_dir, f"{name}_fmloss_{args.loss}.npy"), r["per_sample"].cpu().numpy())     # [N, K]
+            print(f"{name}: {B} frames, L={L}, K={K}, {args.model} sigma={args.fm_sigma}: mean {args.loss} "
+                  f"{float(r['loss'].mean()):.6f}: {dt:.2f}s ({B / dt:.1f} structures/s)", flush=True)
+            for tv, v in zip(ts, r["loss"].tolist()):
+                print(f"  t={tv:.4f} {args.loss} {v:.6f}", flush=True)
             continue
         if args.experiment == "latent":
             z = torch.randn(B * E, L, args.latent_size, device=device, generator=gen)
@@ -520,7 +578,7 @@ if __name__ == "__main__":
     p.add_argument("--predict_xstart", action="store_true", default=False)
     p.add_argument("--rescale_learned_sigmas", action="store_true", default=False)
     p.add_argument("--noise_schedule", type=str, default="linear", choices=["linear", "squaredcos_cap_v2"])
-    p.add_argument("--experiment", type=str, default="latent", choices=["genzprot", "recon", "latent", "bpd"])
+    p.add_argument("--experiment", type=str, default="latent", choices=["genzprot", "recon", "latent", "bpd", "fmloss"])
     p.add_argument("--ckpt_type", type=str, default="net")
     p.add_argument("--sample_index", type=int, default=0)
     p.add_argument("--compute_nfe", action="store_true",
@@ -538,6 +596,9 @@ if __name__ == "__main__":
     p.add_argument("--steps", type=int, default=2)
     # additions
     p.add_argument("--data_files", nargs="*", default=[], help="with --data_process: pickles of (list of frame dicts, info)")
+    p.add_argument("--loss", type=str, default="l2", choices=["l2", "l1", "huber", "smooth_l1", "log_cosh"],
+                   help="--experiment fmloss: the regression loss reported (the reference's train_latent.py --loss)")
+    p.add_argument("--fm_sigma", type=float, default=0.0, help="--experiment fmloss: the matcher's sigma")
     p.add_argument("--synthetic", action="store_true", help="synthetic PED/PDB/Atlas-shaped proteins")
     p.add_argument("--synthetic_frames", type=int, default=10)
     p.add_argument("--synthetic_weights", action="store_true", help="seeded random weights (no checkpoints ship)")
