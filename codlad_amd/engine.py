@@ -1199,9 +1199,27 @@ class Decoder:
             o += L
         return torch.from_numpy(rng).to(self.device)
 
-    def ic_decode(self, z_q, cg_z, cg_xyz, pairs=None, csr=None):
+    # The decoder's scratch, float [M][200], as the kernels lay it out (csrc/ic_decoder_kernels.hip, "Scratch"): four
+    # planes of 40 M floats, S^T [40][M] | V [M][40] | phi_a [M][40] | phi_b [M][40]; message block b reads its phi from
+    # plane b & 1 and writes the next block's to the other.  Nothing else in Python knows this.
+    SCRATCH_WIDTH = 200
+
+    @staticmethod
+    def read_taps(scratch):
+        """What a finished ic_decode leaves in the `scratch` it was given -> dict of [M,40] tensors (copies): "S" the
+        final state (the heads' input), "V" the message sum of block 3, "phi3" the phi rows block 3 summed over and
+        "phi2" those of block 2."""
+        M = scratch.shape[0]
+        assert scratch.shape == (M, Decoder.SCRATCH_WIDTH) and scratch.is_contiguous()
+        planes = scratch.reshape(-1).reshape(5, 40 * M)
+        return {"S": planes[0].reshape(40, M).t().contiguous(), "V": planes[1].reshape(M, 40).clone(),
+                "phi2": planes[2].reshape(M, 40).clone(), "phi3": planes[3].reshape(M, 40).clone()}
+
+    def ic_decode(self, z_q, cg_z, cg_xyz, pairs=None, csr=None, scratch=None):
         """z_q [M,3], cg_z [M], cg_xyz [M,3] and either the undirected CG pairs [E,2] (flat node
-        indices, as in batch['CG_nbr_list']) or a prebuilt csr = (ptr, src) -> ic [M,13,3]."""
+        indices, as in batch['CG_nbr_list']) or a prebuilt csr = (ptr, src) -> ic [M,13,3].
+        scratch: the caller's own float32 [M,200] work buffer in place of a fresh one; `read_taps` reads the
+        intermediate state out of it afterwards."""
         _require_cuda(z_q, "z_q")
         M = z_q.shape[0]
         cg_z = cg_z.to(self.device, torch.int32).contiguous()
@@ -1210,7 +1228,15 @@ class Decoder:
             raise ValueError(f"cg_z (residue types {lo}..{hi}) outside the decoder's 25-row embedding tables")
         ptr, src = csr if csr is not None else self.csr_from_pairs(pairs.to(self.device), M)
         assert ptr.numel() == M + 1 and ptr.dtype == torch.int32 and src.dtype == torch.int32
-        scratch = torch.empty(M, 200, dtype=torch.float32, device=self.device)
+        if src.numel() == 0:        # a graph without edges (either builder returns an empty src, whose pointer is null):
+            src = torch.zeros(1, dtype=torch.int32, device=self.device)      # the library wants a buffer; every V is 0
+        if scratch is None:
+            scratch = torch.empty(M, self.SCRATCH_WIDTH, dtype=torch.float32, device=self.device)
+        else:
+            _require_cuda(scratch, "scratch")
+            if scratch.shape != (M, self.SCRATCH_WIDTH) or scratch.dtype != torch.float32 or not scratch.is_contiguous():
+                raise ValueError(f"scratch must be a contiguous float32 [{M}, {self.SCRATCH_WIDTH}] tensor, got "
+                                 f"{scratch.dtype} {tuple(scratch.shape)}")
         ic = torch.empty(M, 13, 3, dtype=torch.float32, device=self.device)
         rc = self.lib.codlad_ic_decode(C.byref(self.weights.struct), _lib.ptr(z_q.contiguous().float()),
                                        _lib.ptr(cg_z),

@@ -46,35 +46,63 @@ def _seq(sd, p, x):
     return _lin(sd, f"{p}.3", _swish(_lin(sd, f"{p}.1", _swish(x))))
 
 
-def ic_decode(sd, z_q_flat, cg_z, cg_xyz, nbr_undirected, angle=False, p="equivaraintconv", latent_is_state=False):
-    """z_q_flat [M,3] (restore_shape'd), cg_z [M], cg_xyz [M,3], nbr [E,2] j>i -> ic [M,13,3].
-    latent_is_state: the C2 model (GenZProt.decoder, vae_model.py:556-561) hands its 36-wide latent to the IC decoder
-    as it is - no map_out."""
-    S = z_q_flat if latent_is_state else _lin(sd, "map_out", z_q_flat)  # vae_model.py:762
-    nb = nbr_undirected
-    gtr_ij = bool((nb[:, 0] > nb[:, 1]).any())
-    gtr_ji = bool((nb[:, 1] > nb[:, 0]).any())
-    if not (gtr_ij and gtr_ji):                                         # gcn_nn.py:54-64
-        nb = torch.cat([nb, nb.flip(1)], dim=0)
+def directed(nbr):
+    """make_directed (gcn_nn.py:54-64): a list that already holds rows with i > j and rows with j > i is the directed
+    graph as given (receiver in column 0, sender in column 1); anything else is mirrored."""
+    gtr_ij = bool((nbr[:, 0] > nbr[:, 1]).any())
+    gtr_ji = bool((nbr[:, 1] > nbr[:, 0]).any())
+    if not (gtr_ij and gtr_ji):
+        nbr = torch.cat([nbr, nbr.flip(1)], dim=0)
+    return nbr
+
+
+def edge_geometry(cg_xyz, nbr, dtype=None):
+    """-> (directed pairs [E,2], dist [E], rbf [E,15], env [E]) in `dtype` (default: that of cg_xyz).
+    The radial-basis coefficients n pi / 21 are the model's float32 buffer (gcn_nn.py:231-240 registers
+    `torch.arange(1, 16).float() * pi / cutoff`), cast up as the weights are - not recomputed in float64."""
+    dtype = cg_xyz.dtype if dtype is None else dtype
+    cg_xyz = cg_xyz.to(dtype)
+    nb = directed(nbr)
     r_ij = cg_xyz[nb[:, 1]] - cg_xyz[nb[:, 0]]
     dist = ((r_ij ** 2 + 1e-8).sum(-1)) ** 0.5                           # gcn_nn.py:66-70
-    bb_dist = F.embedding(cg_z, sd[f"{p}.backbone_dist.weight"]).unsqueeze(-1)
-    sc_dist = F.embedding(cg_z, sd[f"{p}.sidechain_dist.weight"]).unsqueeze(-1)
-    S = torch.cat([S, F.embedding(cg_z, sd[f"{p}.res_embed.weight"])], dim=-1)
     n = torch.arange(1, 16).float()
-    coef = n * math.pi / 21.0
+    coef = (n * math.pi / 21.0).to(dtype)
+    one, zero = torch.ones((), dtype=dtype), torch.zeros((), dtype=dtype)
     sd_ = dist.unsqueeze(-1)
     num = torch.where(sd_ == 0, coef, torch.sin(coef * sd_))
-    den = torch.where(sd_ == 0, torch.tensor(1.0), sd_)
-    rbf = torch.where(sd_ >= 21.0, torch.tensor(0.0), num / den)        # gcn_nn.py:231-255
+    den = torch.where(sd_ == 0, one, sd_)
+    rbf = torch.where(sd_ >= 21.0, zero, num / den)                     # gcn_nn.py:231-255
     env = 0.5 * (torch.cos(math.pi * dist / 21.0) + 1)
     env = torch.where(dist >= 21.0, torch.zeros_like(env), env)         # gcn_nn.py:265-271
-    for i in range(4):
-        mp = f"{p}.message_blocks.{i}"
-        phi = _lin(sd, f"{mp}.inv_dense.1", _swish(_lin(sd, f"{mp}.inv_dense.0", S)))[nb[:, 1]]
-        w_s = _lin(sd, f"{mp}.dist_embed.block.1", rbf) * env.reshape(-1, 1)
-        v = torch.zeros_like(S).index_add_(0, nb[:, 0], phi * w_s)     # scatter_add
-        S = S + _seq(sd, f"{p}.dense_blocks.{i}", v)
+    return nb, dist, rbf, env
+
+
+def block_phi(sd, blk, S, p="equivaraintconv"):
+    """inv_dense of message block `blk` on the raw state: phi [M,40], one row per sending residue."""
+    mp = f"{p}.message_blocks.{blk}"
+    return _lin(sd, f"{mp}.inv_dense.1", _swish(_lin(sd, f"{mp}.inv_dense.0", S)))
+
+
+def message_sum(sd, blk, phi, cg_xyz, nbr, p="equivaraintconv", geometry=None):
+    """The message sum of block `blk` alone: v[n] = sum over incoming edges (j -> n), in list order, of
+    phi[j] * (dist_embed(rbf(d)) * envelope(d)), in the dtype of `sd` (phi and cg_xyz are cast to it).  `phi` may be a
+    device's own rows: the sum is then held to a reference that shares its input."""
+    dtype = sd[f"{p}.message_blocks.{blk}.dist_embed.block.1.weight"].dtype
+    nb, _dist, rbf, env = edge_geometry(cg_xyz, nbr, dtype) if geometry is None else geometry
+    phi = phi.to(dtype)
+    w_s = _lin(sd, f"{p}.message_blocks.{blk}.dist_embed.block.1", rbf) * env.reshape(-1, 1)
+    return torch.zeros_like(phi).index_add_(0, nb[:, 0], phi[nb[:, 1]] * w_s)     # scatter_add
+
+
+def dense_update(sd, blk, S, v, p="equivaraintconv"):
+    return S + _seq(sd, f"{p}.dense_blocks.{blk}", v)
+
+
+def heads(sd, S, cg_z, angle=False, p="equivaraintconv"):
+    """The output heads on the final state S [M,40] -> ic [M,13,3]; bond lengths (and, for the non-angle model, the
+    side-chain angles) are table rows."""
+    bb_dist = F.embedding(cg_z, sd[f"{p}.backbone_dist.weight"]).unsqueeze(-1)
+    sc_dist = F.embedding(cg_z, sd[f"{p}.sidechain_dist.weight"]).unsqueeze(-1)
     bb_angle = _seq(sd, f"{p}.backbone_angle", S)
     bb_tors = _seq(sd, f"{p}.backbone_torsion", torch.cat([S, bb_angle], dim=-1))
     if angle:                                                           # vae_model.py:403-407
@@ -89,6 +117,35 @@ def ic_decode(sd, z_q_flat, cg_z, cg_xyz, nbr_undirected, angle=False, p="equiva
     ic_bb = torch.cat([bb_dist, bb_angle.unsqueeze(-1), bb_tors.unsqueeze(-1)], dim=-1)
     ic_sc = torch.cat([sc_dist, sc_angle.unsqueeze(-1), sc_tors.unsqueeze(-1)], dim=-1)
     return torch.cat([ic_bb, ic_sc], dim=-2)
+
+
+def ic_decode(sd, z_q_flat, cg_z, cg_xyz, nbr_undirected, angle=False, p="equivaraintconv", latent_is_state=False,
+              taps=None, phi_sub=None):
+    """z_q_flat [M,3] (restore_shape'd), cg_z [M], cg_xyz [M,3], nbr [E,2] j>i -> ic [M,13,3].
+    latent_is_state: the C2 model (GenZProt.decoder, vae_model.py:556-561) hands its 36-wide latent to the IC decoder
+    as it is - no map_out.
+    Runs in the dtype of `sd`: z_q_flat and cg_xyz are cast to it, so a float64 state dict (tests/conditioning.py
+    to_dtype) gives a float64 evaluation throughout.  One thing stays float32 then, as it does in the model: the
+    radial-basis coefficients n pi / 21 are a float32 buffer, cast up like the weights (edge_geometry).
+    taps: a dict that receives "S0" (the state after map_out and res_embed) and per message block i "phi{i}" [M,40],
+    "v{i}" (the message sum) and "S{i+1}" (the state after the block); heads(sd, taps["S4"], ...) is the result.
+    phi_sub: {block: phi [M,40]} used in place of the block's own phi (a device's rows, cast to the dtype)."""
+    dtype = sd[f"{p}.res_embed.weight"].dtype
+    z_q_flat = z_q_flat.to(dtype)
+    S = z_q_flat if latent_is_state else _lin(sd, "map_out", z_q_flat)  # vae_model.py:762
+    S = torch.cat([S, F.embedding(cg_z, sd[f"{p}.res_embed.weight"])], dim=-1)
+    geometry = edge_geometry(cg_xyz, nbr_undirected, dtype)
+    if taps is not None:
+        taps["S0"] = S
+    for i in range(4):
+        phi = block_phi(sd, i, S, p)
+        if phi_sub is not None and i in phi_sub:
+            phi = phi_sub[i].to(dtype)
+        v = message_sum(sd, i, phi, cg_xyz, nbr_undirected, p, geometry=geometry)
+        S = dense_update(sd, i, S, v, p)
+        if taps is not None:
+            taps[f"phi{i}"], taps[f"v{i}"], taps[f"S{i + 1}"] = phi, v, S
+    return heads(sd, S, cg_z, angle, p)
 
 
 def latent_decode(sd, latent, batch, angle=False):
