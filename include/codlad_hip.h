@@ -772,6 +772,34 @@ int codlad_bond_graph_counts(const float *xyz, const float *xyz_recon, const flo
                              const int32_t *struct_ptr, int n_struct, int max_atoms, float scale, int32_t *counts,
                              void *stream);
 
+/* Ensemble analysis after the path (stands in for md.rmsd in the reference's compute_div, test.py:37-95, and serves the
+ * analyses a backmapping user expects: RMSD to a reference on an atom subset, pairwise RMSD matrices, aligned output):
+ * the minimal mean squared deviation of conformation a onto conformation b under a proper rotation plus translation.
+ * Added to ABI version 19 without changing the number: four new entry points, no existing signature, struct or option
+ * changes, so a binding written against 19 keeps working.
+ * Conformations are fp32 [n_atoms][3], converted exactly; all arithmetic is fp64.  sel (device int32 [n_sel], entries in
+ * [0, n_atoms); NULL with n_sel = 0: all atoms) restricts the fit and the deviation to an atom subset, m = its size; an
+ * entry out of range reads nothing and makes the results NaN.  msd = max(Ga + Gb - 2 lambda, 0) / m with G = sum |x - c|^2
+ * about the centroid c and lambda the largest eigenvalue of Horn's 4x4 matrix of S = sum (a - ca)(b - cb)^T (cyclic Jacobi):
+ * reflections are excluded by construction.  All sums run in one fixed order and there are no atomics: results are
+ * bit-identical from call to call and a pair's result does not depend on the other pairs of the call or on its place.
+ *
+ * codlad_ens_moments: mom [n_conf][4] = {cx, cy, cz, G} of every conformation of the pool x [n_conf][n_atoms][3] (over sel). */
+int codlad_ens_moments(const float *x, int n_conf, int n_atoms, const int32_t *sel, int n_sel, double *mom, void *stream);
+/* Pair p = (pairs[p][0] into pool A [nA], pairs[p][1] into pool B [nB]) (device int32 [n_pairs][2]; an index out of
+ * range gives NaN), momA / momB from codlad_ens_moments with the same sel.  out [n_pairs] = msd (squared != 0) or its
+ * square root; Rt (may be NULL) [n_pairs][12] = R row-major then t, with R a + t superposed on b. */
+int codlad_ens_pair_msd(const float *A, const double *momA, int nA, const float *B, const double *momB, int nB, int n_atoms,
+                        const int32_t *sel, int n_sel, const int32_t *pairs, int n_pairs, int squared, double *out,
+                        double *Rt, void *stream);
+/* out[c] = R_c x[c] + t_c for every atom of conformation c, computed in fp64 and rounded once to fp32 (out may be x). */
+int codlad_ens_apply(const float *x, const double *Rt, int n_conf, int n_atoms, float *out, void *stream);
+/* x [G][F][n_atoms][3] (members x frames), mom [G * F][4] of it: out [F][G][G] = msd or RMSD of every pair of members of
+ * a frame.  The upper triangle is computed (the bits codlad_ens_pair_msd gives for the pair) and mirrored, the diagonal
+ * is written as 0. */
+int codlad_ens_pairwise(const float *x, const double *mom, int G, int F, int n_atoms, const int32_t *sel, int n_sel,
+                        int squared, double *out, void *stream);
+
 /* Self-test of the MFMA chain primitive: Y[n][:] = act(W @ X[n][:] + bias), n < 32*tiles.
  * act: 0 = none, 1 = exact-erf GELU. */
 int codlad_selftest_gemm128(const float *W_packed, const float *bias, const float *X, int n_rows,

@@ -9,6 +9,8 @@ p_sample_loop -> get_norm_feature -> latent_decode -> ic_to_xyz, and the output 
 Different by design: all ensemble members of a batch of frames are sampled in ONE launch set (the
 reference loops over them); the C2 prior call that only supplies `mask` (test.py:495) is replaced by
 the length mask; mdtraj I/O is replaced by saving coordinates as .npy (and multi-model PDB + .xtc, --save_pdb).
+Addition: `--superpose first|ref` writes the --save_pdb models superposed on model 0 of their frame's ensemble or on the true
+structure (CA fit on the device, metrics.superpose); the .npy is never altered.
 Data: `--pdb_files ens.pdb ...` (multi-model PDB ensembles -> the reference's load_dataset without mdtraj),
 `--data_process --data_files f.pkl ...` (pickled per-frame dicts, as the reference's --data_process branch reads
 them) or `--synthetic` (no PED/PDB/Atlas files ship with the reference).
@@ -319,8 +321,8 @@ class Evaluation:
         self.ged += ag
         a, b = xr.reshape(-1, n_atoms, 3), xyz.reshape(-1, n_atoms, 3)
         self.rmsd.append((a - b).pow(2).sum(-1).mean(-1).sqrt().mean().item())      # unaligned all-atom RMSD, test.py:661
-        self.recon.append(a.cpu())
-        self.true = b.cpu()
+        self.recon.append(a)                                 # stay on the device: report superposes them there
+        self.true = b
 
     def report(self, name, args):
         mean = lambda k: float(np.mean([r[k] for r in self.rows]))  # noqa: E731
@@ -335,6 +337,38 @@ class Evaluation:
             print(k, v)
         print("############## ^^^^^^^^^ result test_stats:")
         return stats
+
+
+def ca_indices(topology):
+    """Positions of the CA atoms among the written atoms of a (residue names, atom names per residue) topology (the
+    flanking residues are not written, protein_module.write_pdb)."""
+    idx, serial = [], 0
+    for present in topology[1][1:-1]:
+        for a in present:
+            if a == "CA":
+                idx.append(serial)
+            serial += 1
+    return idx
+
+
+def superpose_models(xyz, mode, ref=None, sel=None):
+    """--superpose: the ensemble xyz [E, B, n_atoms, 3] (device) with every model moved rigidly onto model 0 of its frame's
+    ensemble ("first", model 0 itself is left as it is) or onto the true structure ref [B, n_atoms, 3] ("ref"); the fit uses
+    the atoms `sel` (default: all), all atoms move.  "none" returns xyz itself."""
+    if mode == "none":
+        return xyz
+    E, B, n = xyz.shape[:3]
+    if mode == "first":
+        if E == 1:
+            return xyz
+        moved = metrics.superpose(xyz[1:].reshape(-1, n, 3), xyz[0].repeat(E - 1, 1, 1), sel=sel)
+        return torch.cat((xyz[:1], moved.reshape(E - 1, B, n, 3).to(xyz.dtype)))
+    if mode != "ref":
+        raise ValueError(f"--superpose must be none, first or ref, not {mode!r}")
+    if ref is None:
+        raise ValueError("--superpose ref needs the true coordinates of the batch (nxyz): this input has none")
+    ref = ref.reshape(B, n, 3)
+    return metrics.superpose(xyz.reshape(-1, n, 3), ref.repeat(E, 1, 1), sel=sel).reshape(E, B, n, 3).to(xyz.dtype)
 
 
 def unit_generator(args, batch_id, device):
@@ -539,7 +573,13 @@ def main(args):
             # of member 0 first (multi-model PDB in Angstrom, .xtc in nm as the format has it)
             from codlad_amd.utils.protein_module import write_pdb
             from codlad_amd.utils.xtc import write_xtc
-            frames = xyz.reshape(-1, xyz.shape[2], 3).cpu().numpy()
+            mode = getattr(args, "superpose", "none")
+            if mode == "ref" and "nxyz" not in batch:
+                raise SystemExit("--superpose ref needs the true coordinates of the batch (nxyz); this input has none: "
+                                 "use --superpose first")
+            out = superpose_models(xyz, mode, ref=batch["nxyz"][:, 1:] if mode == "ref" else None,
+                                   sel=(ca_indices(_TOPOLOGY[name]) or None) if mode != "none" else None)
+            frames = out.reshape(-1, xyz.shape[2], 3).cpu().numpy()
             write_pdb(os.path.join(save_dir, f"generated_traj_{name}.pdb"), frames, *_TOPOLOGY[name])
             write_xtc(os.path.join(save_dir, f"generated_traj_{name}.xtc"), frames)
         print(f"{name}: {B} frames x {E} members, L={L}, {xyz.shape[2]} atoms: {dt:.2f}s "
@@ -605,6 +645,10 @@ if __name__ == "__main__":
     p.add_argument("--ode_stepwise", action="store_true",
                    help="ODE sampling: one model call per stage from the host instead of the fused loop (same numbers)")
     p.add_argument("--save_pdb", action="store_true", help="also write the generated ensemble as a multi-model PDB and an .xtc trajectory")
+    p.add_argument("--superpose", default="none", choices=["none", "first", "ref"],
+                   help="with --save_pdb: write the models rigidly superposed on model 0 of the same frame's ensemble (first) or "
+                        "on the true structure (ref; needs input with atoms); the fit uses the CA atoms; _xyz_recon.npy is "
+                        "never altered")
     p.add_argument("--save_codes", action="store_true", help="also save the VQ code index of every residue, [structures, L] (VQ-VAE decoders)")
     p.add_argument("--pdb_files", nargs="*", default=None,
                    help="multi-model PDB ensembles to build the test set from (the reference's load_dataset, without mdtraj)")
