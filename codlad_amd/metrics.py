@@ -6,6 +6,9 @@ as the reference functions; tensors must be on the GPU (no CPU path).
 `evaluate` computes all eight numbers in one launch; the per-metric functions call it with the lists
 they need.  The clash list (rows of cat(edge_list, nbr_list) occurring once) depends on the topology
 only and is cached per (edge_list, nbr_list) pair.
+
+`geometry_check` needs no true structure: generated structures against the template topology they were built from
+(broken / spurious covalent bonds, clashes; codlad_geometry_check, one all-pairs launch).
 """
 import ctypes as C
 
@@ -311,3 +314,102 @@ def compute_div(gen_structures, ref_structure):
     to_ref = [superposed_rmsd(g[p], ref[p]) for g in gen for p in range(g.shape[0])]
     to_mean = [superposed_rmsd(g[p], mean_gen[p]) for g in gen for p in range(g.shape[0])]
     return 1.0 - (sum(to_mean) / len(to_mean)) / (sum(to_ref) / len(to_ref))
+
+
+# --- Reference-free geometry check (codlad_geometry_check, csrc/geometry_kernels.hip): generated structures judged
+# against the template topology they were built from, with no true coordinates.
+
+GEOMETRY_COUNTS = ("broken", "spurious", "bonded", "near", "clash")
+
+
+def exclusion_csr(bonds, order, n_atoms):
+    """The pairs within `order` bonds (dataset_builder.high_order_edges' pair set) as the CSR codlad_geometry_check reads:
+    (ptr int32 [n_atoms + 1], partners int32) - row i lists, sorted, every j != i within `order` bonds of i (so the list
+    is symmetric), with _lib.GEOM_BOND_FLAG set on the bonded (order-1) ones.  Walks adjacency lists: no n x n matrix."""
+    adj = [set() for _ in range(n_atoms)]
+    for i, j in torch.as_tensor(bonds).reshape(-1, 2).tolist():
+        if not (0 <= i < n_atoms and 0 <= j < n_atoms) or i == j:
+            raise ValueError(f"bond ({i}, {j}) is not a pair of different atoms of [0, {n_atoms})")
+        adj[i].add(j)
+        adj[j].add(i)
+    ptr, words = [0], []
+    for i in range(n_atoms):
+        seen, frontier = {i}, {i}
+        for _ in range(order):
+            frontier = {k for f in frontier for k in adj[f]} - seen
+            seen |= frontier
+        seen.discard(i)
+        words += [j | _lib.GEOM_BOND_FLAG if j in adj[i] else j for j in sorted(seen)]
+        ptr.append(len(words))
+    return torch.tensor(ptr, dtype=torch.int32), torch.tensor(words, dtype=torch.int32)
+
+
+def _geometry_tables(top, order, dev):
+    """(radius, excl_ptr, excl, bonds) of a topology on `dev`, built once and kept ON the topology object (its lifetime,
+    no key that a reused address could alias)."""
+    cache = top.__dict__.setdefault("_geometry_tables", {})
+    key = (int(order), str(dev))
+    if key not in cache:
+        from .utils.dataset_builder import standard_bonds
+        z = torch.as_tensor(top.atomic_nums()).to(torch.int64)
+        if z.numel() and (int(z.min()) < 1 or int(z.max()) > len(COV_CUTOFF)):
+            raise ValueError("atomic number outside the covalent cut-off table (1..107)")
+        bonds = standard_bonds(top)
+        ptr, words = exclusion_csr(bonds, order, top.n_atoms)
+        cache[key] = (torch.tensor(COV_CUTOFF, dtype=torch.float32)[z - 1].to(dev).contiguous(), ptr.to(dev), words.to(dev),
+                      bonds.to(torch.int32).to(dev).contiguous())
+    return cache[key]
+
+
+def _geometry_launch(xyz, radius, ptr_, words, bonds, scale, clash_dist, near_dist):
+    _need_cuda(xyz, "xyz")
+    if xyz.dim() != 3 or xyz.shape[-1] != 3 or xyz.shape[0] == 0:
+        raise ValueError(f"geometry_check: xyz must be a non-empty [S, n_atoms, 3] tensor, got {tuple(xyz.shape)}")
+    if xyz.shape[1] != radius.shape[0] or ptr_.shape[0] != radius.shape[0] + 1:
+        raise ValueError(f"geometry_check: xyz has {xyz.shape[1]} atoms, the topology {radius.shape[0]}")
+    dev = xyz.device
+    x = xyz.detach().to(torch.float32).contiguous()
+    S = x.shape[0]
+    counts = torch.empty(S, 5, dtype=torch.int32, device=dev)
+    min_dist = torch.empty(S, dtype=torch.float32, device=dev)
+    rc = _lib.lib().codlad_geometry_check(_lib.ptr(x), S, x.shape[1], _lib.ptr(radius), _lib.ptr(ptr_), _lib.ptr(words),
+                                          _lib.ptr(bonds), bonds.shape[0], C.c_float(scale), C.c_float(clash_dist),
+                                          C.c_float(near_dist), _lib.ptr(counts), _lib.ptr(min_dist), _lib.stream_ptr(dev))
+    _lib.check(rc, "codlad_geometry_check")
+    out = {k: counts[:, c] for c, k in enumerate(GEOMETRY_COUNTS)}
+    out.update(counts=counts, min_dist=min_dist, valid=(counts[:, 0] == 0) & (counts[:, 1] == 0))
+    return out
+
+
+def geometry_check_lists(xyz, radius, bonds, order=2, scale=1.3, clash_dist=1.2, near_dist=9.0):
+    """geometry_check for a topology given as lists: radius [n_atoms] (covalent cut-off radii), bonds [n_bonds, 2] (each
+    bond once, i < j).  The exclusion list is rebuilt on every call: for repeated calls on a protein use geometry_check."""
+    _need_cuda(xyz, "xyz")
+    dev = xyz.device
+    bonds = torch.as_tensor(bonds).reshape(-1, 2).to(torch.int64).cpu()
+    if bonds.numel() and not bool((bonds[:, 0] < bonds[:, 1]).all()):
+        raise ValueError("geometry_check: bonds must be pairs i < j")
+    radius = torch.as_tensor(radius).detach().to(torch.float32).reshape(-1)
+    ptr_, words = exclusion_csr(bonds, order, radius.shape[0])
+    return _geometry_launch(xyz, radius.to(dev).contiguous(), ptr_.to(dev), words.to(dev),
+                            bonds.to(torch.int32).to(dev).contiguous(), scale, clash_dist, near_dist)
+
+
+def geometry_check(xyz, top, order=2, scale=1.3, clash_dist=1.2, near_dist=9.0):
+    """xyz [S, n_atoms, 3] (device): S structures of the topology `top` (a dataset_builder.Topology of the written, i.e.
+    interior, residues) -> dict of device tensors, one entry per structure, over unordered atom pairs:
+      broken    template bonds (standard_bonds) at d >= (r_i + r_j) * scale, r = COV_CUTOFF of the element
+      spurious  pairs at d < (r_i + r_j) * scale that are no template bond
+      bonded    all pairs at d < (r_i + r_j) * scale (= n_bonds - broken + spurious)
+      near      pairs more than `order` bonds apart at d <= near_dist
+      clash     of those, the ones at sqrt(d^2 + 1e-7) < clash_dist (clash / near: the first term of clash_result with
+                the structure's own neighbour list)
+      min_dist  the smallest d over pairs more than `order` bonds apart (inf: there is none)
+      valid     broken == 0 and spurious == 0: the covalent graph of the structure IS the template's
+    and `counts`, the five counts as one int32 [S, 5] in the order of GEOMETRY_COUNTS.  One launch, no host transfer."""
+    _need_cuda(xyz, "xyz")
+    if xyz.dim() == 3 and xyz.shape[1] != top.n_atoms:
+        raise ValueError(f"geometry_check: xyz has {xyz.shape[1]} atoms, the topology {top.n_atoms}")
+    if order < 1:
+        raise ValueError(f"geometry_check: order must be >= 1, got {order}")
+    return _geometry_launch(xyz, *_geometry_tables(top, order, xyz.device), scale, clash_dist, near_dist)

@@ -17,7 +17,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from .utils.ic_tables import core_atoms, atom_order_list
+from .utils.ic_tables import PDB_ATOM_ORDER, core_atoms, atom_order_list  # noqa: F401
 
 H = 128
 
@@ -25,31 +25,8 @@ H = 128
 IDX2THR = ['ASN', 'HIS', 'ALA', 'GLY', 'ARG', 'MET', 'SER', 'ILE', 'GLU', 'LEU', 'TYR',
            'ASP', 'VAL', 'TRP', 'GLN', 'LYS', 'PRO', 'PHE', 'CYS', 'THR', 'TPO', 'SEP']
 
-# heavy-atom order a PDB file lists per residue (what mdtraj's topology would give)
-PDB_ATOM_ORDER = {
-    'ALA': ['N', 'CA', 'C', 'O', 'CB'],
-    'ARG': ['N', 'CA', 'C', 'O', 'CB', 'CG', 'CD', 'NE', 'CZ', 'NH1', 'NH2'],
-    'ASP': ['N', 'CA', 'C', 'O', 'CB', 'CG', 'OD1', 'OD2'],
-    'ASN': ['N', 'CA', 'C', 'O', 'CB', 'CG', 'OD1', 'ND2'],
-    'CYS': ['N', 'CA', 'C', 'O', 'CB', 'SG'],
-    'GLU': ['N', 'CA', 'C', 'O', 'CB', 'CG', 'CD', 'OE1', 'OE2'],
-    'GLN': ['N', 'CA', 'C', 'O', 'CB', 'CG', 'CD', 'OE1', 'NE2'],
-    'GLY': ['N', 'CA', 'C', 'O'],
-    'HIS': ['N', 'CA', 'C', 'O', 'CB', 'CG', 'ND1', 'CD2', 'CE1', 'NE2'],
-    'ILE': ['N', 'CA', 'C', 'O', 'CB', 'CG1', 'CG2', 'CD1'],
-    'LEU': ['N', 'CA', 'C', 'O', 'CB', 'CG', 'CD1', 'CD2'],
-    'LYS': ['N', 'CA', 'C', 'O', 'CB', 'CG', 'CD', 'CE', 'NZ'],
-    'MET': ['N', 'CA', 'C', 'O', 'CB', 'CG', 'SD', 'CE'],
-    'PHE': ['N', 'CA', 'C', 'O', 'CB', 'CG', 'CD1', 'CD2', 'CE1', 'CE2', 'CZ'],
-    'PRO': ['N', 'CA', 'C', 'O', 'CB', 'CG', 'CD'],
-    'SER': ['N', 'CA', 'C', 'O', 'CB', 'OG'],
-    'THR': ['N', 'CA', 'C', 'O', 'CB', 'OG1', 'CG2'],
-    'TRP': ['N', 'CA', 'C', 'O', 'CB', 'CG', 'CD1', 'CD2', 'NE1', 'CE2', 'CE3', 'CZ2', 'CZ3', 'CH2'],
-    'TYR': ['N', 'CA', 'C', 'O', 'CB', 'CG', 'CD1', 'CD2', 'CE1', 'CE2', 'CZ', 'OH'],
-    'VAL': ['N', 'CA', 'C', 'O', 'CB', 'CG1', 'CG2'],
-    'TPO': ['N', 'CA', 'C', 'O', 'CB', 'OG1', 'CG2', 'P', 'OE1', 'OE2', 'OE3'],
-    'SEP': ['N', 'CA', 'C', 'O', 'CB', 'OG', 'P', 'OE1', 'OE2', 'OE3'],
-}
+# PDB_ATOM_ORDER (heavy-atom file order per residue) lives with the residue templates in utils/ic_tables.py; the name
+# stays importable from here
 
 
 def _rng(seed):

@@ -281,14 +281,15 @@ class CGDataset(torch.utils.data.Dataset):
         self.props = props
 
     def __len__(self):
-        return len(self.props["nxyz"])
+        return len(self.props["nxyz" if "nxyz" in self.props else "CG_nxyz"])      # CA-only input has no atoms
 
     def __getitem__(self, idx):
         return {key: val[idx] for key, val in self.props.items()}
 
     def generate_neighbor_list(self, atom_cutoff, cg_cutoff, device="cpu"):
         """protein_module.py:651-691 (undirected, cut-off form)."""
-        self.props["nbr_list"] = [neighbor_list(nxyz[:, 1:4].to(device), atom_cutoff).cpu() for nxyz in self.props["nxyz"]]
+        if "nxyz" in self.props:
+            self.props["nbr_list"] = [neighbor_list(nxyz[:, 1:4].to(device), atom_cutoff).cpu() for nxyz in self.props["nxyz"]]
         self.props["CG_nbr_list"] = [neighbor_list(nxyz[:, 1:4].to(device), cg_cutoff).cpu()
                                      for nxyz in self.props["CG_nxyz"]]
 

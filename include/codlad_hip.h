@@ -800,6 +800,30 @@ int codlad_ens_apply(const float *x, const double *Rt, int n_conf, int n_atoms, 
 int codlad_ens_pairwise(const float *x, const double *mom, int G, int F, int n_atoms, const int32_t *sel, int n_sel,
                         int squared, double *out, void *stream);
 
+/* Reference-free geometry check (csrc/geometry_kernels.hip): n_struct structures xyz [n_struct][n_atoms][3] that share ONE
+ * topology are judged against that topology's template bond graph, with no true coordinates.  Added to ABI version 19
+ * without changing the number: one new entry point, no existing signature, struct or option changes.
+ * radius [n_atoms]: the covalent cut-off radius of each atom's element (as for codlad_bond_graph_counts).  excl_ptr
+ * [n_atoms + 1], excl: CSR of the exclusion list - row i holds, sorted by index, every atom j != i within `order` bonds of
+ * i (both directions: j's row holds i), as j, or j | CODLAD_GEOM_BOND_FLAG when j is bonded to i (order 1).  bonds
+ * [n_bonds][2]: the template bonds, each once, i < j.  Entries out of [0, n_atoms) are skipped; excl_ptr must be a valid
+ * non-decreasing offset table into excl (it is not checked on the device).  n_atoms <= 65536.
+ * With d = sqrtf((dx*dx + dy*dy) + dz*dz) in unfused fp32, over unordered pairs i < j of one structure:
+ *   counts[0] broken   template bonds with d >= (r_i + r_j) * scale
+ *   counts[1] spurious pairs with d < (r_i + r_j) * scale that are not flagged order-1 partners
+ *   counts[2] bonded   all pairs with d < (r_i + r_j) * scale      (== n_bonds - broken + spurious when the flags of the
+ *                                                                   CSR and the bond list describe the same graph)
+ *   counts[3] near     pairs not in the exclusion list with d <= near_dist
+ *   counts[4] clash    pairs not in the exclusion list with sqrtf(((dx*dx + dy*dy) + dz*dz) + 1e-7f) < clash_dist
+ *                      (the root of the clash term of the evaluation metrics above)
+ *   min_dist           the smallest d over pairs not in the exclusion list, +inf if there is none
+ * counts int32 [n_struct][5], min_dist float [n_struct] (device).  Integer atomics and an integer minimum only: results are
+ * bit-identical from call to call and a structure's row does not depend on the other structures of the call. */
+#define CODLAD_GEOM_BOND_FLAG (1 << 30)
+int codlad_geometry_check(const float *xyz, int n_struct, int n_atoms, const float *radius, const int32_t *excl_ptr,
+                          const int32_t *excl, const int32_t *bonds, int n_bonds, float scale, float clash_dist,
+                          float near_dist, int32_t *counts, float *min_dist, void *stream);
+
 /* Self-test of the MFMA chain primitive: Y[n][:] = act(W @ X[n][:] + bias), n < 32*tiles.
  * act: 0 = none, 1 = exact-erf GELU. */
 int codlad_selftest_gemm128(const float *W_packed, const float *bias, const float *X, int n_rows,

@@ -29,6 +29,11 @@ Addition: `--experiment fmloss` scores a flow-matching checkpoint (--model fm / 
 validation pass does (train_latent.py:338-350: the matcher's path, the model, loss_fn), at the K = --num_steps times
 (k + 0.5) / K, one fused sweep per batch: x1 = the batch's own VQ-VAE latents, x0 and the path's noise from the run's seed;
 prints the mean --loss per file and per time and saves the per-sample table [N, K] as .npy.  One rank only.
+Addition: `--cg_pdb ca.pdb ... [--cg_xtc traj.xtc]` backmaps a CA-only (coarse-grained) trajectory: the sequence and the CA
+frames are all the input there is (utils/cg_input.py), the atoms written are the residue templates'.  The chain loses its
+first and last residue, which supply only the flanking CAs (as on every route).  With no true atoms there is no Evaluation
+block; instead `--geometry_check` (implied by --cg_pdb, available on every route whose topology is known) judges every
+generated structure against its template topology on the device (metrics.geometry_check): broken / spurious bonds, clashes.
 """
 import argparse
 import os
@@ -116,6 +121,42 @@ def check_fix_residues(args):
         return parse_fix_residues(args.fix_residues)
     except ValueError as e:
         raise SystemExit(str(e))
+
+
+CG_NEEDS_ATOMS = {"recon": "encodes the input's atoms", "genzprot": "is evaluated against the input's atoms",
+                  "bpd": "scores the latents of the input's atoms", "fmloss": "scores the latents of the input's atoms"}
+
+
+def check_cg_input(args):
+    """Where --cg_pdb / --cg_xtc / --geometry_check apply.  A CA-only input has no atoms: it feeds latent sampling (every
+    sampler, every flow model) and nothing that encodes, pins or compares with atoms.  Sets args.geometry_check (implied by
+    --cg_pdb) and returns it."""
+    cg, xtc = getattr(args, "cg_pdb", None), getattr(args, "cg_xtc", None)
+    want = bool(getattr(args, "geometry_check", False)) or bool(cg)
+    if xtc and not cg:
+        raise SystemExit("--cg_xtc needs --cg_pdb: the PDB file supplies the sequence of the trajectory's CA beads")
+    if xtc and len(cg) != 1:
+        raise SystemExit(f"--cg_xtc goes with a single --cg_pdb file (the sequence of that trajectory), not {len(cg)}")
+    if cg:
+        if args.synthetic or getattr(args, "pdb_files", None) or args.data_process:
+            raise SystemExit("--cg_pdb is an input route of its own: not together with --pdb_files, --data_process or --synthetic")
+        if args.experiment != "latent":
+            raise SystemExit(f"--cg_pdb needs --experiment latent: {args.experiment!r} "
+                             f"{CG_NEEDS_ATOMS.get(args.experiment, 'needs atoms')}, and a CA-only input has none")
+        if getattr(args, "fix_residues", None) is not None:
+            raise SystemExit("--cg_pdb cannot be combined with --fix_residues: the pinned latents are encoded from the input's "
+                             "atoms, and a CA-only input has none")
+        if getattr(args, "superpose", "none") == "ref":
+            raise SystemExit("--cg_pdb cannot be combined with --superpose ref: there is no true structure to superpose on "
+                             "(use --superpose first)")
+    elif want:
+        if args.experiment in ("bpd", "fmloss"):
+            raise SystemExit(f"--geometry_check judges generated structures: --experiment {args.experiment} generates none")
+        if args.data_process and not args.synthetic:
+            raise SystemExit("--geometry_check needs the topology of the structures: --data_process pickles carry none "
+                             "(use --pdb_files, --cg_pdb or --synthetic)")
+    args.geometry_check = want
+    return want
 
 
 def check_sampler(args):
@@ -235,6 +276,7 @@ def load_cvae(args, device, load=True):
 
 
 _TOPOLOGY = {}                     # output name -> (residue names, atom names per residue) where known (--save_pdb)
+_GEOMETRY_TOP = {}                 # output name -> Topology of the written (interior) residues (--geometry_check)
 MAX_FRAMES_PER_BATCH = 96          # reference utils/dataset_module.py:220-226: batch_size = min(n_frames, 96)
 
 
@@ -260,9 +302,15 @@ def iter_batches(args):
                                       phospho=args.vae_type != "N6")
             plan = chunk_plan(args.synthetic_frames)
             names = [synth.IDX2THR[int(z)] for z in prot["z_full"]]
+            geom_top = None
+            if getattr(args, "geometry_check", False):
+                from codlad_amd.utils.cg_input import template_topology
+                geom_top = template_topology(names[1:-1])             # one Topology (and one set of device tables) per protein
             for c, (a, b) in enumerate(plan):
                 out = output_name(f"synthetic_L{L}", c, len(plan))
                 _TOPOLOGY[out] = (names, [synth.PDB_ATOM_ORDER[nm] for nm in names])
+                if geom_top is not None:
+                    _GEOMETRY_TOP[out] = geom_top
                 batch = synth.make_batch(prot, range(a, b))
                 # the encoder reads the all-atom side of the batch (recon; the known latents of --fix_residues)
                 if getattr(args, "experiment", "latent") in ("recon", "bpd", "fmloss") or getattr(args, "fix_residues", None) is not None:
@@ -282,7 +330,28 @@ def iter_batches(args):
             for c, batch in enumerate(loader):
                 out = output_name(os.path.basename(stem), c, n_batches)
                 _TOPOLOGY[out] = (["GLY"] + top.res_names + ["GLY"], [["CA"]] + top.atom_names + [["CA"]])
+                _GEOMETRY_TOP[out] = top
                 yield out, batch, info_dict[0]
+        return
+    if getattr(args, "cg_pdb", None):
+        # a CA-only trajectory: sequence + CA frames -> template topology -> the batch keys of the latent path, built as
+        # load_dataset builds them from atoms (utils/cg_input.py); one Topology per file, shared by its batches
+        from codlad_amd.utils.cg_input import cg_batches, load_cg_frames, template_topology
+        params = {"atom_cutoff": args.atom_cutoff, "cg_cutoff": args.cg_cutoff, "edgeorder": args.edgeorder}
+        for path in args.cg_pdb:
+            stem = os.path.basename(path[:-4] if path.endswith(".pdb") else path)
+            try:
+                seq, ca_xyz = load_cg_frames(path, getattr(args, "cg_xtc", None))
+                top = template_topology(*seq)
+            except ValueError as e:
+                raise SystemExit(f"--cg_pdb: {e}")
+            inner = top.subset_residues(1, top.n_residues - 1)
+            units = list(cg_batches(top, ca_xyz, params, device="cuda"))
+            for c, (batch, info) in enumerate(units):
+                out = output_name(stem, c, len(units))
+                _TOPOLOGY[out] = (top.res_names, top.atom_names)
+                _GEOMETRY_TOP[out] = inner
+                yield out, batch, info
         return
     if not args.data_process:
         raise SystemExit("xtc loading is not built: use --pdb_files (multi-model PDB), --data_process --data_files ... or --synthetic")
@@ -337,6 +406,23 @@ class Evaluation:
             print(k, v)
         print("############## ^^^^^^^^^ result test_stats:")
         return stats
+
+
+def geometry_report(name, geo, n_atoms):
+    """The printed summary of --geometry_check for one output file (geo: metrics.geometry_check's dict) -> the stats."""
+    c = geo["counts"].to(torch.float64)
+    near = c[:, 3]
+    ratio = torch.where(near > 0, c[:, 4] / near.clamp(min=1), torch.zeros_like(near))
+    stats = {"data_name": name, "structures": int(c.shape[0]), "atoms": int(n_atoms),
+             "geometry_valid_ratio": float(geo["valid"].to(torch.float64).mean()),
+             "geometry_broken_bonds": float(c[:, 0].mean()), "geometry_spurious_bonds": float(c[:, 1].mean()),
+             "geometry_clashes": float(c[:, 4].mean()), "geometry_clash_over_near": float(ratio.mean()),
+             "geometry_min_dist": float(geo["min_dist"].min())}
+    print("############## vvvvvvvvv geometry check (template topology, no true structure):")
+    for k, v in stats.items():
+        print(k, v)
+    print("############## ^^^^^^^^^ geometry check")
+    return stats
 
 
 def ca_indices(topology):
@@ -398,6 +484,7 @@ def run_sampling(model, args, x, mask=None, batch=None):
 
 
 def main(args):
+    check_cg_input(args)
     check_sampler(args)
     if not torch.cuda.is_available():
         raise SystemExit("test.py (codlad_amd) needs an MI355X: there is no CPU path")
@@ -562,12 +649,23 @@ def main(args):
             if evaluation is not None:                               # reference test.py:589-594, per ensemble member
                 evaluation.add(batch, ic_recon, xyz_all[-1], xyz_all[-1].shape[1])
         xyz = torch.stack(xyz_all)                                   # [E, B, n_atoms, 3]
+        geo = None
+        if args.geometry_check:
+            if name not in _GEOMETRY_TOP:
+                raise SystemExit(f"--geometry_check: the topology of {name} is not known on this input route")
+            # every member of every frame against the template bond graph: one launch, read back after the one sync below
+            geo = metrics.geometry_check(xyz.reshape(-1, xyz.shape[2], 3), _GEOMETRY_TOP[name], order=args.edgeorder,
+                                         near_dist=args.atom_cutoff)
         torch.cuda.synchronize()
         dt = time.time() - st
         total += B * E
         if evaluation is not None:
             evaluation.report(name, args)
         np.save(os.path.join(save_dir, f"{name}_xyz_recon.npy"), xyz.cpu().numpy())
+        if geo is not None:
+            np.save(os.path.join(save_dir, f"{name}_geometry.npy"), geo["counts"].cpu().numpy())        # [E * B, 5]
+            np.save(os.path.join(save_dir, f"{name}_geometry_min.npy"), geo["min_dist"].cpu().numpy())
+            geometry_report(name, geo, xyz.shape[2])
         if getattr(args, "save_pdb", False) and name in _TOPOLOGY:
             # reference test.py:787-796 writes the generated ensemble through mdtraj (.xtc + .pdb); here both directly, frames
             # of member 0 first (multi-model PDB in Angstrom, .xtc in nm as the format has it)
@@ -652,6 +750,18 @@ if __name__ == "__main__":
     p.add_argument("--save_codes", action="store_true", help="also save the VQ code index of every residue, [structures, L] (VQ-VAE decoders)")
     p.add_argument("--pdb_files", nargs="*", default=None,
                    help="multi-model PDB ensembles to build the test set from (the reference's load_dataset, without mdtraj)")
+    p.add_argument("--cg_pdb", nargs="+", default=None, metavar="FILE",
+                   help="backmap CA-only (coarse-grained) input: multi-model PDB files of which only the CA records are read "
+                        "(sequence + CA frames; the atoms written are the residue templates').  The chain loses its first and "
+                        "last residue: they supply only the flanking CAs.  --experiment latent only; implies --geometry_check")
+    p.add_argument("--cg_xtc", default=None, metavar="FILE",
+                   help="with a single --cg_pdb: take the CA frames from this .xtc (one atom per CA of the PDB file, which then "
+                        "supplies the sequence only)")
+    p.add_argument("--geometry_check", action="store_true",
+                   help="judge every generated structure against its template topology, with no true structure (broken and "
+                        "spurious covalent bonds, clashes, smallest non-bonded distance): saves <name>_geometry.npy "
+                        "[structures, 5] = broken, spurious, bonded, near, clash and <name>_geometry_min.npy, prints a summary. "
+                        "'valid' is a statement about geometry, not about accuracy")
     p.add_argument("--atom_cutoff", type=float, default=9.0)
     p.add_argument("--cg_cutoff", type=float, default=21.0)
     p.add_argument("--edgeorder", type=int, default=2)
