@@ -120,6 +120,8 @@ FM_KINDS = {"icfm": 0, "target": 1, "vp": 2}           # CODLAD_FM_* of include/
 FM_TARGET_FLOW = 3                                     # CODLAD_FM_TARGET_FLOW: the target matcher's flow of a given xt
 ODE_METHODS = {"euler": 0, "midpoint": 1, "rk4": 2}    # CODLAD_ODE_* of include/codlad_hip.h
 GEOM_BOND_FLAG = 1 << 30                               # CODLAD_GEOM_BOND_FLAG: an order-1 partner in the exclusion CSR
+STEREO_COLUMNS, STEREO_N_COUNTS, STEREO_KIND_PRO = 9, 6, 1   # CODLAD_STEREO_COLUMNS, _COUNTS, _KIND_PRO
+STEREO_FLAGS = {"inverted_ca": 1, "inverted_side": 2, "cis": 4, "twisted": 8, "undefined": 16}   # CODLAD_STEREO_* flag bits
 ODE_NORM_WORDS = 257                                   # CODLAD_ODE_NORM_WORDS
 
 _JOB = [C.POINTER(DenoiserWeights), C.POINTER(JobDesc)]    # what every entry point that runs the denoiser starts with
@@ -136,6 +138,7 @@ _SIGS = {
     "codlad_ens_apply": (C.c_int, [P, P, C.c_int, C.c_int, P, P]),
     "codlad_ens_pairwise": (C.c_int, [P, P, C.c_int, C.c_int, C.c_int, P, C.c_int, C.c_int, P, P]),
     "codlad_geometry_check": (C.c_int, [P, C.c_int, C.c_int, P, P, P, P, C.c_int, C.c_float, C.c_float, C.c_float, P, P, P]),
+    "codlad_stereo_check": (C.c_int, [P, C.c_int, C.c_int, P, P, C.c_int, P, P, P, P]),
     "codlad_last_error": (C.c_char_p, []),
     "codlad_struct_sizes": (None, [C.POINTER(C.c_int)]),
     "codlad_pack_block_host": (None, [P, C.c_int, C.c_float, P]),

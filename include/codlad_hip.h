@@ -824,6 +824,43 @@ int codlad_geometry_check(const float *xyz, int n_struct, int n_atoms, const flo
                           const int32_t *excl, const int32_t *bonds, int n_bonds, float scale, float clash_dist,
                           float near_dist, int32_t *counts, float *min_dist, void *stream);
 
+/* Stereochemistry check (csrc/stereo_kernels.hip): per residue of n_struct structures xyz [n_struct][n_atoms][3] that share
+ * ONE topology, nine quantities, the decisions taken on them and their counts per structure; no true coordinates.  Added to
+ * ABI version 19 without changing the number: one new entry point, no existing signature, struct or option changes.
+ * sites int32 [n_res][9][4] (16-byte aligned): the four atoms p0..p3 of each quantity of each residue; a quantity with an
+ * index < 0 or >= n_atoms is ABSENT: nothing is read for it, its value is NaN and it sets no flag.  res_kind uint8 [n_res]:
+ * bit 0 (CODLAD_STEREO_KIND_PRO) = the residue is a proline.  Columns (atoms in the order of sites, i = the residue, i-1 /
+ * i+1 its neighbours in the same chain):
+ *   0 phi       C(i-1), N, CA, C          3 .. 6 chi1 .. chi4 (side chain, by residue type)
+ *   1 psi       N, CA, C, N(i+1)          7 v_ca    CA, N, C, CB              = (N - CA) . ((C - CA) x (CB - CA))
+ *   2 omega_in  CA(i-1), C(i-1), N, CA    8 v_side  CB, CA, OG1 | CG1, CG2    = (CA - CB) . ((X - CB) x (CG2 - CB))
+ * Arithmetic, fp32 with one rounding per operation (no contraction), a - b and a x b per component,
+ * cross(a, b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x), dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z:
+ *   columns 0 .. 6, degrees in (-180, 180], IUPAC sign: b1 = p1 - p0, b2 = p2 - p1, b3 = p3 - p2, n1 = cross(b1, b2),
+ *     n2 = cross(b2, b3), x = dot(n1, n2), y = dot(cross(n1, n2), b2) / sqrtf(dot(b2, b2)),
+ *     value = atan2f(y, x) * (float)(180 / pi), -180 written as 180; NaN where x == 0 and y == 0 (coincident or exactly
+ *     collinear atoms: there is no angle).  p = (1,0,0), (0,0,0), (0,0,1), (0,1,1) gives +90.
+ *   columns 7, 8, A^3: dot(p1 - p0, cross(p2 - p0, p3 - p0)).  An L residue has v_ca > 0 (+2.509 for ideal geometry), natural
+ *     (2S,3R)-THR and (2S,3S)-ILE have v_side > 0.
+ * values float [n_struct][n_res][9].  flags uint8 [n_struct][n_res]:
+ *   CODLAD_STEREO_INVERTED_CA    v_ca is finite and not > 0         CODLAD_STEREO_CIS      |omega_in| < 30
+ *   CODLAD_STEREO_INVERTED_SIDE  v_side is finite and not > 0       CODLAD_STEREO_TWISTED  30 <= |omega_in| <= 150
+ *   CODLAD_STEREO_UNDEFINED      a quantity that is not absent came out non-finite (a NaN / inf coordinate, no angle)
+ * counts int32 [n_struct][6] = residues with inverted_ca, inverted_side, cis and PRO, cis and not PRO, twisted, undefined:
+ * integer sums per workgroup and integer atomics on a table the call zeroes first, so results are bit-identical from call
+ * to call and a structure's rows do not depend on the other structures of the call.  All pointers are device pointers;
+ * a null pointer, n_struct <= 0, n_res <= 0 or n_atoms <= 0 returns -1 (codlad_last_error) before any launch. */
+#define CODLAD_STEREO_COLUMNS 9
+#define CODLAD_STEREO_COUNTS 6
+#define CODLAD_STEREO_KIND_PRO 1
+#define CODLAD_STEREO_INVERTED_CA 1
+#define CODLAD_STEREO_INVERTED_SIDE 2
+#define CODLAD_STEREO_CIS 4
+#define CODLAD_STEREO_TWISTED 8
+#define CODLAD_STEREO_UNDEFINED 16
+int codlad_stereo_check(const float *xyz, int n_struct, int n_atoms, const int32_t *sites, const uint8_t *res_kind,
+                        int n_res, float *values, uint8_t *flags, int32_t *counts, void *stream);
+
 /* Self-test of the MFMA chain primitive: Y[n][:] = act(W @ X[n][:] + bias), n < 32*tiles.
  * act: 0 = none, 1 = exact-erf GELU. */
 int codlad_selftest_gemm128(const float *W_packed, const float *bias, const float *X, int n_rows,

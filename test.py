@@ -34,6 +34,8 @@ frames are all the input there is (utils/cg_input.py), the atoms written are the
 first and last residue, which supply only the flanking CAs (as on every route).  With no true atoms there is no Evaluation
 block; instead `--geometry_check` (implied by --cg_pdb, available on every route whose topology is known) judges every
 generated structure against its template topology on the device (metrics.geometry_check): broken / spurious bonds, clashes.
+Addition: `--stereo_check` (opt-in, wherever --geometry_check is allowed) adds what the covalent graph cannot see
+(metrics.stereo_check): inverted CA / CB centres, cis and twisted peptide bonds, and the phi / psi / omega / chi table.
 """
 import argparse
 import os
@@ -156,6 +158,20 @@ def check_cg_input(args):
             raise SystemExit("--geometry_check needs the topology of the structures: --data_process pickles carry none "
                              "(use --pdb_files, --cg_pdb or --synthetic)")
     args.geometry_check = want
+    return want
+
+
+def check_stereo(args):
+    """Where --stereo_check applies: exactly where --geometry_check does - structures are generated and their topology is
+    known.  (The refusals of --cg_pdb itself are check_cg_input's.)  Returns whether it is on."""
+    want = bool(getattr(args, "stereo_check", False))
+    if want and not getattr(args, "cg_pdb", None):
+        if args.experiment in ("bpd", "fmloss"):
+            raise SystemExit(f"--stereo_check judges generated structures: --experiment {args.experiment} generates none")
+        if args.data_process and not args.synthetic:
+            raise SystemExit("--stereo_check needs the topology of the structures: --data_process pickles carry none "
+                             "(use --pdb_files, --cg_pdb or --synthetic)")
+    args.stereo_check = want
     return want
 
 
@@ -303,7 +319,7 @@ def iter_batches(args):
             plan = chunk_plan(args.synthetic_frames)
             names = [synth.IDX2THR[int(z)] for z in prot["z_full"]]
             geom_top = None
-            if getattr(args, "geometry_check", False):
+            if getattr(args, "geometry_check", False) or getattr(args, "stereo_check", False):
                 from codlad_amd.utils.cg_input import template_topology
                 geom_top = template_topology(names[1:-1])             # one Topology (and one set of device tables) per protein
             for c, (a, b) in enumerate(plan):
@@ -425,6 +441,23 @@ def geometry_report(name, geo, n_atoms):
     return stats
 
 
+def stereo_report(name, ste):
+    """The printed summary of --stereo_check for one output file (ste: metrics.stereo_check's dict) -> the stats."""
+    c = ste["counts"].to(torch.int64)
+    bad = c.sum(1) - c[:, metrics.STEREO_COUNTS.index("cis_pro")]                # what fails stereo_ok, per structure
+    worst = int(bad.argmax())
+    stats = {"data_name": name, "structures": int(c.shape[0]), "residues": int(ste["flags"].shape[1]),
+             "stereo_ok_ratio": float(ste["stereo_ok"].to(torch.float64).mean())}
+    stats.update({f"stereo_total_{k}": int(c[:, i].sum()) for i, k in enumerate(metrics.STEREO_COUNTS)})
+    stats["stereo_worst_structure"] = worst
+    stats["stereo_worst_counts"] = " ".join(f"{k}={int(c[worst, i])}" for i, k in enumerate(metrics.STEREO_COUNTS))
+    print("############## vvvvvvvvv stereo check (chirality, peptide bonds; geometry, not accuracy):")
+    for k, v in stats.items():
+        print(k, v)
+    print("############## ^^^^^^^^^ stereo check")
+    return stats
+
+
 def ca_indices(topology):
     """Positions of the CA atoms among the written atoms of a (residue names, atom names per residue) topology (the
     flanking residues are not written, protein_module.write_pdb)."""
@@ -485,6 +518,7 @@ def run_sampling(model, args, x, mask=None, batch=None):
 
 def main(args):
     check_cg_input(args)
+    check_stereo(args)
     check_sampler(args)
     if not torch.cuda.is_available():
         raise SystemExit("test.py (codlad_amd) needs an MI355X: there is no CPU path")
@@ -656,6 +690,11 @@ def main(args):
             # every member of every frame against the template bond graph: one launch, read back after the one sync below
             geo = metrics.geometry_check(xyz.reshape(-1, xyz.shape[2], 3), _GEOMETRY_TOP[name], order=args.edgeorder,
                                          near_dist=args.atom_cutoff)
+        ste = None
+        if args.stereo_check:
+            if name not in _GEOMETRY_TOP:
+                raise SystemExit(f"--stereo_check: the topology of {name} is not known on this input route")
+            ste = metrics.stereo_check(xyz.reshape(-1, xyz.shape[2], 3), _GEOMETRY_TOP[name])      # one launch, as above
         torch.cuda.synchronize()
         dt = time.time() - st
         total += B * E
@@ -666,6 +705,11 @@ def main(args):
             np.save(os.path.join(save_dir, f"{name}_geometry.npy"), geo["counts"].cpu().numpy())        # [E * B, 5]
             np.save(os.path.join(save_dir, f"{name}_geometry_min.npy"), geo["min_dist"].cpu().numpy())
             geometry_report(name, geo, xyz.shape[2])
+        if ste is not None:
+            np.save(os.path.join(save_dir, f"{name}_stereo.npy"), ste["counts"].cpu().numpy())          # [E * B, 6]
+            np.save(os.path.join(save_dir, f"{name}_stereo_flags.npy"), ste["flags"].cpu().numpy())     # [E * B, R]
+            np.save(os.path.join(save_dir, f"{name}_torsions.npy"), ste["values"].cpu().numpy())        # [E * B, R, 9]
+            stereo_report(name, ste)
         if getattr(args, "save_pdb", False) and name in _TOPOLOGY:
             # reference test.py:787-796 writes the generated ensemble through mdtraj (.xtc + .pdb); here both directly, frames
             # of member 0 first (multi-model PDB in Angstrom, .xtc in nm as the format has it)
@@ -762,6 +806,12 @@ if __name__ == "__main__":
                         "spurious covalent bonds, clashes, smallest non-bonded distance): saves <name>_geometry.npy "
                         "[structures, 5] = broken, spurious, bonded, near, clash and <name>_geometry_min.npy, prints a summary. "
                         "'valid' is a statement about geometry, not about accuracy")
+    p.add_argument("--stereo_check", action="store_true",
+                   help="also judge the stereochemistry of every generated structure (allowed wherever --geometry_check is): "
+                        "saves <name>_stereo.npy [structures, 6] = inverted_ca, inverted_side, cis_pro, cis_nonpro, twisted, "
+                        "undefined (residues), <name>_stereo_flags.npy [structures, residues] and <name>_torsions.npy "
+                        "[structures, residues, 9] = phi, psi, omega, chi1-4 (degrees), v_ca, v_side (A^3); prints a summary. "
+                        "Geometry, not accuracy")
     p.add_argument("--atom_cutoff", type=float, default=9.0)
     p.add_argument("--cg_cutoff", type=float, default=21.0)
     p.add_argument("--edgeorder", type=int, default=2)
