@@ -139,6 +139,11 @@ _SIGS = {
     "codlad_ens_pairwise": (C.c_int, [P, P, C.c_int, C.c_int, C.c_int, P, C.c_int, C.c_int, P, P]),
     "codlad_geometry_check": (C.c_int, [P, C.c_int, C.c_int, P, P, P, P, C.c_int, C.c_float, C.c_float, C.c_float, P, P, P]),
     "codlad_stereo_check": (C.c_int, [P, C.c_int, C.c_int, P, P, C.c_int, P, P, P, P]),
+    "codlad_relax_scratch_bytes": (C.c_longlong, [C.c_int] * 5),
+    "codlad_relax_energy": (C.c_int, [P, P, C.c_int, C.c_int, P, P, P, P, P, P, C.c_int, P, C.c_int, P, P, C.c_int] +
+                            [C.c_float] * 4 + [P] * 5),
+    "codlad_relax": (C.c_int, [P, C.c_int, C.c_int, P, P, P, P, P, P, C.c_int, P, C.c_int, P, P, C.c_int] +
+                     [C.c_float] * 6 + [C.c_int] + [P] * 9),
     "codlad_last_error": (C.c_char_p, []),
     "codlad_struct_sizes": (None, [C.POINTER(C.c_int)]),
     "codlad_pack_block_host": (None, [P, C.c_int, C.c_float, P]),

@@ -861,6 +861,63 @@ int codlad_geometry_check(const float *xyz, int n_struct, int n_atoms, const flo
 int codlad_stereo_check(const float *xyz, int n_struct, int n_atoms, const int32_t *sites, const uint8_t *res_kind,
                         int n_res, float *values, uint8_t *flags, int32_t *counts, void *stream);
 
+/* Restrained clash relaxation (csrc/relax_kernels.hip): pushes overlapping atoms of n_struct structures xyz
+ * [n_struct][n_atoms][3] that share ONE topology apart while holding their covalent geometry to what a START structure
+ * has.  Added to ABI version 19 without changing the number: three new entry points, no existing signature, struct or
+ * option changes.  fp32 coordinates in A, one rounding per operation (no contraction), d_ij = sqrtf(((dx*dx + dy*dy) +
+ * dz*dz) + 1e-7f) everywhere, so coincident atoms have a gradient.
+ * Topology tables (device): radius [n_atoms] covalent cut-off radii; fixed uint8 [n_atoms] (non-zero: the atom does not
+ * move); excl_ptr / excl: the exclusion CSR of codlad_geometry_check (pairs within `order` bonds: never repelled);
+ * pair_ptr [n_atoms + 1] / pair_j [n_pairs]: the restrained pairs as a CSR of the same form (symmetric, sorted, flag bit
+ * ignored; normally the pairs within 2 bonds); quads int32 [n_quads][4] (16-byte aligned): the atoms a, b, c, d of every
+ * restrained torsion; quad_ptr [n_atoms + 1] / quad_ref [n_refs]: per atom the quads it is part of, as 4 * quad + position.
+ * Entries out of range are skipped (a quad with one: weight 0); the offset tables must be non-decreasing.
+ * Energy of one structure against the start structure xyz0 (d0, phi0 = its distances and torsions):
+ *   energy[0] distance  sum over restrained pairs i < j of k_r * (d - d0)^2
+ *   energy[1] torsion   sum over quads of k_t * w * (1 - cos * cos0 - sin * sin0), evaluated as k_t * w * (0.5f * (dc*dc + ds*ds)),
+ *                       dc = cos - cos0, ds = sin - sin0 (the same function of two unit vectors; exactly 0 at the start
+ *                       structure, no cancellation near it); (cos, sin) = (x, y) / sqrtf(x*x + y*y),
+ *                       b1 = b - a, b2 = c - b, b3 = d - c, n1 = b1 x b2, n2 = b2 x b3, x = n1 . n2, y = |b2| * (b1 . n2) (the
+ *                       IUPAC torsion, no atan2f); w = 0 where a bond angle of the quad has |sin| < 0.1 IN xyz0, else 1:
+ *                       decided once, so the energy is one fixed function for a whole relaxation
+ *   energy[2] repulsion sum over pairs i < j NOT in the exclusion list with d < sigma = (r_i + r_j) * contact_scale of
+ *                       k_c * (sigma - d)^2
+ * Terms are fp32, their sums float64: per thread, a fixed tree per workgroup of 256 atoms, the workgroups of a structure in
+ * ascending order.  grad [n_struct][n_atoms][3]: each atom gathers its own gradient in fp32 (repulsion over ascending j,
+ * then its pairs, then its quads; no floating-point atomics), fixed atoms 0.  gmax [n_struct] = max |grad component| (an
+ * integer maximum on the bit pattern).  Results are bit-identical from call to call and independent of the batch.
+ * scratch: codlad_relax_scratch_bytes(n_struct, n_atoms, n_pairs, n_quads, n_iter) bytes of device memory, 8-byte aligned,
+ * n_iter = -1 for codlad_relax_energy; every part is written before it is read. */
+long long codlad_relax_scratch_bytes(int n_struct, int n_atoms, int n_pairs, int n_quads, int n_iter);
+/* One evaluation: energy float64 [n_struct][3], grad float [n_struct][n_atoms][3], gmax float [n_struct].  xyz0 may be xyz.
+ * A null pointer, a count <= 0 (n_pairs, n_quads, n_refs: < 0), a force constant or contact_scale <= 0 or n_atoms > 65536
+ * returns -1 (codlad_last_error) before any launch. */
+int codlad_relax_energy(const float *xyz, const float *xyz0, int n_struct, int n_atoms, const float *radius,
+                        const uint8_t *fixed, const int32_t *excl_ptr, const int32_t *excl, const int32_t *pair_ptr,
+                        const int32_t *pair_j, int n_pairs, const int32_t *quads, int n_quads, const int32_t *quad_ptr,
+                        const int32_t *quad_ref, int n_refs, float k_r, float k_t, float k_c, float contact_scale,
+                        double *energy, float *grad, float *gmax, void *scratch, void *stream);
+/* Steepest descent from xyz (which is also the start structure), per structure, exactly n_iter iterations, all state on
+ * the device, two launches per iteration on `stream`, no host synchronisation.  h = h0, E and g at the input; iteration t:
+ *   gmax = max |g component|; gmax == 0: the trial is the state itself (never accepted), the structure is `converged`
+ *   x' = x - fl32(h / gmax) * g  (one multiply, one subtract);  E(x') < E(x): accept, h = min(h * 1.2f, h_max);
+ *   otherwise keep x, h = h * 0.5f.
+ * The evaluations are codlad_relax_energy's, bit for bit.  xyz_out [n_struct][n_atoms][3] (not xyz itself): the accepted
+ * state after the last iteration; fixed atoms return their input bits.  Trace (device):
+ *   trace_energy float64 [n_struct][n_iter + 1]   total energy of the accepted state, column 0 = the input
+ *   trace_trial_energy float64 [n_struct][n_iter] E(x') of iteration t
+ *   trace_step float [n_struct][n_iter]           the h iteration t used       trace_gmax: the gmax it used
+ *   trace_accepted uint8 [n_struct][n_iter]       trial_energy[t] < energy[t]
+ *   converged uint8 [n_struct]                    gmax of the final state == 0
+ * The four [n_iter] tables may be null when n_iter == 0.  Beyond codlad_relax_energy's checks: n_iter < 0, h0 <= 0 or
+ * h_max <= 0 returns -1. */
+int codlad_relax(const float *xyz, int n_struct, int n_atoms, const float *radius, const uint8_t *fixed,
+                 const int32_t *excl_ptr, const int32_t *excl, const int32_t *pair_ptr, const int32_t *pair_j, int n_pairs,
+                 const int32_t *quads, int n_quads, const int32_t *quad_ptr, const int32_t *quad_ref, int n_refs, float k_r,
+                 float k_t, float k_c, float contact_scale, float h0, float h_max, int n_iter, float *xyz_out,
+                 double *trace_energy, double *trace_trial_energy, float *trace_step, uint8_t *trace_accepted,
+                 float *trace_gmax, uint8_t *converged, void *scratch, void *stream);
+
 /* Self-test of the MFMA chain primitive: Y[n][:] = act(W @ X[n][:] + bias), n < 32*tiles.
  * act: 0 = none, 1 = exact-erf GELU. */
 int codlad_selftest_gemm128(const float *W_packed, const float *bias, const float *X, int n_rows,

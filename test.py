@@ -36,6 +36,9 @@ block; instead `--geometry_check` (implied by --cg_pdb, available on every route
 generated structure against its template topology on the device (metrics.geometry_check): broken / spurious bonds, clashes.
 Addition: `--stereo_check` (opt-in, wherever --geometry_check is allowed) adds what the covalent graph cannot see
 (metrics.stereo_check): inverted CA / CB centres, cis and twisted peptide bonds, and the phi / psi / omega / chi table.
+Addition: `--relax [N]` (opt-in, wherever --geometry_check is allowed) relaxes every generated structure on the device before
+it is checked and written (metrics.relax: N iterations of restrained steepest descent, CAs fixed): overlapping atoms are
+pushed apart, bonded geometry and rigid torsions stay the decoder's.  The decoder's own coordinates are kept beside them.
 """
 import argparse
 import os
@@ -173,6 +176,24 @@ def check_stereo(args):
                              "(use --pdb_files, --cg_pdb or --synthetic)")
     args.stereo_check = want
     return want
+
+
+def check_relax(args):
+    """Where --relax applies: exactly where --geometry_check does (structures are generated and their topology is known; the
+    refusals of --cg_pdb itself are check_cg_input's).  Returns the number of iterations, 0 = off."""
+    n = getattr(args, "relax", None)
+    if n is None:
+        args.relax = 0
+        return 0
+    if n < 0:
+        raise SystemExit(f"--relax takes a number of iterations >= 0, got {n}")
+    if not getattr(args, "cg_pdb", None):
+        if args.experiment in ("bpd", "fmloss"):
+            raise SystemExit(f"--relax relaxes generated structures: --experiment {args.experiment} generates none")
+        if args.data_process and not args.synthetic:
+            raise SystemExit("--relax needs the topology of the structures: --data_process pickles carry none "
+                             "(use --pdb_files, --cg_pdb or --synthetic)")
+    return n
 
 
 def check_sampler(args):
@@ -319,7 +340,7 @@ def iter_batches(args):
             plan = chunk_plan(args.synthetic_frames)
             names = [synth.IDX2THR[int(z)] for z in prot["z_full"]]
             geom_top = None
-            if getattr(args, "geometry_check", False) or getattr(args, "stereo_check", False):
+            if getattr(args, "geometry_check", False) or getattr(args, "stereo_check", False) or getattr(args, "relax", 0):
                 from codlad_amd.utils.cg_input import template_topology
                 geom_top = template_topology(names[1:-1])             # one Topology (and one set of device tables) per protein
             for c, (a, b) in enumerate(plan):
@@ -519,6 +540,7 @@ def run_sampling(model, args, x, mask=None, batch=None):
 def main(args):
     check_cg_input(args)
     check_stereo(args)
+    check_relax(args)
     check_sampler(args)
     if not torch.cuda.is_available():
         raise SystemExit("test.py (codlad_amd) needs an MI355X: there is no CPU path")
@@ -683,6 +705,15 @@ def main(args):
             if evaluation is not None:                               # reference test.py:589-594, per ensemble member
                 evaluation.add(batch, ic_recon, xyz_all[-1], xyz_all[-1].shape[1])
         xyz = torch.stack(xyz_all)                                   # [E, B, n_atoms, 3]
+        rel = None
+        if getattr(args, "relax", 0):
+            if name not in _GEOMETRY_TOP:
+                raise SystemExit(f"--relax: the topology of {name} is not known on this input route")
+            # every member of every frame, each on its own, CAs fixed; everything below sees the relaxed coordinates
+            flat = xyz.reshape(-1, xyz.shape[2], 3)
+            geo0 = metrics.geometry_check(flat, _GEOMETRY_TOP[name], order=args.edgeorder, near_dist=args.atom_cutoff)
+            rel = metrics.relax(flat, _GEOMETRY_TOP[name], n_iter=args.relax, order=args.edgeorder)
+            xyz_unrelaxed, xyz = xyz, rel["xyz"].reshape(xyz.shape)
         geo = None
         if args.geometry_check:
             if name not in _GEOMETRY_TOP:
@@ -700,6 +731,17 @@ def main(args):
         total += B * E
         if evaluation is not None:
             evaluation.report(name, args)
+        if rel is not None:
+            np.save(os.path.join(save_dir, f"{name}_xyz_unrelaxed.npy"), xyz_unrelaxed.cpu().numpy())
+            # [E * B, 3] float64: total energy before, after, accepted steps
+            np.save(os.path.join(save_dir, f"{name}_relax.npy"),
+                    torch.stack((rel["energy0"], rel["energy"], rel["n_accepted"].to(torch.float64)), 1).cpu().numpy())
+            geo1 = geo if geo is not None else metrics.geometry_check(xyz.reshape(-1, xyz.shape[2], 3), _GEOMETRY_TOP[name],
+                                                                      order=args.edgeorder, near_dist=args.atom_cutoff)
+            print(f"relax {name}: {args.relax} iterations, {float(rel['n_accepted'].to(torch.float64).mean()):.1f} accepted, "
+                  f"energy {float(rel['energy0'].mean()):.3f} -> {float(rel['energy'].mean()):.3f}, clashes "
+                  f"{int(geo0['clash'].sum())} -> {int(geo1['clash'].sum())}, min_dist {float(geo0['min_dist'].min()):.3f} -> "
+                  f"{float(geo1['min_dist'].min()):.3f}", flush=True)
         np.save(os.path.join(save_dir, f"{name}_xyz_recon.npy"), xyz.cpu().numpy())
         if geo is not None:
             np.save(os.path.join(save_dir, f"{name}_geometry.npy"), geo["counts"].cpu().numpy())        # [E * B, 5]
@@ -812,6 +854,12 @@ if __name__ == "__main__":
                         "undefined (residues), <name>_stereo_flags.npy [structures, residues] and <name>_torsions.npy "
                         "[structures, residues, 9] = phi, psi, omega, chi1-4 (degrees), v_ca, v_side (A^3); prints a summary. "
                         "Geometry, not accuracy")
+    p.add_argument("--relax", nargs="?", type=int, const=200, default=None, metavar="N",
+                   help="relax every generated structure before it is checked and written (allowed wherever --geometry_check "
+                        "is): N iterations (default 200) of restrained steepest descent on the device push overlapping atoms "
+                        "apart, CAs fixed, bonded geometry and rigid torsions held to the decoder's (metrics.relax).  The "
+                        "checks, <name>_xyz_recon.npy and --save_pdb see the relaxed coordinates; saves the decoder's as "
+                        "<name>_xyz_unrelaxed.npy and <name>_relax.npy [structures, 3] = energy before, after, accepted steps")
     p.add_argument("--atom_cutoff", type=float, default=9.0)
     p.add_argument("--cg_cutoff", type=float, default=21.0)
     p.add_argument("--edgeorder", type=int, default=2)
