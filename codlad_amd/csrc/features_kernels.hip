@@ -5,7 +5,8 @@
 //
 // One 256-thread workgroup per structure node i:
 //   A  distances to every node of the structure -> LDS
-//   B  rank selection of the K = min(64, L) nearest (ascending, ties by lower index)
+//   B  rank selection of the K = min(64, L) nearest (ascending, ties by lower index; a NaN distance sorts after every
+//      number: a total order, so the ranks are a permutation and every slot is written whatever bits the trace holds)
 //   C  167 raw features per edge -> LDS
 //   D  edge_embedding (167 -> 128)      E  LayerNorm(affine, 1e-5)      F  W_e (128 -> 128)
 #include "common.h"
@@ -88,10 +89,13 @@ __global__ __launch_bounds__(256) void features_kernel(codlad_denoiser_weights w
     __syncthreads();
     for (int j = tid; j < L; j += 256) {
         const float dj = D[j];
+        const bool nan_j = dj != dj;
         int rank = 0;
         for (int q = 0; q < L; ++q) {
             const float dq = D[q];
-            rank += (dq < dj || (dq == dj && q < j)) ? 1 : 0;
+            // q before j: the first two terms are false whenever either distance is NaN; a number goes before a NaN,
+            // two NaNs by index
+            rank += (dq < dj || (dq == dj && q < j) || (nan_j && (dq == dq || q < j))) ? 1 : 0;
         }
         if (rank < K) { nb[rank] = j; dnb[rank] = dj; }
     }

@@ -15,9 +15,15 @@
 // partners under the cut-off, so spurious = bonded - intact, and bonded == n_bonds - broken + spurious ties the bond list
 // to the flags of the CSR.
 //
-// Counts are integer atomics (one per block and counter) and the minimum is an integer atomicMin on the bit pattern of a
-// non-negative float: both are order-independent, so results are bit-identical from run to run and a structure's row
+// Counts are integer atomics (one per block and counter) and the minimum is a signed integer atomicMin on the bit pattern
+// of a non-negative float: both are order-independent, so results are bit-identical from run to run and a structure's row
 // does not depend on the other structures of the call.
+//
+// Non-finite coordinates: every comparison with a NaN distance is false, so such a pair is in no count except `broken`,
+// which is !(d < cut) - the complement of `intact`, so bonded == n_bonds - broken + spurious holds for any bits.  A row
+// atom with a coordinate that is NaN or +-inf puts NAN_BITS into the minimum instead of a distance: a NaN whose bit
+// pattern is a negative integer, so it wins the signed atomicMin against every distance in any order.  min_dist of such a
+// structure is NaN, which is what metrics.geometry_check's `valid` reads.
 // Compiled with -ffp-contract=off: distances round as bond_graph_kernel's and metrics_partial_kernel's do.
 #include "common.h"
 #include "../../include/codlad_hip.h"
@@ -29,6 +35,9 @@ constexpr float EPS = 1e-7f;     // as metrics_partial_kernel (reference test.py
 constexpr int32_t BOND_FLAG = CODLAD_GEOM_BOND_FLAG;
 constexpr int N_COUNTS = 5;
 constexpr uint32_t INF_BITS = 0x7f800000u;
+constexpr uint32_t NAN_BITS = 0xffc00000u;   // a quiet NaN, negative as an int32
+
+__device__ inline bool non_finite(float v) { return (__float_as_uint(v) & INF_BITS) == INF_BITS; }
 
 struct Cuts { float scale, clash, near; };
 
@@ -110,7 +119,7 @@ __global__ __launch_bounds__(ROWS) void geometry_check_kernel(const float *xyz, 
         const int p = bonds[2 * b], q = bonds[2 * b + 1];
         if ((unsigned)p >= (unsigned)n || (unsigned)q >= (unsigned)n) continue;
         const float d = sqrtf(dist2(x[3 * p], x[3 * p + 1], x[3 * p + 2], x[3 * q], x[3 * q + 1], x[3 * q + 2]));
-        broken += d >= (radius[p] + radius[q]) * cut.scale;
+        broken += !(d < (radius[p] + radius[q]) * cut.scale);
     }
 
     // --- block sums, then one integer atomic per counter
@@ -126,13 +135,14 @@ __global__ __launch_bounds__(ROWS) void geometry_check_kernel(const float *xyz, 
         if (threadIdx.x == 0 && red[0]) atomicAdd(counts + N_COUNTS * s + c, red[0]);
     }
     __syncthreads();
-    red[threadIdx.x] = (int)__float_as_uint(dmin);       // d >= 0: the bit patterns order as the values do
+    // d >= 0: the bit patterns order as the values do, as signed integers too, and NAN_BITS lies below all of them
+    red[threadIdx.x] = (int)((non_finite(xi) || non_finite(yi) || non_finite(zi)) ? NAN_BITS : __float_as_uint(dmin));
     __syncthreads();
     for (int st = ROWS / 2; st > 0; st >>= 1) {
         if ((int)threadIdx.x < st) red[threadIdx.x] = min(red[threadIdx.x], red[threadIdx.x + st]);
         __syncthreads();
     }
-    if (threadIdx.x == 0 && (uint32_t)red[0] < INF_BITS) atomicMin(min_bits + s, (uint32_t)red[0]);
+    if (threadIdx.x == 0 && red[0] < (int)INF_BITS) atomicMin(reinterpret_cast<int *>(min_bits) + s, red[0]);
 }
 }  // namespace
 

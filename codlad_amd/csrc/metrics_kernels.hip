@@ -15,6 +15,9 @@ constexpr int N_ACC = 10;
 constexpr int MAX_BLOCKS = 256;
 constexpr float EPS = 1e-7f;   // reference test.py:27
 
+// torch.maximum(v, 0) of the reference: a NaN stays a NaN (fmaxf would return the 0), every number as fmaxf gives it
+__device__ inline float relu_nan(float v) { return v <= 0.0f ? 0.0f : v; }
+
 __device__ inline float dist(const float *xyz, int64_t i, int64_t j) {
     const float dx = xyz[3 * i] - xyz[3 * j], dy = xyz[3 * i + 1] - xyz[3 * j + 1], dz = xyz[3 * i + 2] - xyz[3 * j + 2];
     return sqrtf(((dx * dx + dy * dy) + dz * dz) + EPS);
@@ -43,7 +46,7 @@ __global__ __launch_bounds__(256) void metrics_partial_kernel(codlad_metric_inpu
             acc[3] += dist(in.xyz_recon, e[0], e[1]) < 1.2f ? 1.0 : 0.0;
         } else if (t < o5) {                            // inter_result, test.py:103-106
             const int64_t *e = in.interaction_list + 2 * (t - o4);
-            acc[4] += fmaxf(dist(in.xyz_recon, e[0], e[1]) - 4.0f, 0.0f);
+            acc[4] += relu_nan(dist(in.xyz_recon, e[0], e[1]) - 4.0f);
         } else if (t < o6) {                            // inter_result, test.py:109-113
             const int64_t *q = in.pi_pi_list + 4 * (t - o5);
             float c0[3], c1[3];
@@ -53,7 +56,7 @@ __global__ __launch_bounds__(256) void metrics_partial_kernel(codlad_metric_inpu
                 c1[k] = (in.xyz_recon[3 * q[2] + k] + in.xyz_recon[3 * q[3] + k]) / 2.0f;
             }
             const float dx = c0[0] - c1[0], dy = c0[1] - c1[1], dz = c0[2] - c1[2];
-            acc[5] += fmaxf(sqrtf(((dx * dx + dy * dy) + dz * dz) + EPS) - 6.0f, 0.0f);
+            acc[5] += relu_nan(sqrtf(((dx * dx + dy * dy) + dz * dz) + EPS) - 6.0f);
         } else {                                        // recon_result, test.py:153-166
             const int64_t s = t - o6;
             const float m = in.ic_mask[s];

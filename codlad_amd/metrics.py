@@ -377,7 +377,7 @@ def _geometry_launch(xyz, radius, ptr_, words, bonds, scale, clash_dist, near_di
                                           C.c_float(near_dist), _lib.ptr(counts), _lib.ptr(min_dist), _lib.stream_ptr(dev))
     _lib.check(rc, "codlad_geometry_check")
     out = {k: counts[:, c] for c, k in enumerate(GEOMETRY_COUNTS)}
-    out.update(counts=counts, min_dist=min_dist, valid=(counts[:, 0] == 0) & (counts[:, 1] == 0))
+    out.update(counts=counts, min_dist=min_dist, valid=(counts[:, 0] == 0) & (counts[:, 1] == 0) & ~torch.isnan(min_dist))
     return out
 
 
@@ -398,14 +398,18 @@ def geometry_check_lists(xyz, radius, bonds, order=2, scale=1.3, clash_dist=1.2,
 def geometry_check(xyz, top, order=2, scale=1.3, clash_dist=1.2, near_dist=9.0):
     """xyz [S, n_atoms, 3] (device): S structures of the topology `top` (a dataset_builder.Topology of the written, i.e.
     interior, residues) -> dict of device tensors, one entry per structure, over unordered atom pairs:
-      broken    template bonds (standard_bonds) at d >= (r_i + r_j) * scale, r = COV_CUTOFF of the element
+      broken    template bonds (standard_bonds) not at d < (r_i + r_j) * scale, r = COV_CUTOFF of the element (a bond
+                whose d is not a number is broken)
       spurious  pairs at d < (r_i + r_j) * scale that are no template bond
       bonded    all pairs at d < (r_i + r_j) * scale (= n_bonds - broken + spurious)
       near      pairs more than `order` bonds apart at d <= near_dist
       clash     of those, the ones at sqrt(d^2 + 1e-7) < clash_dist (clash / near: the first term of clash_result with
                 the structure's own neighbour list)
-      min_dist  the smallest d over pairs more than `order` bonds apart (inf: there is none)
-      valid     broken == 0 and spurious == 0: the covalent graph of the structure IS the template's
+      min_dist  the smallest d over pairs more than `order` bonds apart (inf: there is none; NaN: a coordinate of the
+                structure is NaN or +-inf)
+      valid     broken == 0 and spurious == 0 and min_dist is not NaN: the covalent graph of the structure IS the
+                template's.  A structure with a non-finite coordinate is never valid: a comparison with a NaN distance is
+                false, so its pairs are in no count but `broken`, and bonded == n_bonds - broken + spurious still holds.
     and `counts`, the five counts as one int32 [S, 5] in the order of GEOMETRY_COUNTS.  One launch, no host transfer."""
     _need_cuda(xyz, "xyz")
     if xyz.dim() == 3 and xyz.shape[1] != top.n_atoms:

@@ -809,16 +809,21 @@ int codlad_ens_pairwise(const float *x, const double *mom, int G, int F, int n_a
  * [n_bonds][2]: the template bonds, each once, i < j.  Entries out of [0, n_atoms) are skipped; excl_ptr must be a valid
  * non-decreasing offset table into excl (it is not checked on the device).  n_atoms <= 65536.
  * With d = sqrtf((dx*dx + dy*dy) + dz*dz) in unfused fp32, over unordered pairs i < j of one structure:
- *   counts[0] broken   template bonds with d >= (r_i + r_j) * scale
+ *   counts[0] broken   template bonds with !(d < (r_i + r_j) * scale): a bond whose d is not a number is broken
  *   counts[1] spurious pairs with d < (r_i + r_j) * scale that are not flagged order-1 partners
  *   counts[2] bonded   all pairs with d < (r_i + r_j) * scale      (== n_bonds - broken + spurious when the flags of the
  *                                                                   CSR and the bond list describe the same graph)
  *   counts[3] near     pairs not in the exclusion list with d <= near_dist
  *   counts[4] clash    pairs not in the exclusion list with sqrtf(((dx*dx + dy*dy) + dz*dz) + 1e-7f) < clash_dist
  *                      (the root of the clash term of the evaluation metrics above)
- *   min_dist           the smallest d over pairs not in the exclusion list, +inf if there is none
+ *   min_dist           the smallest d over pairs not in the exclusion list, +inf if there is none; NaN if any
+ *                      coordinate of the structure is NaN or +-inf
+ * A comparison with a d that is not a number is false: such a pair is in no count but `broken`, and the identity of
+ * counts[2] holds for any bits.  A caller that reads "no broken, no spurious bond" as a verdict must also require that
+ * min_dist is not NaN (metrics.geometry_check's `valid` does).
  * counts int32 [n_struct][5], min_dist float [n_struct] (device).  Integer atomics and an integer minimum only: results are
- * bit-identical from call to call and a structure's row does not depend on the other structures of the call. */
+ * bit-identical from call to call and a structure's row does not depend on the other structures of the call, whatever
+ * those hold. */
 #define CODLAD_GEOM_BOND_FLAG (1 << 30)
 int codlad_geometry_check(const float *xyz, int n_struct, int n_atoms, const float *radius, const int32_t *excl_ptr,
                           const int32_t *excl, const int32_t *bonds, int n_bonds, float scale, float clash_dist,

@@ -451,7 +451,8 @@ def geometry_report(name, geo, n_atoms):
     near = c[:, 3]
     ratio = torch.where(near > 0, c[:, 4] / near.clamp(min=1), torch.zeros_like(near))
     stats = {"data_name": name, "structures": int(c.shape[0]), "atoms": int(n_atoms),
-             "geometry_valid_ratio": float(geo["valid"].to(torch.float64).mean()),
+             "geometry_valid_ratio": float(geo["valid"].to(torch.float64).mean()),          # non-finite ones are not valid
+             "geometry_non_finite": int(torch.isnan(geo["min_dist"]).sum()),
              "geometry_broken_bonds": float(c[:, 0].mean()), "geometry_spurious_bonds": float(c[:, 1].mean()),
              "geometry_clashes": float(c[:, 4].mean()), "geometry_clash_over_near": float(ratio.mean()),
              "geometry_min_dist": float(geo["min_dist"].min())}
