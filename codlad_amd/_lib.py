@@ -130,6 +130,7 @@ _SIGS = {
     "codlad_abi_version": (C.c_int, []),
     "codlad_probe_edge_launches": (C.c_int, [C.c_int]),
     "codlad_probe_read": (C.c_int, [C.c_int, C.POINTER(C.c_double)]),
+    "codlad_dispatch_read": (C.c_int, [P, C.c_int]),
     "codlad_metrics_scratch_bytes": (C.c_int, []),
     "codlad_eval_metrics": (C.c_int, [C.POINTER(MetricInputs), P, P, P]),
     "codlad_bond_graph_counts": (C.c_int, [P, P, P, P, P, C.c_int, C.c_int, C.c_float, P, P]),
@@ -212,7 +213,11 @@ def lib():
                 "(build it with `python -m codlad_amd.build`)")
         handle = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
         for name, (res, args) in _SIGS.items():
-            fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
+            try:
+                fn = getattr(handle, name)
+            except AttributeError:      # e.g. a build from before an entry point was added under the same ABI version
+                raise RuntimeError(f"{LIB_PATH} does not export {name}: it was built from an older include/codlad_hip.h "
+                                   f"(ABI version {ABI_VERSION} covers additions); rebuild it") from None
             fn.restype = res
             fn.argtypes = args
         if handle.codlad_abi_version() != ABI_VERSION:
@@ -235,6 +240,26 @@ def edge_plan(K, pair=True, grid=EDGE_GRID):
     check(lib().codlad_edge_plan_host(K.ctypes.data_as(P), K.shape[0], grid[0], grid[1], int(bool(pair)),
                                       bounds.ctypes.data_as(P), stats.ctypes.data_as(P)), "codlad_edge_plan_host")
     return bounds, stats
+
+
+DISPATCH_WORDS = ("edge", "node_in", "node_upd", "chunked_in", "chunked_upd", "grid_edge_msg", "grid_edge_upd", "grid_node_in",
+                  "grid_node_upd")                                   # CODLAD_DISPATCH_* of include/codlad_hip.h
+EDGE_KINDS = ("f32", "wide", "tile", "node", "node_upd1")           # CODLAD_EDGE_KIND_*
+NODE_KINDS = ("f32", "w", "q", "h4", "h8")                          # CODLAD_NODE_KIND_*
+
+
+def dispatch_read():
+    """codlad_dispatch_read: what the last forward of this process dispatched -> dict of DISPATCH_WORDS; the three kinds by
+    name (EDGE_KINDS / NODE_KINDS), the placement flags as bool, the grids as int."""
+    out = (C.c_int32 * len(DISPATCH_WORDS))()
+    n = lib().codlad_dispatch_read(out, len(DISPATCH_WORDS))
+    if n != len(DISPATCH_WORDS):
+        raise RuntimeError(f"codlad_dispatch_read: the library keeps {n} words, this binding knows {len(DISPATCH_WORDS)}")
+    rec = dict(zip(DISPATCH_WORDS, (int(v) for v in out)))
+    rec["edge"] = EDGE_KINDS[rec["edge"]]
+    rec["node_in"], rec["node_upd"] = NODE_KINDS[rec["node_in"]], NODE_KINDS[rec["node_upd"]]
+    rec["chunked_in"], rec["chunked_upd"] = bool(rec["chunked_in"]), bool(rec["chunked_upd"])
+    return rec
 
 
 def set_option(option, value):

@@ -140,9 +140,11 @@ __global__ __launch_bounds__(64, 1) void node_kernel(NodeArgs a) {
 }
 
 void launch_edge_f32(bool update, const EdgeArgs &ea, hipStream_t st) {
+    dispatch_note((ea.n_nodes + 3) / 4);
     hipLaunchKernelGGL(update ? edge_kernel<true> : edge_kernel<false>, dim3((ea.n_nodes + 3) / 4), dim3(256), 0, st, ea);
 }
 void launch_node_f32(bool upd, const NodeArgs &na, hipStream_t st) {
+    dispatch_note((na.n_nodes + 31) / 32);
     hipLaunchKernelGGL(upd ? node_kernel<true> : node_kernel<false>, dim3((na.n_nodes + 31) / 32), dim3(64), 0, st, na);
 }
 

@@ -6,21 +6,63 @@
 #include "flow_loss_args.h"
 #include "ode_args.h"
 
+// Dispatch record (codlad_dispatch_read): which kernels the last enqueue_forward launched and on what grids, the words
+// of CODLAD_DISPATCH_* in include/codlad_hip.h.  Host bookkeeping only: launch_edge_now / launch_node below write the
+// kinds and name the words the launcher they call reports to (dispatch_note, called by every launcher of host_util.h
+// right where it sizes its grid; node_kernel_h's adds the wave count of the instantiation it launches and whether that
+// takes the chunked placement).  Only enqueue_forward clears the record; another caller of launch_edge (the single-launch
+// hook codlad_bench_edge_launch) overwrites its launch's words and leaves the rest.  Not thread-safe, like the probe below.
+static struct {
+    int32_t v[CODLAD_DISPATCH_WORDS] = {};
+    int grid_word = -1, node_word = -1, chunked_word = -1;      // where the next dispatch_note goes (-1: nowhere)
+} g_dispatch;
+
+void dispatch_note(int grid, int stream_waves, bool chunked) {
+    if (g_dispatch.grid_word >= 0) g_dispatch.v[g_dispatch.grid_word] = grid;
+    if (g_dispatch.node_word >= 0 && stream_waves)
+        g_dispatch.v[g_dispatch.node_word] = stream_waves == 8 ? CODLAD_NODE_KIND_H8 : CODLAD_NODE_KIND_H4;
+    if (g_dispatch.chunked_word >= 0) g_dispatch.v[g_dispatch.chunked_word] = chunked;
+    g_dispatch.grid_word = g_dispatch.node_word = g_dispatch.chunked_word = -1;
+}
+
+extern "C" int codlad_dispatch_read(int32_t *out, int n) {
+    CODLAD_REQUIRE(out && n >= 0, "bad arguments");
+    for (int i = 0; i < n && i < CODLAD_DISPATCH_WORDS; ++i) out[i] = g_dispatch.v[i];
+    return CODLAD_DISPATCH_WORDS;
+}
+
 // precision: 0 = fp32 MFMA, 1 = f16x4, 2 = f16x3 (include/codlad_hip.h); terms = 4 or 3 products per split contraction, 0 = fp32
 static void launch_edge_now(bool update, const EdgeArgs &ea, int precision, hipStream_t st, const int2 *tile_list,
                             int n_tiles) {
     const int terms = precision == 2 ? 3 : (precision == 1 ? 4 : 0);
-    if (!terms) return launch_edge_f32(update, ea, st);
-    if (tile_list && n_tiles <= option_value(CODLAD_OPT_EDGE_WIDE_MAX_TILES)) return launch_edge_wide(terms, update, ea, tile_list, n_tiles, st);
-    if (tile_list) return launch_edge_tile(terms, update, ea, tile_list, n_tiles, st);
+    // the kinds are numbered so that a forward's edge kind is the largest of its launches': only the edge updates of a
+    // per-node job can take upd1_kernel_h
+    auto kind = [&](int k) {
+        if (k > g_dispatch.v[CODLAD_DISPATCH_EDGE]) g_dispatch.v[CODLAD_DISPATCH_EDGE] = k;
+        g_dispatch.grid_word = update ? CODLAD_DISPATCH_GRID_EDGE_UPD : CODLAD_DISPATCH_GRID_EDGE_MSG;
+    };
+    if (!terms) { kind(CODLAD_EDGE_KIND_F32); return launch_edge_f32(update, ea, st); }
+    if (tile_list && n_tiles <= option_value(CODLAD_OPT_EDGE_WIDE_MAX_TILES)) {
+        kind(CODLAD_EDGE_KIND_WIDE);
+        return launch_edge_wide(terms, update, ea, tile_list, n_tiles, st);
+    }
+    if (tile_list) { kind(CODLAD_EDGE_KIND_TILE); return launch_edge_tile(terms, update, ea, tile_list, n_tiles, st); }
     if (update) {
         // upd1_kernel_h gives every node two tiles: worth it while (nearly) every node has two (n_tiles counts the
         // non-empty ones; 0 = the caller gave no tile list, i.e. nothing is known about the job)
         const bool two_tiles_each = n_tiles > 0 && 20ll * n_tiles >= 19ll * 2 * ea.n_nodes;
         const int variant = option_value(CODLAD_OPT_EDGE_UPD_VARIANT);
-        if ((variant == 1 && two_tiles_each) || variant == 2) launch_edge_upd1(terms, ea, st);   // 2: always (tests)
-        else launch_edge_upd(terms, ea, st);
-    } else launch_edge_msg(terms, ea, st);
+        if ((variant == 1 && two_tiles_each) || variant == 2) {                                  // 2: always (tests)
+            kind(CODLAD_EDGE_KIND_NODE_UPD1);
+            launch_edge_upd1(terms, ea, st);
+        } else {
+            kind(CODLAD_EDGE_KIND_NODE);
+            launch_edge_upd(terms, ea, st);
+        }
+    } else {
+        kind(CODLAD_EDGE_KIND_NODE);
+        launch_edge_msg(terms, ea, st);
+    }
 }
 
 // Measurement aid (codlad_probe_edge_launches): while on, every edge-kernel launch of a forward is bracketed by a pair
@@ -81,11 +123,24 @@ extern "C" int codlad_probe_read(int kind, double *total_ms) {
 // spilled registers) finish in one and stream every weight block once per 256 nodes.
 static void launch_node(bool upd, const NodeArgs &na, int precision, hipStream_t st) {
     const int terms = precision == 2 ? 3 : (precision == 1 ? 4 : 0);
-    if (!terms) return launch_node_f32(upd, na, st);
+    auto kind = [&](int k) {
+        g_dispatch.node_word = upd ? CODLAD_DISPATCH_NODE_UPD : CODLAD_DISPATCH_NODE_IN;
+        g_dispatch.v[g_dispatch.node_word] = k;
+        g_dispatch.grid_word = upd ? CODLAD_DISPATCH_GRID_NODE_UPD : CODLAD_DISPATCH_GRID_NODE_IN;
+        g_dispatch.chunked_word = upd ? CODLAD_DISPATCH_CHUNKED_UPD : CODLAD_DISPATCH_CHUNKED_IN;
+    };
+    if (!terms) { kind(CODLAD_NODE_KIND_F32); return launch_node_f32(upd, na, st); }
     const int tiles = (na.n_nodes + 31) / 32;
-    if (upd && tiles <= option_value(CODLAD_OPT_NODE_QUAD_MAX_TILES)) launch_node_quad(terms, na, st);
-    else if (tiles <= option_value(CODLAD_OPT_NODEQ_MAX_TILES)) launch_node_wide(terms, upd, na, st);
-    else launch_node_stream(terms, tiles > 4 * num_cu() ? 8 : 4, upd, na, st);
+    if (upd && tiles <= option_value(CODLAD_OPT_NODE_QUAD_MAX_TILES)) {
+        kind(CODLAD_NODE_KIND_Q);
+        launch_node_quad(terms, na, st);
+    } else if (tiles <= option_value(CODLAD_OPT_NODEQ_MAX_TILES)) {
+        kind(CODLAD_NODE_KIND_W);
+        launch_node_wide(terms, upd, na, st);
+    } else {
+        kind(CODLAD_NODE_KIND_H4);      // node_kernel_h: the instantiation that is launched reports its own wave count
+        launch_node_stream(terms, tiles > 4 * num_cu() ? 8 : 4, upd, na, st);
+    }
 }
 
 // What every launch of one forward shares: the caller's descriptor and what the host derives from it.
@@ -180,6 +235,7 @@ static void enqueue_forward(const codlad_denoiser_weights *w, const codlad_job *
     const codlad_workspace *ws = job->ws;
     const int n_nodes = job->n_nodes;
     const float *h_E0 = job->h_E0, *E1 = job->E1;
+    g_dispatch = {};
     // small jobs: edge kernels per 32-edge tile, message sums per half (S[2][n_nodes][128])
     // (while every wave of the persistent grid gets at most one tile: beyond that the per-node order is as good)
     const bool tilewise = j.split && ws->tile_list && ws->n_tiles > 0 &&

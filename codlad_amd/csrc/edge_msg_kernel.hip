@@ -241,6 +241,7 @@ static void launch_msg_t(const EdgeArgs &ea, hipStream_t st) {
     }
     const int groups = (ea.n_nodes + NW - 1) / NW;
     dim3 grid(groups < edge_cus() ? groups : edge_cus()), block(NW * 64);
+    dispatch_note(grid.x);
     if (ea.E1 != nullptr) hipLaunchKernelGGL((msg_kernel_h<NW, true, TERMS>), grid, block, lds, st, ea);
     else hipLaunchKernelGGL((msg_kernel_h<NW, false, TERMS>), grid, block, lds, st, ea);
 }

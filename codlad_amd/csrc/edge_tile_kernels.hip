@@ -337,6 +337,7 @@ static void launch_tile_h(bool update, const EdgeArgs &ea, const int2 *tile_list
     ta.tile_list = tile_list; ta.n_tiles = n_tiles;
     const int groups = (n_tiles + nw - 1) / nw;
     dim3 grid(groups < num_cu() ? groups : num_cu()), block(nw * 64);
+    dispatch_note(grid.x);
     if (update && hoisted) hipLaunchKernelGGL((upd_tile_kernel_h<UPD_WAVES, true, TERMS>), grid, block, lds_upd, st, ta);
     else if (update) hipLaunchKernelGGL((upd_tile_kernel_h<UPD_WAVES, false, TERMS>), grid, block, lds_upd, st, ta);
     else if (hoisted) hipLaunchKernelGGL((msg_tile_kernel_h<MSG_WAVES, true, TERMS>), grid, block, lds_msg, st, ta);

@@ -441,6 +441,7 @@ static void launch_upd1_t(const EdgeArgs &ea, hipStream_t st) {
     }
     const int groups = (ea.n_nodes + U1_NW - 1) / U1_NW;
     dim3 grid(groups < edge_cus() ? groups : edge_cus()), block(U1_NW * 64);
+    dispatch_note(grid.x);
     if (ea.E1 != nullptr) hipLaunchKernelGGL((upd1_kernel_h<true, TERMS>), grid, block, lds, st, ea);
     else hipLaunchKernelGGL((upd1_kernel_h<false, TERMS>), grid, block, lds, st, ea);
 }

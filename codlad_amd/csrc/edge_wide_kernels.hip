@@ -301,6 +301,7 @@ void launch_wide_h(bool update, const EdgeArgs &ea, const int2 *tile_list, int n
     const int cap = 2 * num_cu();                    // two workgroups (one wave per SIMD each) per CU
     dim3 grid(n_tiles < cap ? n_tiles : cap), block(EW_WAVES * 64);
     const size_t lds_msg = 16 * (size_t)EW_FRAG_B;
+    dispatch_note(grid.x);
     if (update && hoisted) hipLaunchKernelGGL((upd_wide_kernel<true, TERMS>), grid, block, EW_LDS_BYTES, st, ta);
     else if (update) hipLaunchKernelGGL((upd_wide_kernel<false, TERMS>), grid, block, EW_LDS_BYTES, st, ta);
     else if (hoisted) hipLaunchKernelGGL((msg_wide_kernel<true, TERMS>), grid, block, lds_msg, st, ta);

@@ -15,6 +15,9 @@ void set_max_lds(const void *fn, size_t bytes);   // hipFuncSetAttribute; a fail
 hipError_t codlad_take_attr_error();              // that failure, if any (read once)
 int option_value(int opt);    // the value of CODLAD_OPT_<opt>: what codlad_set_option stored, else the environment's, else the default
 int edge_cus();               // persistent workgroups of an edge kernel: num_cu() unless CODLAD_OPT_EDGE_CUS says fewer
+// denoiser_forward.hip: every launcher below reports the grid it launches to the dispatch record (codlad_dispatch_read);
+// node_kernel_h's also its waves per workgroup and whether it takes the XCD-chunked placement
+void dispatch_note(int grid, int stream_waves = 0, bool chunked = false);
 
 void launch_edge_f32(bool update, const EdgeArgs &ea, hipStream_t st);   // denoiser_f32_kernels.hip
 void launch_node_f32(bool upd, const NodeArgs &na, hipStream_t st);

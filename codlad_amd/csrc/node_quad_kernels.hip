@@ -248,6 +248,7 @@ void launch_q(const NodeArgs &na, hipStream_t st) {
         attr_set = true;
     }
     dim3 grid((na.n_nodes + 31) / 32), block(QUAD_WAVES * 64);
+    dispatch_note(grid.x);
     hipLaunchKernelGGL((node_kernel_q<TERMS>), grid, block, QUAD_LDS_BYTES, st, na);
 }
 

@@ -155,9 +155,10 @@ static void launch_node_hw(bool upd, const NodeArgs &na, hipStream_t st) {
         attr_set = true;
     }
     static_assert(NODE_WG_TILE % (32 * NW) == 0, "chunks hold whole workgroup tiles");
-    const int wgs = na.n_nodes >= XCD_CHUNKED_NODE_KERNEL_MIN ? 8 * (xcd_chunk_nodes(na.n_nodes) / (32 * NW))
-                                                              : (na.n_nodes + 32 * NW - 1) / (32 * NW);
+    const bool chunked = na.n_nodes >= XCD_CHUNKED_NODE_KERNEL_MIN;      // the kernel's own test for wg_node0
+    const int wgs = chunked ? 8 * (xcd_chunk_nodes(na.n_nodes) / (32 * NW)) : (na.n_nodes + 32 * NW - 1) / (32 * NW);
     dim3 grid(wgs), block(NW * 64);
+    dispatch_note(grid.x, NW, chunked);
     hipLaunchKernelGGL((upd ? node_kernel_h<true, NW, TERMS> : node_kernel_h<false, NW, TERMS>), grid, block, lds, st, na);
 }
 

@@ -353,6 +353,7 @@ void launch_w(bool upd, const NodeArgs &na, hipStream_t st) {
         attr_set = true;
     }
     dim3 grid((na.n_nodes + 31) / 32), block(WIDE_WAVES * 64);
+    dispatch_note(grid.x);
     if (upd) hipLaunchKernelGGL((node_kernel_w<true, TERMS>), grid, block, WIDE_LDS_BYTES, st, na);
     else hipLaunchKernelGGL((node_kernel_w<false, TERMS>), grid, block, WIDE_LDS_BYTES, st, na);
 }

@@ -304,7 +304,7 @@ class Denoiser:
 
     SAMPLE_KINDS = ("ddpm", "ddim", "ddim_reverse", "dpmpp")
 
-    def sample(self, job, x_T, noise, tables, check=True, coef=None, streams=None, pin=None, kind="ddpm"):
+    def sample(self, job, x_T, noise, tables, check=True, coef=None, streams=None, pin=None, kind="ddpm", x_start_out=None):
         """Full ancestral loop.  x_T [n_nodes,3]; noise [T,n_nodes,3] in loop order (first entry
         is used at step T-1); tables = diffusion_and_flow.schedule.Tables.  Returns x_0.
         check: after the loop, synchronise and raise if any step's output was not finite.
@@ -316,7 +316,10 @@ class Denoiser:
         kind: "ddpm" (the ancestral loop above), "ddim" (the DDIM loop, codlad_ddim_loop; coef = a Tables.ddim_coefficients
         table, default eta = 0), "ddim_reverse" (DDIM inversion: x_T holds x_0, the result is x_T; noise must be None) or
         "dpmpp" (DPM-Solver++(2M), codlad_dpm_loop; coef = a Tables.dpm_solver_coefficients table, default order 2;
-        deterministic: noise must be None)."""
+        deterministic: noise must be None).
+        x_start_out: a test aid (tests/test_dispatch_thresholds.py): a [n_nodes,3] float32 tensor to use as the loop's
+        x_start buffer, which then holds the last step's pred_xstart.  The loop is the same with or without it:
+        self-conditioning follows the model, not this pointer."""
         if kind not in self.SAMPLE_KINDS:
             raise ValueError(f"kind must be one of {self.SAMPLE_KINDS}, got {kind!r}")
         reverse = kind == "ddim_reverse"
@@ -331,6 +334,9 @@ class Denoiser:
             _require_cuda(noise, "noise")
             assert noise.shape == (T, job.n_nodes, 3)
         assert x_T.shape == (job.n_nodes, 3)
+        if x_start_out is not None:
+            _require_cuda(x_start_out, "x_start_out")
+            assert x_start_out.shape == x_T.shape and x_start_out.dtype == torch.float32 and x_start_out.is_contiguous()
         if pin is not None:
             pin = self._pin_arrays(pin, job.n_nodes)
         streams = self._n_streams(job, streams)
@@ -338,11 +344,15 @@ class Denoiser:
             parts = job.parts(streams)
             pins = None if pin is None else [(pin[0][i], pin[1][i]) for _p, i in parts]
             noises = [None if noiseless else noise[:, i] for _p, i in parts]
+            starts = None if x_start_out is None else [torch.empty(p.n_nodes, 3, dtype=torch.float32, device=self.device)
+                                                        for p, _i in parts]
             outs = self.sample_many([p for p, _i in parts], [x_T[i] for _p, i in parts], noises,
-                                    tables, check=check, coef=coef, pins=pins, kind=kind)
+                                    tables, check=check, coef=coef, pins=pins, kind=kind, x_start_outs=starts)
             x0 = torch.empty(job.n_nodes, 3, dtype=torch.float32, device=self.device)
-            for (_p, i), o in zip(parts, outs):
+            for k, ((_p, i), o) in enumerate(zip(parts, outs)):
                 x0[i] = o
+                if starts is not None:
+                    x_start_out[i] = starts[k]
             return x0
         if coef is None:
             coef = (tables.step_coefficients() if kind == "ddpm" else tables.dpm_solver_coefficients() if kind == "dpmpp"
@@ -359,7 +369,8 @@ class Denoiser:
         coef = torch.from_numpy(coef).to(self.device)
         self._fresh_features(job.structures)
         # pred_xstart, step to step: the self-conditioning input, and the history of the multistep solver
-        x_start = torch.empty_like(x) if self.self_condition or kind == "dpmpp" else None
+        x_start = x_start_out if x_start_out is not None else (
+            torch.empty_like(x) if self.self_condition or kind == "dpmpp" else None)
         loop = [_lib.ptr(t) for t in (x, x_start, noise, mods, coef)] + [T]
         pin_ptrs = [_lib.ptr(t) for t in (pin or (None, None))]
         if kind == "dpmpp":
@@ -374,15 +385,16 @@ class Denoiser:
             self.check_status(job)
         return x
 
-    def sample_many(self, jobs, x_Ts, noises, tables, check=True, coef=None, pins=None, kind="ddpm"):
+    def sample_many(self, jobs, x_Ts, noises, tables, check=True, coef=None, pins=None, kind="ddpm", x_start_outs=None):
         """Several independent jobs at once, each on its own HIP stream: the node kernel of a 35 000-node job occupies 139 of
         the 256 CUs and every kernel has a tail - with a second job in flight another job's edge kernels run there (two
         half-jobs of BASELINE configuration 2: 1.03 x; more than two parts lose).  Every job carries its
         own workspace and the library keeps no state between jobs, so the results are those of `sample` job by job.
         pins: None, or one `pin` of `sample` (or None) per job.  kind as for `sample` (noises: None per job for
-        "ddim_reverse" and "dpmpp")."""
+        "ddim_reverse" and "dpmpp").  x_start_outs: None, or one `x_start_out` of `sample` (or None) per job."""
         pins = [None] * len(jobs) if pins is None else list(pins)
-        assert len(pins) == len(jobs)
+        starts = [None] * len(jobs) if x_start_outs is None else list(x_start_outs)
+        assert len(pins) == len(jobs) == len(starts)
         for job in jobs:                                  # features and the step tables once, on the caller's stream
             self._fresh_features(job.structures)
         self.step_mods(tables.timestep_map)
@@ -390,10 +402,11 @@ class Denoiser:
         # joined: the block of a mask released earlier goes to the next job's mask while a side stream still reads it
         pins = [None if pin is None else self._pin_arrays(pin, job.n_nodes) for job, pin in zip(jobs, pins)]
 
-        def one(job, x_T, noise, pin):
-            return self.sample(job, x_T, noise, tables, check=False, coef=coef, streams=1, pin=pin, kind=kind)
+        def one(job, x_T, noise, pin, start):
+            return self.sample(job, x_T, noise, tables, check=False, coef=coef, streams=1, pin=pin, kind=kind,
+                               x_start_out=start)
 
-        outs = self._on_streams([lambda a=a: one(*a) for a in zip(jobs, x_Ts, noises, pins)], len(jobs))
+        outs = self._on_streams([lambda a=a: one(*a) for a in zip(jobs, x_Ts, noises, pins, starts)], len(jobs))
         if check:
             for job in jobs:
                 self.check_status(job)

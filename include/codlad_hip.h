@@ -724,6 +724,35 @@ int codlad_set_option(int option, int value);
 int codlad_probe_edge_launches(int enable);
 int codlad_probe_read(int kind, double *total_ms);
 
+/* Test aid (not part of the reference's interface): what the last forward of this process dispatched - any entry point
+ * that runs the denoiser; of a loop, its last forward.  Copies min(n, CODLAD_DISPATCH_WORDS) words of the record to `out`
+ * and returns CODLAD_DISPATCH_WORDS; negative = error.  The record is written by the code that picks the kernels and by
+ * the launchers where they size their grids, so it is the dispatch itself, not a restatement of its rules.  Only a
+ * forward clears the record: a single launch made outside one (codlad_bench_edge_launch) overwrites the words of its
+ * launch and leaves the rest, so read the record right after the forward it is about.  Host bookkeeping only; not
+ * thread-safe; one forward at a time. */
+#define CODLAD_DISPATCH_EDGE 0           /* CODLAD_EDGE_KIND_* of the forward's edge launches */
+#define CODLAD_DISPATCH_NODE_IN 1        /* CODLAD_NODE_KIND_* of the input node launch (h_V = x_in(x)) */
+#define CODLAD_DISPATCH_NODE_UPD 2       /* ... of the node updates */
+#define CODLAD_DISPATCH_CHUNKED_IN 3     /* 1: the input node kernel took its XCD-chunked placement */
+#define CODLAD_DISPATCH_CHUNKED_UPD 4    /* ... the node update */
+#define CODLAD_DISPATCH_GRID_EDGE_MSG 5  /* workgroups of the last message launch */
+#define CODLAD_DISPATCH_GRID_EDGE_UPD 6  /* ... edge-update launch */
+#define CODLAD_DISPATCH_GRID_NODE_IN 7   /* ... input node launch */
+#define CODLAD_DISPATCH_GRID_NODE_UPD 8  /* ... node-update launch */
+#define CODLAD_DISPATCH_WORDS 9
+#define CODLAD_EDGE_KIND_F32 0           /* edge_kernel */
+#define CODLAD_EDGE_KIND_WIDE 1          /* msg_wide_kernel / upd_wide_kernel: four waves per 32-edge tile */
+#define CODLAD_EDGE_KIND_TILE 2          /* msg_tile_kernel_h / upd_tile_kernel_h: one wave per tile */
+#define CODLAD_EDGE_KIND_NODE 3          /* msg_kernel_h / upd_kernel_h: per node, persistent grid */
+#define CODLAD_EDGE_KIND_NODE_UPD1 4     /* ... with upd1_kernel_h for the edge updates */
+#define CODLAD_NODE_KIND_F32 0           /* node_kernel */
+#define CODLAD_NODE_KIND_W 1             /* node_kernel_w */
+#define CODLAD_NODE_KIND_Q 2             /* node_kernel_q */
+#define CODLAD_NODE_KIND_H4 3            /* node_kernel_h, four waves per workgroup */
+#define CODLAD_NODE_KIND_H8 4            /* node_kernel_h, eight waves */
+int codlad_dispatch_read(int32_t *out, int n);
+
 /* Measurement hook: ONE launch of the message kernel (which = 0) or the edge-update kernel
  * (which = 1) of encoder layer `layer` (0 or 1) on a job whose workspace holds the state of a
  * previous forward; both GEMM layers are executed (no E1 shortcut).  Layer 0 reads the shared h_E0,

@@ -185,7 +185,8 @@ def test_forward_after_features_against_float64_large_job_kernels(name, mode):
                                            variant 0, the default) upd_kernel_h, one workgroup pass per node;
       CODLAD_OPT_NODE_QUAD_MAX_TILES = 0 and CODLAD_OPT_NODEQ_MAX_TILES = 0   neither node_kernel_q nor node_kernel_w:
                                            node_kernel_h, the streaming node update (four waves per workgroup at this
-                                           size; a job of more than 4 x 256 tiles runs the same code with eight).
+                                           size; the eight-wave instantiation, the XCD-chunked placement and the
+                                           shipped thresholds themselves: tests/test_dispatch_thresholds.py).
     The f32 mode has one set of kernels whatever the switches say, so it is not run twice."""
     spec = spec_of(name)
     _lib.set_option(_lib.OPT_EDGE_TILE_MAX_NODES, 0)
