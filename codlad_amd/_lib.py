@@ -122,6 +122,7 @@ ODE_METHODS = {"euler": 0, "midpoint": 1, "rk4": 2}    # CODLAD_ODE_* of include
 GEOM_BOND_FLAG = 1 << 30                               # CODLAD_GEOM_BOND_FLAG: an order-1 partner in the exclusion CSR
 STEREO_COLUMNS, STEREO_N_COUNTS, STEREO_KIND_PRO = 9, 6, 1   # CODLAD_STEREO_COLUMNS, _COUNTS, _KIND_PRO
 STEREO_FLAGS = {"inverted_ca": 1, "inverted_side": 2, "cis": 4, "twisted": 8, "undefined": 16}   # CODLAD_STEREO_* flag bits
+SASA_MAX_POINTS = 1024                                 # CODLAD_SASA_MAX_POINTS
 ODE_NORM_WORDS = 257                                   # CODLAD_ODE_NORM_WORDS
 
 _JOB = [C.POINTER(DenoiserWeights), C.POINTER(JobDesc)]    # what every entry point that runs the denoiser starts with
@@ -145,6 +146,8 @@ _SIGS = {
                             [C.c_float] * 4 + [P] * 5),
     "codlad_relax": (C.c_int, [P, C.c_int, C.c_int, P, P, P, P, P, P, C.c_int, P, C.c_int, P, P, C.c_int] +
                      [C.c_float] * 6 + [C.c_int] + [P] * 9),
+    "codlad_sasa": (C.c_int, [P, C.c_int, C.c_int, P, P, P, C.c_int, P, C.c_int, P, P, P, P, P, P]),
+    "codlad_contact_counts": (C.c_int, [P, C.c_int, C.c_int, P, C.c_int, C.c_float, P, P]),
     "codlad_last_error": (C.c_char_p, []),
     "codlad_struct_sizes": (None, [C.POINTER(C.c_int)]),
     "codlad_pack_block_host": (None, [P, C.c_int, C.c_float, P]),

@@ -952,6 +952,51 @@ int codlad_relax(const float *xyz, int n_struct, int n_atoms, const float *radiu
                  double *trace_energy, double *trace_trial_energy, float *trace_step, uint8_t *trace_accepted,
                  float *trace_gmax, uint8_t *converged, void *scratch, void *stream);
 
+/* Ensemble observables (csrc/observables_kernels.hip): solvent-accessible surface area and contact counts of n_struct
+ * structures xyz [n_struct][n_atoms][3] that share ONE topology.  (The third observable, the radius of gyration, is
+ * sqrt(G / m) of codlad_ens_moments.)  Added to ABI version 19 without changing the number: two new entry points, no
+ * existing signature, struct or option changes.
+ *
+ * codlad_sasa, Shrake-Rupley: atom i carries the sphere of radius R_i = radius[i] (van der Waals radius + probe) about
+ * x_i with the n_points test points R_i * u_k, u_k = dirs[k] (unit vectors, one table for all atoms).  fp32 with one
+ * rounding per operation (no contraction), per component:
+ *   e = fl(R_i * u_k) - fl(x_j - x_i)      the difference of the coordinates is formed first: a translation of the
+ *                                          structure costs no precision
+ *   point k of i is BURIED by atom j != i (by index only: coincident atoms bury each other's points as any pair does)
+ *   when (e.x*e.x + e.y*e.y) + e.z*e.z < R_j*R_j
+ *   exposed[i]   = the number of points of i that no j buries, 0 .. n_points
+ *   atom_area[i] = (float)exposed[i] * unit_area[i], one rounding; unit_area[i] = (float)(4 pi R_i^2 / n_points), the
+ *                  quotient formed in double by the caller
+ *   res_area[r]  = the fp32 rounding of the fp64 sum of atom_area[q], q = res_ptr[r] .. res_ptr[r + 1] - 1 ascending
+ *   total        = the fp64 sum of all atom_area of the structure in this order: partial p (0 .. 255) adds the atoms
+ *                  p, p + 256, p + 512, ... ascending; then for stride = 128, 64, .. 1: partial[p] += partial[p + stride]
+ *                  for every p < stride; total = partial[0]
+ * An atom j is left out without the test only when (dx*dx + dy*dy) + dz*dz > fl(fl(s*s) * (1 + 2^-10)), s = fl(R_i + R_j),
+ * d = x_j - x_i: three orders of magnitude beyond every rounding involved, so leaving it out never changes a decision.
+ * A structure with a coordinate that is NaN or +-inf gets finite = 0, exposed = -1 for every atom and NaN in every area
+ * and in total; the other structures of the call keep their bits (finite = 1).  No index is formed from a coordinate.
+ * All pointers are device pointers EXCEPT res_ptr, a HOST table int32 [n_res + 1] that is read during the call (it need
+ * not outlive it): it is checked - 0 <= res_ptr[r] <= res_ptr[r + 1] <= n_atoms - and handed to the device in kernel
+ * arguments.  res_ptr = NULL, n_res = 0, res_area = NULL: no residues.  exposed int32 and atom_area float
+ * [n_struct][n_atoms], res_area float [n_struct][n_res], total double [n_struct], finite uint8 [n_struct].
+ * Integer counts, no atomics, sums in one order: results are bit-identical from call to call and a structure's results do
+ * not depend on n_struct or on its place in the call.  A null pointer, n_struct <= 0, n_atoms <= 0, n_points outside
+ * 1 .. CODLAD_SASA_MAX_POINTS, res_ptr / n_res / res_area that do not go together or a table that fails the check returns
+ * -1 (codlad_last_error) before any launch. */
+#define CODLAD_SASA_MAX_POINTS 1024
+int codlad_sasa(const float *xyz, int n_struct, int n_atoms, const float *radius, const float *unit_area, const float *dirs,
+                int n_points, const int32_t *res_ptr, int n_res, int32_t *exposed, float *atom_area, float *res_area,
+                double *total, uint8_t *finite, void *stream);
+/* counts int32 [m][m], m = n_sel (sel: device int32 [n_sel], entries in [0, n_atoms)) or n_atoms (sel = NULL, n_sel = 0):
+ * counts[a][b] = the number of structures with (dx*dx + dy*dy) + dz*dz < cut2, d = x[sel[a]] - x[sel[b]] in unfused fp32
+ * (the distance of codlad_geometry_check, squared).  The upper triangle is computed and mirrored, the diagonal is written
+ * as 0.  A distance that is not a number compares false: that structure is not counted for the pair.  A pair with a sel
+ * entry out of range reads nothing and counts 0.  Integer counts per thread, no atomics.  A null pointer, n_struct <= 0,
+ * n_atoms <= 0, sel / n_sel that do not go together, a cut2 that is negative or NaN or m > 65535 * 16 returns -1 before
+ * any launch. */
+int codlad_contact_counts(const float *xyz, int n_struct, int n_atoms, const int32_t *sel, int n_sel, float cut2,
+                          int32_t *counts, void *stream);
+
 /* Self-test of the MFMA chain primitive: Y[n][:] = act(W @ X[n][:] + bias), n < 32*tiles.
  * act: 0 = none, 1 = exact-erf GELU. */
 int codlad_selftest_gemm128(const float *W_packed, const float *bias, const float *X, int n_rows,

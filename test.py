@@ -39,6 +39,9 @@ Addition: `--stereo_check` (opt-in, wherever --geometry_check is allowed) adds w
 Addition: `--relax [N]` (opt-in, wherever --geometry_check is allowed) relaxes every generated structure on the device before
 it is checked and written (metrics.relax: N iterations of restrained steepest descent, CAs fixed): overlapping atoms are
 pushed apart, bonded geometry and rigid torsions stay the decoder's.  The decoder's own coordinates are kept beside them.
+Addition: `--observables [N_POINTS]` (opt-in, wherever --geometry_check is allowed; after --relax when both are given)
+describes the written ensemble on the device: per-residue solvent-accessible surface area (metrics.sasa, N_POINTS test
+points per atom), the radius of gyration of every structure and the CA contact-frequency map at 8 A.
 """
 import argparse
 import os
@@ -196,6 +199,24 @@ def check_relax(args):
     return n
 
 
+def check_observables(args):
+    """Where --observables applies: exactly where --geometry_check does (structures are generated and their topology is
+    known; the refusals of --cg_pdb itself are check_cg_input's).  Returns the number of test points per atom, 0 = off."""
+    n = getattr(args, "observables", None)
+    if n is None:
+        args.observables = 0
+        return 0
+    if not 1 <= n <= metrics.SASA_MAX_POINTS:
+        raise SystemExit(f"--observables takes a number of test points per atom in 1 .. {metrics.SASA_MAX_POINTS}, got {n}")
+    if not getattr(args, "cg_pdb", None):
+        if args.experiment in ("bpd", "fmloss"):
+            raise SystemExit(f"--observables describes generated structures: --experiment {args.experiment} generates none")
+        if args.data_process and not args.synthetic:
+            raise SystemExit("--observables needs the topology of the structures: --data_process pickles carry none "
+                             "(use --pdb_files, --cg_pdb or --synthetic)")
+    return n
+
+
 def check_sampler(args):
     """--sampler / --eta / --timestep_spacing: DDIM and DPM-Solver++ apply to latent sampling with the diffusion model; a
     nonzero eta is a DDIM setting; the log-SNR spacing is a respacing of the diffusion model's steps."""
@@ -340,7 +361,8 @@ def iter_batches(args):
             plan = chunk_plan(args.synthetic_frames)
             names = [synth.IDX2THR[int(z)] for z in prot["z_full"]]
             geom_top = None
-            if getattr(args, "geometry_check", False) or getattr(args, "stereo_check", False) or getattr(args, "relax", 0):
+            if getattr(args, "geometry_check", False) or getattr(args, "stereo_check", False) or getattr(args, "relax", 0) \
+                    or getattr(args, "observables", 0):
                 from codlad_amd.utils.cg_input import template_topology
                 geom_top = template_topology(names[1:-1])             # one Topology (and one set of device tables) per protein
             for c, (a, b) in enumerate(plan):
@@ -480,6 +502,40 @@ def stereo_report(name, ste):
     return stats
 
 
+CA_CONTACT_CUTOFF = 8.0            # A: the usual CA contact definition of --observables
+
+
+def observables(xyz, top, n_points):
+    """--observables for the structures xyz [S, n_atoms, 3] (device) of the topology `top` -> dict of device tensors:
+    sasa (metrics.sasa's dict), rg float64 [S], contacts (metrics.contact_map's dict over the CA atoms)."""
+    ca = top.select("CA")
+    if not len(ca):
+        raise SystemExit("--observables: the topology has no CA atoms")
+    return dict(sasa=metrics.sasa(xyz, top, n_points=n_points), rg=metrics.radius_of_gyration(xyz),
+                contacts=metrics.contact_map(xyz, sel=ca, cutoff=CA_CONTACT_CUTOFF))
+
+
+def observables_report(name, obs):
+    """The printed summary of --observables for one output file -> the stats."""
+    def mean_sd(t):
+        t = t.to(torch.float64)
+        return float(t.mean()), float(t.std(unbiased=False))
+
+    fin = obs["sasa"]["finite"]
+    stats = {"data_name": name, "structures": int(fin.shape[0]), "observables_non_finite": int((~fin).sum())}
+    for key, t in (("rg", obs["rg"]), ("sasa_total", obs["sasa"]["total"])):
+        t = t[fin]
+        stats[f"{key}_mean"], stats[f"{key}_sd"] = mean_sd(t) if t.numel() else (float("nan"), float("nan"))
+    freq = obs["contacts"]["frequency"]
+    stats["ca_contacts_per_residue"] = float(freq.sum() / freq.shape[0])
+    print("############## vvvvvvvvv ensemble observables (SASA in A^2, Rg in A, CA contacts at 8 A):")
+    print(f"Rg {stats['rg_mean']:.3f} +- {stats['rg_sd']:.3f}   SASA {stats['sasa_total_mean']:.1f} +- {stats['sasa_total_sd']:.1f}")
+    for k, v in stats.items():
+        print(k, v)
+    print("############## ^^^^^^^^^ ensemble observables")
+    return stats
+
+
 def ca_indices(topology):
     """Positions of the CA atoms among the written atoms of a (residue names, atom names per residue) topology (the
     flanking residues are not written, protein_module.write_pdb)."""
@@ -542,6 +598,7 @@ def main(args):
     check_cg_input(args)
     check_stereo(args)
     check_relax(args)
+    check_observables(args)
     check_sampler(args)
     if not torch.cuda.is_available():
         raise SystemExit("test.py (codlad_amd) needs an MI355X: there is no CPU path")
@@ -727,6 +784,11 @@ def main(args):
             if name not in _GEOMETRY_TOP:
                 raise SystemExit(f"--stereo_check: the topology of {name} is not known on this input route")
             ste = metrics.stereo_check(xyz.reshape(-1, xyz.shape[2], 3), _GEOMETRY_TOP[name])      # one launch, as above
+        obs = None
+        if getattr(args, "observables", 0):
+            if name not in _GEOMETRY_TOP:
+                raise SystemExit(f"--observables: the topology of {name} is not known on this input route")
+            obs = observables(xyz.reshape(-1, xyz.shape[2], 3), _GEOMETRY_TOP[name], args.observables)    # the written coordinates
         torch.cuda.synchronize()
         dt = time.time() - st
         total += B * E
@@ -753,6 +815,11 @@ def main(args):
             np.save(os.path.join(save_dir, f"{name}_stereo_flags.npy"), ste["flags"].cpu().numpy())     # [E * B, R]
             np.save(os.path.join(save_dir, f"{name}_torsions.npy"), ste["values"].cpu().numpy())        # [E * B, R, 9]
             stereo_report(name, ste)
+        if obs is not None:
+            np.save(os.path.join(save_dir, f"{name}_sasa_residue.npy"), obs["sasa"]["residue"].cpu().numpy())     # [E * B, R]
+            np.save(os.path.join(save_dir, f"{name}_rg.npy"), obs["rg"].cpu().numpy())                            # [E * B]
+            np.save(os.path.join(save_dir, f"{name}_ca_contacts.npy"), obs["contacts"]["frequency"].cpu().numpy())  # [R, R]
+            observables_report(name, obs)
         if getattr(args, "save_pdb", False) and name in _TOPOLOGY:
             # reference test.py:787-796 writes the generated ensemble through mdtraj (.xtc + .pdb); here both directly, frames
             # of member 0 first (multi-model PDB in Angstrom, .xtc in nm as the format has it)
@@ -861,6 +928,12 @@ if __name__ == "__main__":
                         "apart, CAs fixed, bonded geometry and rigid torsions held to the decoder's (metrics.relax).  The "
                         "checks, <name>_xyz_recon.npy and --save_pdb see the relaxed coordinates; saves the decoder's as "
                         "<name>_xyz_unrelaxed.npy and <name>_relax.npy [structures, 3] = energy before, after, accepted steps")
+    p.add_argument("--observables", nargs="?", type=int, const=960, default=None, metavar="N_POINTS",
+                   help="also describe the written ensemble on the device (allowed wherever --geometry_check is; after --relax "
+                        "when both are given): solvent-accessible surface area with N_POINTS test points per atom (default "
+                        "960; metrics.sasa), radius of gyration, CA contacts at 8 A.  Prints mean +- sd of Rg and of the total "
+                        "SASA; saves <name>_sasa_residue.npy [structures, R], <name>_rg.npy [structures] and "
+                        "<name>_ca_contacts.npy [R, R] = the fraction of structures with the two CAs closer than 8 A")
     p.add_argument("--atom_cutoff", type=float, default=9.0)
     p.add_argument("--cg_cutoff", type=float, default=21.0)
     p.add_argument("--edgeorder", type=int, default=2)
