@@ -5,7 +5,9 @@ the kernel: the restrained pairs come from dataset_builder.high_order_edges (the
 its complement, the quads from an enumeration over the adjacency MATRIX, the ring bonds from a list by residue name.
 `dtype` switches the arithmetic of the energy terms and of the gradient to float32 (one rounding per operation, the
 formulas in the kernel's form); the energies are sums of those terms in float64 in both, as on the device.  The
-difference of the two evaluations on the same inputs is ref_dev, the deviation the device is allowed four times over.
+difference of the two evaluations on the same inputs is ref_dev, the deviation the device is allowed four times over -
+pooled over all cases in tests/test_relax.py, per atom and per term against `conditioning`'s scales in
+tests/test_relax_fp64_parity.py.
 
 The energy (per structure, A, no hydrogens), d = sqrt(|xi - xj|^2 + 1e-7):
   distance   k_r (d - d0)^2 over the pairs within 2 bonds, d0 from the start structure
@@ -143,13 +145,15 @@ def start_constants(x0, T, dtype=np.float64):
     return d0, t["cos"], t["sin"], w
 
 
-def energy(x, x0, T, fixed=None, dtype=np.float64, k_r=100.0, k_t=50.0, k_c=30.0, contact_scale=1.6, **_unused):
+def energy(x, x0, T, fixed=None, dtype=np.float64, k_r=100.0, k_t=50.0, k_c=30.0, contact_scale=1.6, w=None, **_unused):
     """One structure x [n, 3] against the start structure x0 -> (energy float64 [3], grad [n, 3] in `dtype`, gmax).  The
-    terms and the gradient are computed in `dtype` from the coordinates cast to it; the energies are float64 sums."""
+    terms and the gradient are computed in `dtype` from the coordinates cast to it; the energies are float64 sums.
+    w bool [Q]: the quad weights to use instead of the start structure's own (a quad AT the weight threshold)."""
     dt = np.dtype(dtype).type
     x = np.asarray(x).astype(dtype)
     n = T["n"]
-    d0, c0, s0, w = start_constants(x0, T, dtype)
+    d0, c0, s0, w_own = start_constants(x0, T, dtype)
+    w = w_own if w is None else np.asarray(w, dtype=bool)
     g = np.zeros((n, 3), dtype=dtype)
     k_r, k_t, k_c, cs = dt(k_r), dt(k_t), dt(k_c), dt(contact_scale)
     two = dt(2.0)
@@ -190,6 +194,65 @@ def energy(x, x0, T, fixed=None, dtype=np.float64, k_r=100.0, k_t=50.0, k_c=30.0
     if fixed is not None:
         g[np.asarray(fixed, dtype=bool)] = 0
     return np.array([e_r, e_t, e_c]), g, float(np.abs(g).max()) if g.size else 0.0
+
+
+def conditioning(x, x0, T, w=None, k_r=100.0, k_t=50.0, k_c=30.0, contact_scale=1.6, **_unused):
+    """What one float32 rounding can do to the gradient of every atom and to each energy, in float64 from the inputs as
+    given -> dict: S, K float64 [n] (the force magnitudes and the stiffness x length of the terms touching an atom),
+    scale [n] = 2^-24 (S + K), scale_E [3] per energy, contact bool [n] (the atom has a contact inside sigma), members
+    int [3] (the terms of each class that are counted: pairs, quads of weight 1, contacts inside sigma).
+      pair (i, j), t = d - d0             S += |2 k_r t|       K += 2 k_r (d + d0)       E: k_r t^2 + |2 k_r t| (d + d0)
+      contact, t = sigma - d > 0          S += 2 k_c t         K += 2 k_c (d + sigma)    E: k_c t^2 + 2 k_c t (d + sigma)
+      quad of weight 1, atom at `pos`     S += |dE/dphi| G     K += (k_t + |dE/dphi|) G / min(s1, s2)
+        with G = |a1| |n1| + |a2| |n2| (a1, a2: the kernel's coefficients of dphi/dp[pos]) and s1, s2 the |sin| of the quad's
+        bond angles at x;                 E: E_t + k_t chord / min(s1, s2 at x and at x0), chord = |(cos, sin) - (cos0, sin0)|
+    A difference t is formed from two roots that are each off by half a place of their own size, hence (d + d0); the
+    torsion's unit vector is off by a few places over the sine of the flatter bond angle."""
+    x, x0 = np.asarray(x, dtype=np.float64), np.asarray(x0, dtype=np.float64)
+    n = T["n"]
+    d0, c0, s0, w_own = start_constants(x0, T)
+    w = w_own if w is None else np.asarray(w, dtype=bool)
+    S, K, sE = np.zeros(n), np.zeros(n), np.zeros(3)
+    contact = np.zeros(n, dtype=bool)
+
+    def both(i, j, s, k):
+        for a in (i, j):
+            np.add.at(S, a, s)
+            np.add.at(K, a, k)
+    i, j = T["pairs"][:, 0], T["pairs"][:, 1]
+    d = _dist(x, i, j, np.float64)[1]
+    t = d - d0
+    f = np.abs(2 * k_r * t)
+    both(i, j, f, 2 * k_r * (d + d0))
+    sE[0] = (k_r * t * t + f * (d + d0)).sum()
+    q = T["quads"][w]
+    if len(q):
+        c0, s0 = c0[w], s0[w]
+        p = torsion_parts(x, q)
+        de = np.abs(k_t * (p["sin"] * c0 - p["cos"] * s0))
+        bb = _dot(p["b2"], p["b2"])
+        n1, n2 = np.sqrt(_dot(p["n1"], p["n1"])), np.sqrt(_dot(p["n2"], p["n2"]))
+        f0, f3 = -p["lb2"] / (n1 * n1), p["lb2"] / (n2 * n2)
+        u, v = _dot(p["b1"], p["b2"]) / bb, _dot(p["b3"], p["b2"]) / bb
+        flat, flat0 = angle_sines(x, q).min(-1), angle_sines(x0, q).min(-1)
+        for k, (a1, a2) in enumerate([(f0, 0 * f0), (-f0 - u * f0, v * f3), (u * f0, -f3 - v * f3), (0 * f3, f3)]):
+            G = np.abs(a1) * n1 + np.abs(a2) * n2
+            np.add.at(S, q[:, k], de * G)
+            np.add.at(K, q[:, k], (k_t + de) * G / flat)
+        dc, ds = p["cos"] - c0, p["sin"] - s0
+        chord2 = dc * dc + ds * ds
+        sE[1] = (k_t * 0.5 * chord2 + k_t * np.sqrt(chord2) / np.minimum(flat, flat0)).sum()
+    iu, ju = T["free_i"], T["free_j"]
+    d = _dist(x, iu, ju, np.float64)[1]
+    sig = (T["radius"][iu] + T["radius"][ju]) * contact_scale
+    hit = d < sig
+    iu, ju, d, sig = iu[hit], ju[hit], d[hit], sig[hit]
+    t = sig - d
+    both(iu, ju, 2 * k_c * t, 2 * k_c * (d + sig))
+    sE[2] = (k_c * t * t + 2 * k_c * t * (d + sig)).sum()
+    contact[iu] = contact[ju] = True
+    return dict(S=S, K=K, scale=2.0 ** -24 * (S + K), scale_E=2.0 ** -24 * sE, contact=contact,
+                members=np.array([len(i), len(q), int(hit.sum())]))
 
 
 def sigma_margin(x, T, contact_scale=1.6):

@@ -3,18 +3,22 @@
 One evaluation is held to the float64 reference of tests/relax_ref.py on generic topologies (the graphs of
 tests/test_geometry_check.py, with quads over random bonds), with margins asserted on the CPU - no free pair within 1e-4 A
 of its sigma, no quad with a bond-angle |sin| in [0.05, 0.2] in the start structure - so that no inclusion decision can
-differ.  Tolerance, the rule of tests/test_stereo_check.py: |device - float64| <= 4 x ref_dev for each of the three energies
-and per gradient component, ref_dev = the largest deviation, over all cases, of the SAME formulas evaluated in numpy float32
-from float64; the factor 4 covers the different order of the fp32 sums of a gradient.
+differ.  Tolerance here: a POOLED one - |device - float64| <= 4 x ref_dev for each of the three energies and per gradient
+component, ref_dev = the largest deviation, over ALL cases, of the SAME formulas evaluated in numpy float32 from float64.  One
+structure sets the gradient's number (below), so this test alone lets a force that is wrong by 1 pass on every other atom of
+every case, and holds energies of 0.02 to 14 000 to the same absolute 3e-3 to 6e-3.  It stays as a coarse net; the rule the
+kernels are held to - per atom and per term, on these cases and on designed ones, and the loop step by step - is
+tests/test_relax_fp64_parity.py's (tests/relax_cases.py).
 
-The loop is held to its own rule EXACTLY, from the trace of every run in this file (check_rule), and to what it is for:
+The loop is held to its own rule EXACTLY, on its own numbers, from the trace of every run in this file (check_rule; against
+float64 per step: tests/test_relax_fp64_parity.py), and to what it is for:
 the planted clashes of tests/relax_ref.py (conditions asserted by tests/test_relax_host.py with the float64 reference)
 must be gone, with the fixed atoms, the stereo flags and the covalent graph as they were.
 
 Figures (printed by every run): ref_dev 7.11e-4 / 1.52e-3 / 1.11e-3 for the distance / torsion / repulsion energy and 0.620 per
-gradient component (structure 2 of the 2 100-atom case has nearly coincident atoms and a gradient of ~1e6; every other case is
-below 7e-4); bounds 2.84e-3 / 6.09e-3 / 4.46e-3 and 2.48; the device's largest errors on an MI355X: 7.11e-4 / 1.52e-3 / 1.11e-3 and
-0.622 - the float32 restatement's own.  Planted chains: clashes 7 / 6 / 8 -> 0, closest free pair 2.08 / 2.16 / 2.15 A after 200
+gradient component (structure 2 of the 2 100-atom case has nearly coincident atoms and a gradient of 2.4e4; every other
+structure is below 7e-4, one at 3.3e-3, on gradients of 30 to 3000); pooled bounds 2.84e-3 / 6.09e-3 / 4.46e-3 and 2.48; the
+device's largest errors on an MI355X: 7.11e-4 / 1.52e-3 / 1.11e-3 and 0.622 - the float32 restatement's own.  Planted chains: clashes 7 / 6 / 8 -> 0, closest free pair 2.08 / 2.16 / 2.15 A after 200
 iterations (160 / 163 / 159 accepted)."""
 import ctypes as C
 import functools
