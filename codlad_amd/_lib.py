@@ -123,6 +123,9 @@ GEOM_BOND_FLAG = 1 << 30                               # CODLAD_GEOM_BOND_FLAG: 
 STEREO_COLUMNS, STEREO_N_COUNTS, STEREO_KIND_PRO = 9, 6, 1   # CODLAD_STEREO_COLUMNS, _COUNTS, _KIND_PRO
 STEREO_FLAGS = {"inverted_ca": 1, "inverted_side": 2, "cis": 4, "twisted": 8, "undefined": 16}   # CODLAD_STEREO_* flag bits
 SASA_MAX_POINTS = 1024                                 # CODLAD_SASA_MAX_POINTS
+DSSP_MAX_RES = 4096                                    # CODLAD_DSSP_MAX_RES
+DSSP_CODES = " HBEGITS"                                # CODLAD_DSSP_LOOP, _H, _B, _E, _G, _I, _T, _S = 0 .. 7; 255 = undefined
+DSSP_KIND_PRO, DSSP_KIND_CHAIN_START, DSSP_GEOM_LINK, DSSP_GEOM_BEND, DSSP_UNDEFINED = 1, 2, 1, 2, 255   # CODLAD_DSSP_*
 ODE_NORM_WORDS = 257                                   # CODLAD_ODE_NORM_WORDS
 
 _JOB = [C.POINTER(DenoiserWeights), C.POINTER(JobDesc)]    # what every entry point that runs the denoiser starts with
@@ -148,6 +151,8 @@ _SIGS = {
                      [C.c_float] * 6 + [C.c_int] + [P] * 9),
     "codlad_sasa": (C.c_int, [P, C.c_int, C.c_int, P, P, P, C.c_int, P, C.c_int, P, P, P, P, P, P]),
     "codlad_contact_counts": (C.c_int, [P, C.c_int, C.c_int, P, C.c_int, C.c_float, P, P]),
+    "codlad_dssp_hbonds": (C.c_int, [P, C.c_int, C.c_int, P, P, C.c_int, P, P, P, P, P, P, P, P]),
+    "codlad_dssp_assign": (C.c_int, [P, P, P, P, C.c_int, C.c_int, P, P, P, P]),
     "codlad_last_error": (C.c_char_p, []),
     "codlad_struct_sizes": (None, [C.POINTER(C.c_int)]),
     "codlad_pack_block_host": (None, [P, C.c_int, C.c_float, P]),

@@ -997,6 +997,93 @@ int codlad_sasa(const float *xyz, int n_struct, int n_atoms, const float *radius
 int codlad_contact_counts(const float *xyz, int n_struct, int n_atoms, const int32_t *sel, int n_sel, float cut2,
                           int32_t *counts, void *stream);
 
+/* Secondary structure (csrc/dssp_kernels.hip): DSSP of n_struct structures xyz [n_struct][n_atoms][3] that share ONE
+ * topology, in two calls - coordinates to integers, integers to states.  Added to ABI version 19 without changing the
+ * number: two new entry points, no existing signature, struct or option changes.
+ *
+ * codlad_dssp_hbonds.  bb: device int32 [n_res][4], 16-byte aligned, the atom indices of N, CA, C, O of every residue; an
+ * index outside [0, n_atoms) means the atom is absent.  res_kind: device uint8 [n_res], CODLAD_DSSP_KIND_PRO (no amide H)
+ * and CODLAD_DSSP_KIND_CHAIN_START (the residue starts a chain).  All arithmetic is fp32 with one rounding per operation
+ * in the written order (no contraction); |a - b| = sqrtf((dx*dx + dy*dy) + dz*dz), d = a - b per component; sqrtf and the
+ * division are the correctly rounded ones.
+ *   Link r to r+1: intact when residue r+1 does not start a chain, C_r and N_{r+1} are both present, and
+ *     |C_r - N_{r+1}| <= 2.5 A.
+ *   Amide hydrogen: H_j = N_j + (C_{j-1} - O_{j-1}) / |C_{j-1} - O_{j-1}| (per component: one quotient, one sum).  It
+ *     exists only when link j-1 to j is intact, residue j is not PRO, and N_j, C_{j-1}, O_{j-1} are all present.
+ *   Eligible pairs: E(i -> j), the energy of C=O of i with N-H of j, is defined when i != j; C_i and O_i are present; H_j
+ *     exists; not (j = i + 1 with that link intact).
+ *   Energy: E = 27.888 * (((1/r_ON + 1/r_CH) - 1/r_OH) - 1/r_CN) kcal/mol, r_ON = |O_i - N_j|, r_CH = |C_i - H_j|,
+ *     r_OH = |O_i - H_j|, r_CN = |C_i - N_j|.  If any of the four distances is below 0.5 A, E = -9.9.  E is never lower
+ *     than -9.9.  There is no rounding to 0.001.
+ *   Bond: Hbond(i -> j) holds when E < -0.5.
+ *   Other DSSP habits left out: no CA-CA pre-filter is part of the definition (the kernel has no pre-filter at all: every
+ *     eligible pair is evaluated).  No "best two partners" truncation: the full matrix is the result - a difference from
+ *     mkdssp, which keeps the two lowest acceptors and donors of a residue, as is the unrounded energy.
+ *   Bend: kappa_i is the angle in degrees between u = CA_i - CA_{i-2} and v = CA_{i+2} - CA_i:
+ *     acosf(clamp(u.v / sqrtf((u.u) * (v.v)), -1, 1)) * (180 / pi), dots as (x*x + y*y) + z*z, acosf the device library's.
+ *     bend_i holds when kappa_i > 70.  kappa is defined only when all four links between i-2 and i+2 are intact and the
+ *     three CAs are present.  Otherwise it is NaN and there is no bend.
+ * Outputs (device), W = (n_res + 63) / 64:
+ *   acc uint64 [n_struct][n_res][W]    bit j of row i (bit j % 64 of word j / 64) is Hbond(i -> j); bits >= n_res are 0
+ *   don, the same shape                bit j of row i is Hbond(j -> i): exactly the transpose of acc (both directions of a
+ *                                      pair run the same instruction sequence on the same operands)
+ *   geom uint8 [n_struct][n_res]       CODLAD_DSSP_GEOM_LINK: link r to r+1 is intact; CODLAD_DSSP_GEOM_BEND: bend
+ *   kappa float [n_struct][n_res]
+ *   e_best float [n_struct][n_res][2], partner int32 [n_struct][n_res][2]
+ *                                      column 0 describes residue i as acceptor: the lowest E(i -> j) over eligible j, and
+ *                                      that j; column 1 as donor: the lowest E(j -> i).  Ties go to the lowest j.  With no
+ *                                      eligible pair (an energy that is NaN - C and O of a residue coincide - is never the
+ *                                      lowest) the partner is -1 and the energy is 0.
+ *   finite uint8 [n_struct]            0 when any coordinate of an atom named in bb is NaN or +-inf: that structure's
+ *                                      bitmaps and geom are 0, its energies and kappa are NaN, and its partners are -1.
+ *                                      The other structures keep their bits.  Atoms that bb does not name are never read.
+ * Integer decisions, no atomics on floats, one comparison order: results are bit-identical from call to call and a
+ * structure's results do not depend on n_struct or on its place in the call.  A null pointer, n_struct / n_atoms /
+ * n_res <= 0, a bb that is not 16-byte aligned, n_res > CODLAD_DSSP_MAX_RES or n_struct * ((n_res + 3) / 4) >= 2^31
+ * returns -1 (codlad_last_error) before any launch. */
+#define CODLAD_DSSP_MAX_RES 4096
+#define CODLAD_DSSP_KIND_PRO 1
+#define CODLAD_DSSP_KIND_CHAIN_START 2
+#define CODLAD_DSSP_GEOM_LINK 1
+#define CODLAD_DSSP_GEOM_BEND 2
+int codlad_dssp_hbonds(const float *xyz, int n_struct, int n_atoms, const int32_t *bb, const uint8_t *res_kind, int n_res,
+                       uint64_t *acc, uint64_t *don, uint8_t *geom, float *kappa, float *e_best, int32_t *partner,
+                       uint8_t *finite, void *stream);
+/* codlad_dssp_assign reads acc, don, geom and finite in the layouts above (PRO and the chain starts act through them)
+ * and nothing else; any bitmaps may be given, they need not come from codlad_dssp_hbonds (bits >= n_res must be 0, and
+ * the link bit of the last residue is ignored).  The rule (Kabsch & Sander 1983, classic priority):
+ *   Turns: turn_n(i), for n = 3, 4, 5, holds when Hbond(i -> i+n) holds and the links i .. i+n are all intact (the n
+ *     links that join the residues i .. i+n).
+ *   H: turn_4(i-1) and turn_4(i) make residues i .. i+3 H.
+ *   Bridges: Bridge(i, j) requires |i - j| >= 3; links i-1 to i, i to i+1, j-1 to j and j to j+1 intact.
+ *     Parallel: [Hbond(i-1 -> j) and Hbond(j -> i+1)] or [Hbond(j-1 -> i) and Hbond(i -> j+1)].
+ *     Antiparallel: [Hbond(i -> j) and Hbond(j -> i)] or [Hbond(i-1 -> j+1) and Hbond(j-1 -> i+1)].
+ *   E and B: a residue is E when it has a bridge that continues in a neighbour - parallel: bridge (i, j) with (i-1, j-1)
+ *     or (i+1, j+1); antiparallel: bridge (i, j) with (i-1, j+1) or (i+1, j-1).  It is B when it has a bridge but none
+ *     continues.  Neither overwrites H.  Beta bulges and sheet labels are out of scope: a ladder interrupted by a bulge is
+ *     two ladders here, and no ladder or sheet is named.
+ *   G: turn_3(i-1) and turn_3(i) make i .. i+2 G, when all three are loop or G so far.
+ *   I: turn_5(i-1) and turn_5(i) make i .. i+4 I, when all five are loop or I so far.
+ *   T: an unassigned residue i is T when some n and some k in 1 .. n-1 have turn_n(i-k).
+ *   S: an unassigned residue is S when it has a bend.
+ * Outputs (device): ss uint8 [n_struct][n_res], the codes below (CODLAD_DSSP_UNDEFINED marks every residue of a
+ * structure with finite = 0); bridge int32 [n_struct][n_res][2]: the lowest parallel partner and the lowest antiparallel
+ * partner, -1 where there is none (and in a structure with finite = 0); counts int32 [n_struct][8]: residues per code, -1
+ * for a structure with finite = 0.  Integers throughout: exact and bit-identical from call to call.  One workgroup per
+ * structure with its per-residue state in LDS, which is what bounds n_res: a null pointer, n_struct / n_res <= 0,
+ * n_res > CODLAD_DSSP_MAX_RES or n_struct * n_res >= 2^31 returns -1 before any launch. */
+#define CODLAD_DSSP_LOOP 0
+#define CODLAD_DSSP_H 1
+#define CODLAD_DSSP_B 2
+#define CODLAD_DSSP_E 3
+#define CODLAD_DSSP_G 4
+#define CODLAD_DSSP_I 5
+#define CODLAD_DSSP_T 6
+#define CODLAD_DSSP_S 7
+#define CODLAD_DSSP_UNDEFINED 255
+int codlad_dssp_assign(const uint64_t *acc, const uint64_t *don, const uint8_t *geom, const uint8_t *finite, int n_struct,
+                       int n_res, uint8_t *ss, int32_t *bridge, int32_t *counts, void *stream);
+
 /* Self-test of the MFMA chain primitive: Y[n][:] = act(W @ X[n][:] + bias), n < 32*tiles.
  * act: 0 = none, 1 = exact-erf GELU. */
 int codlad_selftest_gemm128(const float *W_packed, const float *bias, const float *X, int n_rows,

@@ -42,6 +42,9 @@ pushed apart, bonded geometry and rigid torsions stay the decoder's.  The decode
 Addition: `--observables [N_POINTS]` (opt-in, wherever --geometry_check is allowed; after --relax when both are given)
 describes the written ensemble on the device: per-residue solvent-accessible surface area (metrics.sasa, N_POINTS test
 points per atom), the radius of gyration of every structure and the CA contact-frequency map at 8 A.
+Addition: `--dssp` (opt-in, wherever --geometry_check is allowed; after --relax when both are given) assigns the secondary
+structure of every written structure on the device (metrics.dssp: Kabsch-Sander hydrogen bonds, DSSP states) and the
+propensity of each state per residue over the file's structures.
 """
 import argparse
 import os
@@ -217,6 +220,20 @@ def check_observables(args):
     return n
 
 
+def check_dssp(args):
+    """Where --dssp applies: exactly where --geometry_check does (structures are generated and their topology is known; the
+    refusals of --cg_pdb itself are check_cg_input's).  Returns whether it is on."""
+    on = bool(getattr(args, "dssp", False))
+    args.dssp = on
+    if on and not getattr(args, "cg_pdb", None):
+        if args.experiment in ("bpd", "fmloss"):
+            raise SystemExit(f"--dssp describes generated structures: --experiment {args.experiment} generates none")
+        if args.data_process and not args.synthetic:
+            raise SystemExit("--dssp needs the topology of the structures: --data_process pickles carry none "
+                             "(use --pdb_files, --cg_pdb or --synthetic)")
+    return on
+
+
 def check_sampler(args):
     """--sampler / --eta / --timestep_spacing: DDIM and DPM-Solver++ apply to latent sampling with the diffusion model; a
     nonzero eta is a DDIM setting; the log-SNR spacing is a respacing of the diffusion model's steps."""
@@ -362,7 +379,7 @@ def iter_batches(args):
             names = [synth.IDX2THR[int(z)] for z in prot["z_full"]]
             geom_top = None
             if getattr(args, "geometry_check", False) or getattr(args, "stereo_check", False) or getattr(args, "relax", 0) \
-                    or getattr(args, "observables", 0):
+                    or getattr(args, "observables", 0) or getattr(args, "dssp", False):
                 from codlad_amd.utils.cg_input import template_topology
                 geom_top = template_topology(names[1:-1])             # one Topology (and one set of device tables) per protein
             for c, (a, b) in enumerate(plan):
@@ -536,6 +553,25 @@ def observables_report(name, obs):
     return stats
 
 
+def dssp_report(name, sec, propensity):
+    """The printed summary of --dssp for one output file (sec: metrics.dssp's dict, propensity: metrics.ss_propensity of its
+    labels) -> the stats: the mean share of helix (H + G + I), strand (E + B) and coil (the rest) over residues and finite
+    structures."""
+    fin = sec["finite"]
+    stats = {"data_name": name, "structures": int(fin.shape[0]), "dssp_non_finite": int((~fin).sum())}
+    share = propensity.mean(dim=0)                                                  # [8]: NaN when no structure is finite
+    codes = {c: i for i, c in enumerate(metrics.DSSP_CODES)}
+    stats["helix"] = float(share[codes["H"]] + share[codes["G"]] + share[codes["I"]])
+    stats["strand"] = float(share[codes["E"]] + share[codes["B"]])
+    stats["coil"] = float(share[codes[" "]] + share[codes["T"]] + share[codes["S"]])
+    print("############## vvvvvvvvv secondary structure (DSSP, mean share of residues):")
+    print(f"helix {stats['helix']:.3f}   strand {stats['strand']:.3f}   coil {stats['coil']:.3f}")
+    for k, v in stats.items():
+        print(k, v)
+    print("############## ^^^^^^^^^ secondary structure")
+    return stats
+
+
 def ca_indices(topology):
     """Positions of the CA atoms among the written atoms of a (residue names, atom names per residue) topology (the
     flanking residues are not written, protein_module.write_pdb)."""
@@ -599,6 +635,7 @@ def main(args):
     check_stereo(args)
     check_relax(args)
     check_observables(args)
+    check_dssp(args)
     check_sampler(args)
     if not torch.cuda.is_available():
         raise SystemExit("test.py (codlad_amd) needs an MI355X: there is no CPU path")
@@ -789,6 +826,12 @@ def main(args):
             if name not in _GEOMETRY_TOP:
                 raise SystemExit(f"--observables: the topology of {name} is not known on this input route")
             obs = observables(xyz.reshape(-1, xyz.shape[2], 3), _GEOMETRY_TOP[name], args.observables)    # the written coordinates
+        sec = None
+        if getattr(args, "dssp", False):
+            if name not in _GEOMETRY_TOP:
+                raise SystemExit(f"--dssp: the topology of {name} is not known on this input route")
+            sec = metrics.dssp(xyz.reshape(-1, xyz.shape[2], 3), _GEOMETRY_TOP[name])            # the written coordinates
+            sec_prop = metrics.ss_propensity(sec["ss"])
         torch.cuda.synchronize()
         dt = time.time() - st
         total += B * E
@@ -820,6 +863,10 @@ def main(args):
             np.save(os.path.join(save_dir, f"{name}_rg.npy"), obs["rg"].cpu().numpy())                            # [E * B]
             np.save(os.path.join(save_dir, f"{name}_ca_contacts.npy"), obs["contacts"]["frequency"].cpu().numpy())  # [R, R]
             observables_report(name, obs)
+        if sec is not None:
+            np.save(os.path.join(save_dir, f"{name}_dssp.npy"), sec["ss"].cpu().numpy())                  # uint8 [E * B, R]
+            np.save(os.path.join(save_dir, f"{name}_dssp_propensity.npy"), sec_prop.cpu().numpy())       # float64 [R, 8]
+            dssp_report(name, sec, sec_prop)
         if getattr(args, "save_pdb", False) and name in _TOPOLOGY:
             # reference test.py:787-796 writes the generated ensemble through mdtraj (.xtc + .pdb); here both directly, frames
             # of member 0 first (multi-model PDB in Angstrom, .xtc in nm as the format has it)
@@ -934,6 +981,12 @@ if __name__ == "__main__":
                         "960; metrics.sasa), radius of gyration, CA contacts at 8 A.  Prints mean +- sd of Rg and of the total "
                         "SASA; saves <name>_sasa_residue.npy [structures, R], <name>_rg.npy [structures] and "
                         "<name>_ca_contacts.npy [R, R] = the fraction of structures with the two CAs closer than 8 A")
+    p.add_argument("--dssp", action="store_true",
+                   help="also assign the secondary structure of every written structure on the device (allowed wherever "
+                        "--geometry_check is; after --relax when both are given): Kabsch-Sander hydrogen bonds and the DSSP "
+                        "states (metrics.dssp).  Prints the mean helix (H+G+I), strand (E+B) and coil shares; saves "
+                        "<name>_dssp.npy uint8 [structures, R] (0 .. 7 = ' HBEGITS', 255 = a structure that is not finite) and "
+                        "<name>_dssp_propensity.npy float64 [R, 8] = the share of finite structures with each state")
     p.add_argument("--atom_cutoff", type=float, default=9.0)
     p.add_argument("--cg_cutoff", type=float, default=21.0)
     p.add_argument("--edgeorder", type=int, default=2)
