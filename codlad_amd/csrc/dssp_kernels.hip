@@ -36,25 +36,17 @@
 #include <cmath>
 
 #include "common.h"
-#include "../../include/codlad_hip.h"
+#include "structure_math.h"
 
 namespace {
 constexpr int WAVE = 64;
 constexpr int ROWS = 4;                      // rows (= waves) per workgroup of dssp_hbond_kernel
 constexpr int THREADS = 256;
 constexpr int MAX_RES = CODLAD_DSSP_MAX_RES;
-constexpr uint32_t INF_BITS = 0x7f800000u;
 constexpr float DEG = 57.295779513082320877f;   // 180 / pi
 constexpr float KS_Q = 27.888f;                 // 332 * 0.42 * 0.20 kcal/mol A
 constexpr float E_MIN = -9.9f, E_BOND = -0.5f, R_MIN = 0.5f, LINK_MAX = 2.5f, BEND_ABOVE = 70.f;
 
-struct V3 { float x, y, z; };
-
-__device__ inline bool non_finite(float v) { return (__float_as_uint(v) & INF_BITS) == INF_BITS; }
-__device__ inline float quiet_nan() { return __uint_as_float(0x7fc00000u); }
-__device__ inline V3 load3(const float *x, int a) { return {x[3 * a], x[3 * a + 1], x[3 * a + 2]}; }
-__device__ inline V3 sub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ inline float dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 __device__ inline float dist(V3 a, V3 b) {
     const V3 d = sub(a, b);
     return sqrtf(dot(d, d));

@@ -26,7 +26,8 @@
 // structure is NaN, which is what metrics.geometry_check's `valid` reads.
 // Compiled with -ffp-contract=off: distances round as bond_graph_kernel's and metrics_partial_kernel's do.
 #include "common.h"
-#include "../../include/codlad_hip.h"
+#include "host_util.h"
+#include "structure_math.h"
 
 namespace {
 constexpr int ROWS = 256;        // rows per workgroup = threads per workgroup
@@ -34,10 +35,7 @@ constexpr int COLS = 1024;       // atoms per LDS column tile
 constexpr float EPS = 1e-7f;     // as metrics_partial_kernel (reference test.py:27)
 constexpr int32_t BOND_FLAG = CODLAD_GEOM_BOND_FLAG;
 constexpr int N_COUNTS = 5;
-constexpr uint32_t INF_BITS = 0x7f800000u;
 constexpr uint32_t NAN_BITS = 0xffc00000u;   // a quiet NaN, negative as an int32
-
-__device__ inline bool non_finite(float v) { return (__float_as_uint(v) & INF_BITS) == INF_BITS; }
 
 struct Cuts { float scale, clash, near; };
 
@@ -49,17 +47,6 @@ __device__ inline float dist2(float xi, float yi, float zi, float xj, float yj, 
 // sqrtf(d2 + EPS) < clash: sqrtf(d2 + EPS) >= sqrtf(d2) (both roundings are monotonic), so d < clash is necessary and
 // the second root is taken for the few pairs that pass it
 __device__ inline bool is_clash(float d2, float d, float clash) { return d < clash && sqrtf(d2 + EPS) < clash; }
-
-// is j among the partners of the CSR row [lo, hi) (sorted by partner index, flag bit ignored)?
-__device__ inline bool excluded(const int32_t *excl, int lo, int hi, int j) {
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        const int p = excl[mid] & ~BOND_FLAG;
-        if (p == j) return true;
-        if (p < j) lo = mid + 1; else hi = mid;
-    }
-    return false;
-}
 
 __global__ __launch_bounds__(ROWS) void geometry_check_kernel(const float *xyz, int n, int row_blocks, const float *radius,
                                                               const int32_t *excl_ptr, const int32_t *excl,
@@ -161,10 +148,7 @@ extern "C" int codlad_geometry_check(const float *xyz, int n_struct, int n_atoms
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipMemsetAsync(counts, 0, sizeof(int32_t) * N_COUNTS * (size_t)n_struct, st);
     if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)min_dist, (int)INF_BITS, (size_t)n_struct, st);
-    if (e != hipSuccess) {
-        codlad_set_error("codlad_geometry_check: %s", hipGetErrorString(e));
-        return (int)e;
-    }
+    if (e != hipSuccess) return codlad_hip_failed("codlad_geometry_check", e);
     const Cuts cut = {scale, clash_dist, near_dist};
     hipLaunchKernelGGL(geometry_check_kernel, dim3((unsigned)(row_blocks * n_struct)), dim3(ROWS), 0, st, xyz, n_atoms,
                        (int)row_blocks, radius, excl_ptr, excl, bonds, n_bonds, cut, counts, (uint32_t *)min_dist);

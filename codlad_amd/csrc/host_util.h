@@ -15,6 +15,13 @@ void set_max_lds(const void *fn, size_t bytes);   // hipFuncSetAttribute; a fail
 hipError_t codlad_take_attr_error();              // that failure, if any (read once)
 int option_value(int opt);    // the value of CODLAD_OPT_<opt>: what codlad_set_option stored, else the environment's, else the default
 int edge_cus();               // persistent workgroups of an edge kernel: num_cu() unless CODLAD_OPT_EDGE_CUS says fewer
+// api.hip (declared in common.h too, beside codlad_check_launch): the message codlad_last_error returns
+void codlad_set_error(const char *fmt, ...);
+// a HIP call before a launch (memset, copy) failed: the message codlad_check_launch gives a failed launch, and its code
+inline int codlad_hip_failed(const char *what, hipError_t e) {
+    codlad_set_error("%s: %s", what, hipGetErrorString(e));
+    return (int)e;
+}
 // denoiser_forward.hip: every launcher below reports the grid it launches to the dispatch record (codlad_dispatch_read);
 // node_kernel_h's also its waves per workgroup and whether it takes the XCD-chunked placement
 void dispatch_note(int grid, int stream_waves = 0, bool chunked = false);

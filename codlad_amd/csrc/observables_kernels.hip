@@ -27,7 +27,7 @@
 // Contacts: one thread per pair (a, b) of a 16 x 16 tile of the selection, a loop over the structures; tiles below the
 // diagonal do nothing, the others write (a, b) and (b, a), the diagonal 0: every element is written exactly once.
 #include "common.h"
-#include "../../include/codlad_hip.h"
+#include "structure_math.h"
 
 namespace {
 constexpr int WAVE = 64;
@@ -35,10 +35,7 @@ constexpr int WAVES = 4;                     // atoms per workgroup of sasa_kern
 constexpr int SUM_THREADS = 256;
 constexpr int RES_CHUNK = 512;               // residue boundaries per launch: 2 KiB of kernel arguments
 constexpr int TILE = 16;
-constexpr uint32_t INF_BITS = 0x7f800000u;
 constexpr float SLACK = 1.0f + 0x1p-10f;
-
-__device__ inline bool non_finite(float v) { return (__float_as_uint(v) & INF_BITS) == INF_BITS; }
 
 __global__ __launch_bounds__(SUM_THREADS) void finite_kernel(const float *xyz, int n3, uint8_t *finite) {
     const float *x = xyz + (size_t)blockIdx.x * n3;

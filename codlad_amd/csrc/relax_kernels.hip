@@ -23,7 +23,8 @@
 // race), moves its own atoms' accepted state and forms their next trial x' = x - fl32(h / gmax) * g: one multiply and one
 // subtract (compiled with -ffp-contract=off).  No host synchronisation, no grid-wide barrier, no cooperative launch.
 #include "common.h"
-#include "../../include/codlad_hip.h"
+#include "host_util.h"
+#include "structure_math.h"
 
 namespace {
 constexpr int ROWS = 256;        // rows per workgroup = threads per workgroup
@@ -39,23 +40,6 @@ struct Tables {
     int n, n_pairs, n_quads, n_refs;
 };
 struct Consts { float k_r, k_t, k_c, contact_scale; };
-struct V3 { float x, y, z; };
-
-__device__ inline V3 load3(const float *x, int a) { return {x[3 * a], x[3 * a + 1], x[3 * a + 2]}; }
-__device__ inline V3 sub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ inline V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ inline float dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-
-// is j among the partners of the CSR row [lo, hi) (sorted by partner index, flag bit ignored)?
-__device__ inline bool excluded(const int32_t *excl, int lo, int hi, int j) {
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        const int p = excl[mid] & ~BOND_FLAG;
-        if (p == j) return true;
-        if (p < j) lo = mid + 1; else hi = mid;
-    }
-    return false;
-}
 
 __device__ inline bool quad_in_range(int4 q, int n) {
     return (unsigned)q.x < (unsigned)n && (unsigned)q.y < (unsigned)n && (unsigned)q.z < (unsigned)n && (unsigned)q.w < (unsigned)n;
@@ -333,11 +317,6 @@ Scratch scratch_layout(int64_t S, int64_t n, int64_t n_pairs, int64_t n_quads, i
     L.total = off;
     return L;
 }
-
-int fail(const char *what, hipError_t e) {
-    codlad_set_error("%s: %s", what, hipGetErrorString(e));
-    return (int)e;
-}
 }  // namespace
 
 #define RELAX_CHECK_COMMON()                                                                                               \
@@ -376,7 +355,7 @@ extern "C" int codlad_relax_energy(const float *xyz, const float *xyz0, int n_st
     const Consts k = {k_r, k_t, k_c, contact_scale};
     hipStream_t st = (hipStream_t)stream;
     const hipError_t e = hipMemsetAsync(gmax, 0, sizeof(float) * (size_t)n_struct, st);
-    if (e != hipSuccess) return fail("codlad_relax_energy", e);
+    if (e != hipSuccess) return codlad_hip_failed("codlad_relax_energy", e);
     const dim3 grid((unsigned)(row_blocks * n_struct));
     hipLaunchKernelGGL(relax_prep_kernel, grid, dim3(ROWS), 0, st, xyz0, T, (int)row_blocks, d0, q0);
     hipLaunchKernelGGL(relax_eval_kernel, grid, dim3(ROWS), 0, st, xyz, T, k, (int)row_blocks, d0, q0, partials, grad,
@@ -411,7 +390,7 @@ extern "C" int codlad_relax(const float *xyz, int n_struct, int n_atoms, const f
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipMemsetAsync(gtrial, 0, sizeof(uint32_t) * (size_t)n_struct * (n_iter + 1), st);
     if (e == hipSuccess) e = hipMemcpyAsync(xa, xyz, sizeof(float) * 3 * (size_t)n_struct * n_atoms, hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) return fail("codlad_relax", e);
+    if (e != hipSuccess) return codlad_hip_failed("codlad_relax", e);
     const dim3 grid((unsigned)(row_blocks * n_struct));
     hipLaunchKernelGGL(relax_prep_kernel, grid, dim3(ROWS), 0, st, xyz, T, (int)row_blocks, d0, q0);
     for (int t = 0; t <= n_iter; ++t) {

@@ -21,7 +21,8 @@
 #include <cmath>
 
 #include "common.h"
-#include "../../include/codlad_hip.h"
+#include "host_util.h"
+#include "structure_math.h"
 
 namespace {
 constexpr int RES = 256;                     // residues (= threads) per workgroup
@@ -30,14 +31,6 @@ constexpr int N_COUNTS = CODLAD_STEREO_COUNTS;
 constexpr int COL_OMEGA = 2, COL_V_CA = 7, COL_V_SIDE = 8;
 constexpr float DEG = 57.295779513082320877f;   // 180 / pi
 constexpr float CIS_BELOW = 30.f, TWISTED_UPTO = 150.f;
-
-struct V3 { float x, y, z; };
-
-__device__ inline V3 load3(const float *x, int a) { return {x[3 * a], x[3 * a + 1], x[3 * a + 2]}; }
-__device__ inline V3 sub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ inline V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ inline float dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ inline float quiet_nan() { return __uint_as_float(0x7fc00000u); }
 
 // IUPAC torsion p0-p1-p2-p3 in degrees, in (-180, 180].  No angle exists where both arguments of atan2f are zero (two
 // of the atoms coincide, three are exactly collinear) or one is not a number: NaN.
@@ -132,10 +125,7 @@ extern "C" int codlad_stereo_check(const float *xyz, int n_struct, int n_atoms, 
     CODLAD_REQUIRE(res_blocks * n_struct < (int64_t)1 << 31, "too many workgroups for one launch");
     hipStream_t st = (hipStream_t)stream;
     const hipError_t e = hipMemsetAsync(counts, 0, sizeof(int32_t) * N_COUNTS * (size_t)n_struct, st);
-    if (e != hipSuccess) {
-        codlad_set_error("codlad_stereo_check: %s", hipGetErrorString(e));
-        return (int)e;
-    }
+    if (e != hipSuccess) return codlad_hip_failed("codlad_stereo_check", e);
     hipLaunchKernelGGL(stereo_check_kernel, dim3((unsigned)(res_blocks * n_struct)), dim3(RES), 0, st, xyz, n_atoms, n_res,
                        (int)res_blocks, (const int4 *)sites, res_kind, values, flags, counts);
     return codlad_check_launch("codlad_stereo_check");

@@ -2,7 +2,7 @@
 reference's loop (reference test.py:97-166, called at test.py:589-593).  Pinned by
 tests/golden/g8_metrics_*.npz, which tools/gen_golden.py produced by calling the reference's own
 functions on the synthetic lists of tests/cases.py.  Only tests/, __graft_entry__.smoke() and bench.py's
-cpu_baseline may import this package; the product path (codlad_amd/metrics.py) never does.
+cpu_baseline may import this package; the product path (codlad_amd/metrics/) never does.
 """
 import torch
 

@@ -14,17 +14,15 @@
 Both paths start from the same device tensors.  Wall clock is taken around the whole call including its one
 synchronisation; the device side of the device path also by HIP events.  Every shape is warmed up; min / median / max
 over the repeats are reported.  Needs a GPU: there is nothing to measure without one."""
-import argparse
 import os
 import statistics
 import sys
-import time
 
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from codlad_amd import metrics, synth  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from cost_common import events, main, metrics, spread, synth, wall  # noqa: E402
 
 
 def atom_count(L, seed):
@@ -40,47 +38,7 @@ def ensemble(G, F, n, seed, dev):
     return torch.from_numpy(gen).to(dev), torch.from_numpy(ref).to(dev)
 
 
-def spread(xs):
-    return f"min {min(xs) * 1e3:9.3f}  median {statistics.median(xs) * 1e3:9.3f}  max {max(xs) * 1e3:9.3f} ms"
-
-
-def wall(fn, repeats, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(repeats):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        out.append(time.perf_counter() - t0)
-    return out
-
-
-def events(fn, repeats):
-    out = []
-    for _ in range(repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        out.append(e0.elapsed_time(e1) * 1e-3)
-    return out
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--repeats", type=int, default=20)
-    ap.add_argument("--host_repeats", type=int, default=5)
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("ensemble_rmsd_cost needs an MI355X: a CPU run measures nothing")
-    dev = "cuda:0"
-    lines = [f"device: {torch.cuda.get_device_name(0)}; torch {torch.__version__}; host threads {torch.get_num_threads()}",
-             f"repeats: device {args.repeats} (3 warm-up), host {args.host_repeats} (1 warm-up); times in ms per call", ""]
-
+def body(args, dev, lines):
     lines.append("(i) compute_div per data file, cfg2 shapes: G = 10 members x F = 10 frames (200 superpositions x 2 tables)")
     tot_host, tot_dev = 0.0, 0.0
     for i, L in enumerate(synth.PED_LENGTHS):
@@ -137,13 +95,9 @@ def main():
               f"    device path wall (incl. one sync)         {spread(td)}",
               f"    device path HIP events                    {spread(te)}",
               f"    median wall ratio host / device: {statistics.median(th) / statistics.median(td):.1f}x"]
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text)
 
 
 if __name__ == "__main__":
-    main()
+    main("ensemble_rmsd_cost", body, options=[("--host_repeats", 5)], header=lambda args: (
+        f"; host threads {torch.get_num_threads()}",
+        f"repeats: device {args.repeats} (3 warm-up), host {args.host_repeats} (1 warm-up); times in ms per call"))

@@ -12,7 +12,6 @@ and the radius of gyration.  Wall clock is taken around the whole call including
 also by HIP events; every shape is warmed up; min / median / max over the repeats.  The float64 numpy reference of the tests
 (tests/observables_ref.margins) is timed on ONE structure of the smallest protein at 96 points: what the same decision
 costs on the host.  Needs a GPU: there is nothing to measure without one."""
-import argparse
 import os
 import sys
 import time
@@ -20,10 +19,8 @@ import time
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from codlad_amd import metrics, synth  # noqa: E402
-from geometry_check_cost import events, job, spread, wall  # noqa: E402
+from cost_common import decoded_sections, events, main, metrics, spread, wall  # noqa: E402
 
 
 def measure(title, jobs, repeats, lines):
@@ -64,30 +61,13 @@ def host_reference(jobs, lines):
               f"{dt * 1e3:.1f} ms wall; atoms whose count differs from the device's: {int(((m >= 0).sum(1) != got).sum())}", ""]
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--repeats", type=int, default=20)
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("observables_cost needs an MI355X: a CPU run measures nothing")
-    torch.set_grad_enabled(False)
-    dev = "cuda:0"
-    lines = [f"device: {torch.cuda.get_device_name(0)}; torch {torch.__version__}",
-             f"repeats: {args.repeats} (3 warm-up); times in ms per call; one call = one protein's structures", ""]
-    ped = [(L, job(L, 1000 + i, 10, 10, "N6", "PED", dev)) for i, L in enumerate(synth.PED_LENGTHS)]
-    measure("(i) cfg2 decode output: 4 PED-shaped proteins x (10 frames x 10 members), N6 decoder", ped, args.repeats, lines)
-    L = max(synth.atlas_test_lengths())
-    measure(f"(ii) largest cfg4 protein: L={L}, 1 frame x 32 members, K4 decoder",
-            [(L, job(L, 1, 1, 32, "K4", "Atlas", dev))], args.repeats, lines)
-    host_reference(ped, lines)
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text)
+def body(args, dev, lines):
+    sections = []
+    for title, jobs in decoded_sections(dev):
+        measure(title, jobs, args.repeats, lines)
+        sections.append(jobs)
+    host_reference(sections[0], lines)
 
 
 if __name__ == "__main__":
-    main()
+    main("observables_cost", body)

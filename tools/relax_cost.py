@@ -4,14 +4,13 @@ and the geometry check that judges it.
 
     python tools/relax_cost.py [--out profiles/relax_cost.txt] [--repeats 10] [--n_iter 200]
 
-The two job shapes of tools/geometry_check_cost.py, built by its own `job`: (i) the four synthetic PED proteins of cfg2, 10
+The two job shapes of tools/geometry_check_cost.py, built by cost_common's `job`: (i) the four synthetic PED proteins of cfg2, 10
 frames x 10 members = 100 structures each; (ii) the largest cfg4 protein (505 residues) x 32 members.  Per shape: the decode
 tail, one geometry check, and relax with --n_iter iterations (two launches each, no host synchronisation), by HIP events
 around the whole call; every shape is warmed up; min / median / max over the repeats.  The cost per iteration is the
 difference of a run with --n_iter and one with 0 iterations (start constants, the first evaluation and the trace's first
 column), divided by --n_iter.  Decode and check are the parent commit's code, measured here in the same process.  Needs a
 GPU: there is nothing to measure without one."""
-import argparse
 import os
 import statistics
 import sys
@@ -19,9 +18,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from codlad_amd import metrics, synth  # noqa: E402
-from geometry_check_cost import events, job, spread  # noqa: E402
+from cost_common import decoded_sections, events, main, metrics, spread  # noqa: E402
 
 
 def measure(title, jobs, repeats, n_iter, lines):
@@ -55,31 +52,12 @@ def measure(title, jobs, repeats, n_iter, lines):
     lines.append("")
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--repeats", type=int, default=10)
-    ap.add_argument("--n_iter", type=int, default=200)
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("relax_cost needs an MI355X: a CPU run measures nothing")
-    torch.set_grad_enabled(False)
-    dev = "cuda:0"
-    lines = [f"device: {torch.cuda.get_device_name(0)}; torch {torch.__version__}",
-             f"repeats: {args.repeats} (2 warm-up); times in ms per call; one call = one protein's structures; defaults "
-             f"{metrics.RELAX_DEFAULTS}", ""]
-    measure("(i) cfg2 decode output: 4 PED-shaped proteins x (10 frames x 10 members), N6 decoder",
-            [(L, job(L, 1000 + i, 10, 10, "N6", "PED", dev)) for i, L in enumerate(synth.PED_LENGTHS)], args.repeats, args.n_iter, lines)
-    L = max(synth.atlas_test_lengths())
-    measure(f"(ii) largest cfg4 protein: L={L}, 1 frame x 32 members, K4 decoder",
-            [(L, job(L, 1, 1, 32, "K4", "Atlas", dev))], args.repeats, args.n_iter, lines)
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text)
+def body(args, dev, lines):
+    for title, jobs in decoded_sections(dev):
+        measure(title, jobs, args.repeats, args.n_iter, lines)
 
 
 if __name__ == "__main__":
-    main()
+    main("relax_cost", body, repeats=10, options=[("--n_iter", 200)], header=lambda args: (
+        "", f"repeats: {args.repeats} (2 warm-up); times in ms per call; one call = one protein's structures; defaults "
+            f"{metrics.RELAX_DEFAULTS}"))

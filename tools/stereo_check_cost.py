@@ -4,14 +4,13 @@
 
     python tools/stereo_check_cost.py [--out profiles/stereo_check_cost.txt] [--repeats 20]
 
-The shapes and the decoded input are those of tools/geometry_check_cost.py (its `job`):
+The shapes and the decoded input are those of tools/geometry_check_cost.py (cost_common's `job`):
 (i)  the cfg2 decode output: the four synthetic PED proteins, 10 frames x 10 members = 100 structures each;
 (ii) the largest cfg4 protein (505 residues, K4 decoder) x 32 members of one frame.
 Both checks run on the SAME xyz tensor, alternating within a repeat.  Device time by HIP events around one call (the
 launch and its memset), wall clock around the call and its one synchronisation; every shape is warmed up; min / median /
 max over the repeats.  The site table of a topology is built once on the host and cached on it: the first call's wall
 clock is reported apart.  There is no threshold: this tool reports, it does not judge.  Needs a GPU."""
-import argparse
 import os
 import statistics
 import sys
@@ -19,10 +18,8 @@ import time
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from codlad_amd import metrics, synth  # noqa: E402
-from geometry_check_cost import events, job, spread, wall  # noqa: E402
+from cost_common import decoded_sections, events, main, metrics, spread, wall  # noqa: E402
 
 
 def measure(title, jobs, repeats, lines):
@@ -66,29 +63,10 @@ def measure(title, jobs, repeats, lines):
     lines += [f"  sum of medians (HIP events): stereo check {tot['stereo'] * 1e3:.3f} ms, geometry check {tot['geometry'] * 1e3:.3f} ms", ""]
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--repeats", type=int, default=20)
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("stereo_check_cost needs an MI355X: a CPU run measures nothing")
-    torch.set_grad_enabled(False)
-    dev = "cuda:0"
-    lines = [f"device: {torch.cuda.get_device_name(0)}; torch {torch.__version__}",
-             f"repeats: {args.repeats} (3 warm-up); times in ms per call; one call = one protein's structures", ""]
-    measure("(i) cfg2 decode output: 4 PED-shaped proteins x (10 frames x 10 members), N6 decoder",
-            [(L, job(L, 1000 + i, 10, 10, "N6", "PED", dev)) for i, L in enumerate(synth.PED_LENGTHS)], args.repeats, lines)
-    L = max(synth.atlas_test_lengths())
-    measure(f"(ii) largest cfg4 protein: L={L}, 1 frame x 32 members, K4 decoder",
-            [(L, job(L, 1, 1, 32, "K4", "Atlas", dev))], args.repeats, lines)
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text)
+def body(args, dev, lines):
+    for title, jobs in decoded_sections(dev):
+        measure(title, jobs, args.repeats, lines)
 
 
 if __name__ == "__main__":
-    main()
+    main("stereo_check_cost", body)
