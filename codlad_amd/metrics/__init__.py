@@ -1,7 +1,7 @@
 """The evaluation and structure-analysis entry points, one module per concern; every public name is read from here
 (`from codlad_amd import metrics; metrics.X`).  recon: the reference's test-loop metrics; ensemble: superposed RMSD and
 diversity; geometry, stereo: the reference-free checks; relax: the clash relaxation; observables: SASA, Rg, contact maps;
-dssp: secondary structure; _inputs: what they share."""
+dssp: secondary structure; saxs: scattering profiles; _inputs: what they share."""
 from .. import _lib   # noqa: F401
 from ._inputs import COV_CUTOFF, exclusion_csr   # noqa: F401
 from .recon import *   # noqa: F401,F403 (every public name of a module, C and torch among them as in the module this replaced)
@@ -14,3 +14,5 @@ from .relax import _relax_table_args, _relax_tables_on   # noqa: F401
 from .observables import *   # noqa: F401,F403
 from .observables import _res_table, _sasa_atom_tables   # noqa: F401
 from .dssp import *   # noqa: F401,F403
+from .saxs import *   # noqa: F401,F403
+from .saxs import _saxs_tables   # noqa: F401

@@ -1095,6 +1095,67 @@ int codlad_selftest_gemm128(const float *W_packed, const float *bias, const floa
 int codlad_selftest_gemm128_h(const void *W_split, const float *bias, const float *X, int n_rows,
                               int act_in, int terms, float *Y, void *stream);
 
+/* Small-angle X-ray scattering (csrc/saxs_kernels.hip): the Debye sum of n_struct structures xyz [n_struct][n_atoms][3]
+ * that share ONE topology.  Added to ABI version 19 without changing the number: one new entry point, no existing
+ * signature, struct or option changes.  With f_i(k) = ff[type[i]][k] (type: device int32 [n_atoms], ff: device float
+ * [n_types][n_q], q: device float [n_q], 1/A),
+ *   I[s][k] = sum_i f_i(k)^2 + 2 sum_{i<j} f_i(k) f_j(k) sinc(q_k r_ij),  sinc(x) = sin(x) / x, sinc(0) = 1.
+ * Per pair i < j and per k, fp32 with one rounding per operation in the written order (no contraction; sqrtf and the
+ * division are the correctly rounded ones):
+ *   d = x_j - x_i per component, r = sqrtf((dx*dx + dy*dy) + dz*dz), inv_r = 1 / r, inv_q_k = 1 / q_k
+ *   x = q_k * r
+ *   sine:   kf = rint(x * INV_PI) (round to nearest, ties to even)
+ *           y  = ((x - kf * P1) - kf * P2) - kf * P3           Cody-Waite: kf * P1 and kf * P2 are exact up to X_MAX
+ *           s  = y * y
+ *           p  = (((S11 * s + S9) * s + S7) * s + S5) * s + S3  ten operations, Horner
+ *           v  = y + (y * s) * p;   sin = kf odd ? -v : v        (the parity of (int)kf flips the sign bit)
+ *   main   = (sin * inv_r) * inv_q_k
+ *   series = 1 - (x2 * C6) * (1 - x2 * C20), x2 = x * x         = 1 - x^2/6 (1 - x^2/20), no division: r = 0 and q = 0
+ *   sinc   = x < X_SMALL ? series : main                        a selection, both sides are evaluated
+ *   term   = f_j(k) * sinc
+ * The same sequence runs beyond X_MAX, with no branch and no fault; the accuracy claim stops there: up to X_MAX the
+ * sine is within CODLAD_SAXS_SIN_ULPS * 2^-24 of sin(x) of the fp32 x (1 from the one rounding of the reduction, 0.7 from
+ * the polynomial with its coefficients rounded, 2.3 from the roundings of s, y * s, the product with p and the last sum,
+ * the rest for the Horner steps).  Beyond it kf * P2 is no longer exact and the error grows with x. */
+#define CODLAD_SAXS_INV_PI 0x1.45f306p-2f
+#define CODLAD_SAXS_P1 0x1.92p+1f
+#define CODLAD_SAXS_P2 0x1.fb4p-11f
+#define CODLAD_SAXS_P3 0x1.4442d2p-23f
+#define CODLAD_SAXS_S3 -0x1.555556p-3f
+#define CODLAD_SAXS_S5 0x1.11111p-7f
+#define CODLAD_SAXS_S7 -0x1.a019ccp-13f
+#define CODLAD_SAXS_S9 0x1.71c83ap-19f
+#define CODLAD_SAXS_S11 -0x1.a5a3eap-26f
+#define CODLAD_SAXS_C6 0x1.555556p-3f
+#define CODLAD_SAXS_C20 0x1.99999ap-5f
+#define CODLAD_SAXS_X_MAX 0x1.9p+14f     /* 25600: kf <= 8149 < 2^13, P1 has 8 significant bits and P2 11 */
+#define CODLAD_SAXS_X_SMALL 0x1p-3f      /* the series' next term, x^6 / 5040, is below 2^-30 there */
+#define CODLAD_SAXS_SIN_ULPS 5
+/* Accumulation.  The atoms form B = (n_atoms + 63) / 64 blocks of 64; workgroup (s, p), p < P = (B + 1) / 2, owns the row
+ * blocks p and B - 1 - p (once when they are the same), lane l of each of its four waves the atom i = 64 * block + l.
+ * Wave w takes the partner tiles t = block + w, block + w + 4, ... < B of a row block, each the atoms 64 t .. 64 t + 63.
+ *   fp32:    a lane's terms of ONE tile (at most 64) for one k, added to 0 in ascending j; a partner j <= i adds 0
+ *   float64: D = the tiles' fp32 sums, converted, added to 0 in ascending t
+ *            E = sum over the row blocks, p first, of (2 * (f_i(k) * D) + self), self = f_i(k) * f_i(k) in wave 0 and 0
+ *                in the others; an atom i >= n_atoms counts as f_i = 0
+ *            the wave's 64 lanes: for stride = 32, 16, .. 1: E[l] += E[l ^ stride]; the four waves:
+ *                ((E_0 + E_1) + E_2) + E_3 = partial[s][p][k]
+ *            I[s][k] = the partials added to 0 in ascending p, by a second launch
+ * partial: device double [n_struct][P][n_q], scratch of the call (every element of a finite structure is written before
+ * it is read).  A type outside [0, n_types) is read as the nearest valid one; the caller checks the tables' contents.
+ * Outputs (device): I double [n_struct][n_q]; finite uint8 [n_struct], as for codlad_sasa: a structure with a coordinate
+ * that is NaN or +-inf gets finite = 0 and NaN in its row, the others keep their bits; mean double [n_q] (may be NULL, a
+ * fourth launch): the rows of the finite structures added to 0 in ascending s, divided by their number in float64, NaN
+ * when there is none.  No atomics, sums in one order:
+ * results are bit-identical from call to call and a structure's results do not depend on n_struct or on its place in the
+ * call (mean is the one result that spans it).  A null pointer, n_struct / n_atoms / n_types / n_q <= 0, n_q > CODLAD_SAXS_MAX_Q, n_types >
+ * CODLAD_SAXS_MAX_TYPES, n_struct * P >= 2^31 or 3 * n_atoms >= 2^31 returns -1 (codlad_last_error) before any launch. */
+#define CODLAD_SAXS_MAX_Q 512
+#define CODLAD_SAXS_MAX_TYPES 32
+#define CODLAD_SAXS_Q_CHUNK 16           /* the k values a lane carries at a time (the tests walk its edges) */
+int codlad_saxs_debye(const float *xyz, int n_struct, int n_atoms, const int32_t *type, int n_types, const float *ff,
+                      const float *q, int n_q, double *partial, double *I, double *mean, uint8_t *finite, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

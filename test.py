@@ -45,6 +45,10 @@ points per atom), the radius of gyration of every structure and the CA contact-f
 Addition: `--dssp` (opt-in, wherever --geometry_check is allowed; after --relax when both are given) assigns the secondary
 structure of every written structure on the device (metrics.dssp: Kabsch-Sander hydrogen bonds, DSSP states) and the
 propensity of each state per residue over the file's structures.
+Addition: `--saxs [N_Q]` (opt-in, wherever --observables is allowed; after --relax when both are given) computes the
+small-angle X-ray scattering profile of every written structure on the device (metrics.saxs_profile: the Debye sum over
+all atom pairs, united-atom form factors in a displaced solvent) on N_Q points of [0, 0.5] 1/A, or on the q grid of
+`--saxs_data FILE` (q, I, sigma columns), against which the ensemble mean is then scaled and its reduced chi^2 printed.
 """
 import argparse
 import os
@@ -220,6 +224,45 @@ def check_observables(args):
     return n
 
 
+def check_saxs(args):
+    """Where --saxs applies: exactly where --observables does.  Returns the number of q values, 0 = off."""
+    n = getattr(args, "saxs", None)
+    if n is None:
+        if getattr(args, "saxs_data", None):
+            raise SystemExit("--saxs_data needs --saxs: the curve is compared with the profile --saxs computes")
+        args.saxs = 0
+        return 0
+    if not 1 <= n <= metrics.SAXS_MAX_Q:
+        raise SystemExit(f"--saxs takes a number of q values in 1 .. {metrics.SAXS_MAX_Q}, got {n}")
+    if not getattr(args, "cg_pdb", None):
+        if args.experiment in ("bpd", "fmloss"):
+            raise SystemExit(f"--saxs describes generated structures: --experiment {args.experiment} generates none")
+        if args.data_process and not args.synthetic:
+            raise SystemExit("--saxs needs the topology of the structures: --data_process pickles carry none "
+                             "(use --pdb_files, --cg_pdb or --synthetic)")
+    return n
+
+
+def read_saxs_data(path):
+    """--saxs_data: three whitespace-separated columns q (1/A), I, sigma; `#` starts a comment -> three float64 arrays."""
+    rows = []
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            cols = line.split("#", 1)[0].split()
+            if not cols:
+                continue
+            try:
+                if len(cols) != 3:
+                    raise ValueError
+                rows.append([float(c) for c in cols])
+            except ValueError:
+                raise SystemExit(f"--saxs_data {path}, line {no}: three columns of numbers are needed (q, I, sigma)") from None
+    if len(rows) < 2:
+        raise SystemExit(f"--saxs_data {path}: two rows or more are needed")
+    q, I, sigma = np.array(rows, dtype=np.float64).T
+    return q, I, sigma
+
+
 def check_dssp(args):
     """Where --dssp applies: exactly where --geometry_check does (structures are generated and their topology is known; the
     refusals of --cg_pdb itself are check_cg_input's).  Returns whether it is on."""
@@ -379,7 +422,7 @@ def iter_batches(args):
             names = [synth.IDX2THR[int(z)] for z in prot["z_full"]]
             geom_top = None
             if getattr(args, "geometry_check", False) or getattr(args, "stereo_check", False) or getattr(args, "relax", 0) \
-                    or getattr(args, "observables", 0) or getattr(args, "dssp", False):
+                    or getattr(args, "observables", 0) or getattr(args, "dssp", False) or getattr(args, "saxs", 0):
                 from codlad_amd.utils.cg_input import template_topology
                 geom_top = template_topology(names[1:-1])             # one Topology (and one set of device tables) per protein
             for c, (a, b) in enumerate(plan):
@@ -553,6 +596,26 @@ def observables_report(name, obs):
     return stats
 
 
+def saxs_report(name, sx, data=None):
+    """The printed summary of --saxs for one output file (sx: metrics.saxs_profile's dict; data: read_saxs_data's curve on
+    the same q grid, or None) -> the stats."""
+    q, mean = sx["q"].cpu().numpy(), sx["mean"].cpu().numpy()
+    fin = sx["finite"]
+    stats = {"data_name": name, "structures": int(fin.shape[0]), "saxs_non_finite": int((~fin).sum()), "saxs_I0": float(mean[0])}
+    picks = sorted({len(q) // 4, len(q) // 2, len(q) - 1})
+    for k in picks:
+        stats[f"saxs_mean_q{float(q[k]):.4f}"] = float(mean[k])
+    if data is not None:
+        fit = metrics.saxs_fit(sx["mean"], data[0], data[1], data[2])
+        stats["saxs_scale"], stats["saxs_chi2"] = float(fit["scale"]), float(fit["chi2"])
+    print("############## vvvvvvvvv SAXS profile (Debye sum, ensemble mean; q in 1/A):")
+    print(f"I({float(q[0]):.4f}) {stats['saxs_I0']:.6g}   " + "   ".join(f"I({float(q[k]):.4f}) {float(mean[k]):.6g}" for k in picks))
+    for k, v in stats.items():
+        print(k, v)
+    print("############## ^^^^^^^^^ SAXS profile")
+    return stats
+
+
 def dssp_report(name, sec, propensity):
     """The printed summary of --dssp for one output file (sec: metrics.dssp's dict, propensity: metrics.ss_propensity of its
     labels) -> the stats: the mean share of helix (H + G + I), strand (E + B) and coil (the rest) over residues and finite
@@ -635,8 +698,10 @@ def main(args):
     check_stereo(args)
     check_relax(args)
     check_observables(args)
+    check_saxs(args)
     check_dssp(args)
     check_sampler(args)
+    saxs_data = read_saxs_data(args.saxs_data) if getattr(args, "saxs_data", None) else None
     if not torch.cuda.is_available():
         raise SystemExit("test.py (codlad_amd) needs an MI355X: there is no CPU path")
     # one process per GPU under torch.distributed.run: batches (independent units) are dealt to the
@@ -826,6 +891,12 @@ def main(args):
             if name not in _GEOMETRY_TOP:
                 raise SystemExit(f"--observables: the topology of {name} is not known on this input route")
             obs = observables(xyz.reshape(-1, xyz.shape[2], 3), _GEOMETRY_TOP[name], args.observables)    # the written coordinates
+        sx = None
+        if getattr(args, "saxs", 0):
+            if name not in _GEOMETRY_TOP:
+                raise SystemExit(f"--saxs: the topology of {name} is not known on this input route")
+            sx = metrics.saxs_profile(xyz.reshape(-1, xyz.shape[2], 3), _GEOMETRY_TOP[name],                # the written coordinates
+                                      q=saxs_data[0] if saxs_data is not None else np.linspace(0.0, 0.5, args.saxs))
         sec = None
         if getattr(args, "dssp", False):
             if name not in _GEOMETRY_TOP:
@@ -863,6 +934,10 @@ def main(args):
             np.save(os.path.join(save_dir, f"{name}_rg.npy"), obs["rg"].cpu().numpy())                            # [E * B]
             np.save(os.path.join(save_dir, f"{name}_ca_contacts.npy"), obs["contacts"]["frequency"].cpu().numpy())  # [R, R]
             observables_report(name, obs)
+        if sx is not None:
+            np.save(os.path.join(save_dir, f"{name}_saxs.npy"), sx["I"].cpu().numpy())                    # float64 [E * B, N_Q]
+            np.save(os.path.join(save_dir, f"{name}_saxs_q.npy"), sx["q"].cpu().numpy())                  # float32 [N_Q]
+            saxs_report(name, sx, saxs_data)
         if sec is not None:
             np.save(os.path.join(save_dir, f"{name}_dssp.npy"), sec["ss"].cpu().numpy())                  # uint8 [E * B, R]
             np.save(os.path.join(save_dir, f"{name}_dssp_propensity.npy"), sec_prop.cpu().numpy())       # float64 [R, 8]
@@ -981,6 +1056,16 @@ if __name__ == "__main__":
                         "960; metrics.sasa), radius of gyration, CA contacts at 8 A.  Prints mean +- sd of Rg and of the total "
                         "SASA; saves <name>_sasa_residue.npy [structures, R], <name>_rg.npy [structures] and "
                         "<name>_ca_contacts.npy [R, R] = the fraction of structures with the two CAs closer than 8 A")
+    p.add_argument("--saxs", nargs="?", type=int, const=51, default=None, metavar="N_Q",
+                   help="also compute the small-angle X-ray scattering profile of every written structure on the device "
+                        "(allowed wherever --observables is; after --relax when both are given): the Debye sum over all atom "
+                        "pairs with united-atom form factors in a displaced solvent (metrics.saxs_profile) on N_Q points of "
+                        "[0, 0.5] 1/A (default 51).  Prints I(0) and the ensemble mean at three q values; saves <name>_saxs.npy "
+                        "float64 [structures, N_Q] and <name>_saxs_q.npy")
+    p.add_argument("--saxs_data", default=None, metavar="FILE",
+                   help="an experimental curve for --saxs: three whitespace-separated columns q (1/A), I, sigma, `#` starts a "
+                        "comment.  Its q values replace the grid of --saxs (there is no interpolation); the scale and the "
+                        "reduced chi^2 of the ensemble mean against it are printed")
     p.add_argument("--dssp", action="store_true",
                    help="also assign the secondary structure of every written structure on the device (allowed wherever "
                         "--geometry_check is; after --relax when both are given): Kabsch-Sander hydrogen bonds and the DSSP "
