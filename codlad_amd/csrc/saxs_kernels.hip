@@ -14,6 +14,7 @@
 // parity), not the hardware instruction and not a library call: the float32 restatement of the tests performs the same
 // operations.  -ffp-contract=off: one rounding per operation, in fp32 and in float64.
 #include "common.h"
+#include "saxs_math.h"
 #include "structure_math.h"
 
 namespace {
@@ -28,30 +29,6 @@ __global__ __launch_bounds__(THREADS) void finite_kernel(const float *xyz, int n
     for (int k = threadIdx.x; k < n3; k += THREADS) bad |= non_finite(x[k]);
     bad = __syncthreads_or(bad);
     if (threadIdx.x == 0) finite[blockIdx.x] = bad ? 0 : 1;
-}
-
-__device__ inline float lane_read(float v, int lane) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
-
-// sin(x) for x >= 0, the header's sequence
-__device__ inline float sin_cw(float x) {
-    const float kf = __builtin_rintf(x * CODLAD_SAXS_INV_PI);
-    const float y = ((x - kf * CODLAD_SAXS_P1) - kf * CODLAD_SAXS_P2) - kf * CODLAD_SAXS_P3;
-    const float s = y * y;
-    float p = CODLAD_SAXS_S11 * s + CODLAD_SAXS_S9;
-    p = p * s + CODLAD_SAXS_S7;
-    p = p * s + CODLAD_SAXS_S5;
-    p = p * s + CODLAD_SAXS_S3;
-    const float v = y + (y * s) * p;
-    return __uint_as_float(__float_as_uint(v) ^ ((uint32_t)(int)kf << 31));
-}
-
-__device__ inline float sinc_term(float x, float sn, float inv_r, float inv_q) {
-    const float far = (sn * inv_r) * inv_q;
-    const float x2 = x * x;
-    const float series = 1.0f - (x2 * CODLAD_SAXS_C6) * (1.0f - x2 * CODLAD_SAXS_C20);
-    return x < CODLAD_SAXS_X_SMALL ? series : far;
 }
 
 __global__ __launch_bounds__(THREADS) void saxs_pair_kernel(const float *xyz, int n, int n_blocks, int n_wg, const int32_t *type,

@@ -1,6 +1,9 @@
 """Small-angle X-ray scattering profiles of an ensemble (codlad_saxs_debye, csrc/saxs_kernels.hip): the Debye sum over all
 atom pairs of every structure, with united-atom form factors (a heavy atom and the hydrogens riding on it) in a displaced
-solvent.  No hydration shell, no fitted contrast, no interpolation between q grids."""
+solvent; and the hydration model on top of it (codlad_saxs_partials, codlad_saxs_hydration_fit,
+csrc/saxs_hydration_kernels.hip): six partial Debye sums from one pass over the pairs, from which the profile at any
+excluded-volume scale c1 and hydration-shell weight c2 is a float64 combination, and the fit of both to a curve.  No
+interpolation between q grids."""
 import numpy as np
 import torch
 
@@ -204,3 +207,185 @@ def saxs_fit(I_calc, q, I_exp, sigma):
     scale = (exp * calc * w).sum() / (calc * calc * w).sum()
     chi2 = (((scale * calc - exp) / sig) ** 2).sum() / float(calc.shape[0] - 1)
     return dict(scale=scale, chi2=chi2)
+
+
+# ---------------------------------------------------------------------------------- hydration shell and fitted contrast --
+SAXS_HYD_PARTIALS, SAXS_HYD_Q_CHUNK, SAXS_HYD_MAX_GRID = _lib.SAXS_HYD_PARTIALS, _lib.SAXS_HYD_Q_CHUNK, _lib.SAXS_HYD_MAX_GRID
+SAXS_PARTIAL_NAMES = ("tt", "td", "dd", "ts", "ds", "ss")
+SAXS_R_M = 1.62                    # A: the mean atomic radius of the expansion factor (CRYSOL, FoXS)
+
+
+def default_c1():
+    """FoXS's range of the excluded-volume scale: 0.95 .. 1.05 in steps of 0.005."""
+    return np.arange(21, dtype=np.float64) * 0.005 + 0.95
+
+
+def default_c2():
+    """FoXS's range of the hydration-shell weight: -2.0 .. 4.0 in steps of 0.1."""
+    return np.arange(61, dtype=np.float64) * 0.1 - 2.0
+
+
+def expansion_factor(q, c1, r_m=SAXS_R_M):
+    """float64 numpy [len(c1), Q]: G(q, c1) = c1^3 exp(-(4 pi / 3)^(3/2) q^2 r_m^2 (c1^2 - 1) / (4 pi)), the scale of the
+    displaced-solvent term when every atomic volume grows by c1^3 (CRYSOL / FoXS); G(q, 1) = 1 exactly."""
+    q = np.asarray(q, dtype=np.float64).reshape(1, -1)
+    c1 = np.asarray(c1, dtype=np.float64).reshape(-1, 1)
+    return c1 ** 3 * np.exp(-((4.0 * np.pi / 3.0) ** 1.5 * q * q * float(r_m) ** 2 * (c1 * c1 - 1.0)) / (4.0 * np.pi))
+
+
+def _partials_launch(xyz, typ, ff_t, ff_d, weight, q, with_mean=False):
+    x = _inputs.structures(xyz, "saxs: xyz", typ.shape[0])
+    dev = x.device
+    S, n, Q = x.shape[0], x.shape[1], q.shape[0]
+    _inputs.need_cuda(weight, "saxs: weight")
+    if tuple(weight.shape) != (S, n):
+        raise ValueError(f"saxs: weight must be [S, n_atoms] = {(S, n)}, one number per atom of every structure, got {tuple(weight.shape)}")
+    wt = weight.detach().to(torch.float32).contiguous()
+    n_wg = ((n + 63) // 64 + 1) // 2
+    partial = torch.empty(S, n_wg, SAXS_HYD_PARTIALS, Q, dtype=torch.float64, device=dev)
+    P = torch.empty(S, SAXS_HYD_PARTIALS, Q, dtype=torch.float64, device=dev)
+    mean = torch.empty(SAXS_HYD_PARTIALS, Q, dtype=torch.float64, device=dev) if with_mean else None
+    finite = torch.empty(S, dtype=torch.uint8, device=dev)
+    p = _lib.ptr
+    rc = _lib.lib().codlad_saxs_partials(p(x), S, n, p(typ), ff_t.shape[0], p(ff_t), p(ff_d), p(wt), p(q), Q, p(partial), p(P),
+                                         p(mean), p(finite), _lib.stream_ptr(dev))
+    _lib.check(rc, "codlad_saxs_partials")
+    out = dict(P=P, finite=finite.to(torch.bool))
+    if with_mean:
+        out["mean"] = mean
+    return out
+
+
+def saxs_partials_lists(xyz, types, table_t, table_d, weight, q):
+    """The six partial Debye sums of the hydration model: xyz [S, n_atoms, 3] (device), types int [n_atoms] in [0, T),
+    table_t and table_d [T, Q] (in-solvent form factor and displaced solvent of every type; rounded to float32), weight
+    [S, n_atoms] (device; the exposed fraction s_i of every atom of every structure) and q [Q] -> dict: P float64
+    [S, 6, Q] (device) in the order SAXS_PARTIAL_NAMES, P_ab = sum_i a_i b_i + sum_{i<j} (a_i b_j + b_i a_j) sinc(q r_ij);
+    finite bool [S], False where a coordinate or a weight is NaN or +-inf (six rows of NaN).  P[:, 0] has the bits of
+    saxs_profile_lists(xyz, types, table_t, q)["I"].  The refusals of saxs_profile_lists, for both tables."""
+    _inputs.need_cuda(xyz, "saxs: xyz")
+    typ, ff_t, qd = _saxs_tables(types, table_t, q, xyz.device)
+    _typ, ff_d, _q = _saxs_tables(types, table_d, q, xyz.device)
+    return _partials_launch(xyz, typ, ff_t, ff_d, weight, qd)
+
+
+def saxs_partials(xyz, top, q=None, solvent_density=0.334, probe=1.4, n_points=960):
+    """The partial profiles of xyz [S, n_atoms, 3] (device), S structures of the topology `top`, from which saxs_combine
+    and saxs_hydration_fit make I(q; c1, c2) -> dict of device tensors:
+      q float32 [Q]              as saxs_profile
+      P float64 [S, 6, Q]        tt, td, dd, ts, ds, ss of t = form_factors(q, groups, solvent_density), d = form_factors(q,
+                                 groups, 0) - t and s = exposure; P[:, 0] has the bits of saxs_profile's I
+      mean float64 [6, Q]        the average over the finite structures, added in index order; NaN if there is none
+      finite bool [S], n_finite  as saxs_profile
+      exposure float32 [S, n]    sasa(xyz, top, probe, n_points)["exposed"] / n_points: the share of an atom's test points
+                                 that no other atom's sphere contains (computed on the device, no host transfer)
+      water float64 [Q]          form_factors(q, [("O", 2)], solvent_density): the form factor of a shell water
+    The tables are built once per (topology, q, solvent_density, device)."""
+    from .observables import sasa
+    _inputs.need_cuda(xyz, "saxs: xyz")
+    q64 = _host(default_q() if q is None else q, np.float64).reshape(-1)
+
+    def build():
+        groups, types = saxs_groups(top)
+        t = form_factors(q64, groups, solvent_density)
+        typ, ff_t, qd = _saxs_tables(types, t, q64, xyz.device)
+        _typ, ff_d, _q = _saxs_tables(types, form_factors(q64, groups, 0.0) - t, q64, xyz.device)
+        water = torch.from_numpy(form_factors(q64, [("O", 2)], solvent_density)[0].copy()).to(xyz.device)
+        return typ, ff_t, ff_d, qd, water
+    typ, ff_t, ff_d, qd, water = _inputs.cached(top, "_saxs_hydration_tables",
+                                                (q64.tobytes(), float(solvent_density), str(xyz.device)), build)
+    exposure = sasa(xyz, top, probe=probe, n_points=n_points)["exposed"] / n_points
+    out = _partials_launch(xyz, typ, ff_t, ff_d, exposure, qd, with_mean=True)
+    return dict(q=qd, P=out["P"], mean=out["mean"], finite=out["finite"], n_finite=out["finite"].sum(), exposure=exposure,
+                water=water)
+
+
+def _hydration_tables(what, shape, q, water, c1, c2, r_m):
+    """The host side of codlad_saxs_hydration_fit's arguments, checked: P's shape [..., 6, Q], q and water [Q], the grids
+    -> float64 numpy (f_w [Q], G [len(c1), Q], c1, c2)."""
+    if len(shape) < 2 or shape[-2] != SAXS_HYD_PARTIALS or shape[-1] < 1 or 0 in shape:
+        raise ValueError(f"{what}: P must be [..., {SAXS_HYD_PARTIALS}, Q] (the partial profiles of saxs_partials), got {tuple(shape)}")
+    Q = shape[-1]
+    q64 = _host(q, np.float64).reshape(-1)
+    fw = _host(water, np.float64).reshape(-1)
+    if q64.shape[0] != Q or fw.shape[0] != Q or Q > SAXS_MAX_Q:
+        raise ValueError(f"{what}: q and water must have the Q = {Q} <= {SAXS_MAX_Q} values of P, got {q64.shape[0]} and {fw.shape[0]}")
+    if not (np.isfinite(q64).all() and (q64 >= 0).all() and (q64 <= SAXS_Q_LIMIT).all()):
+        raise ValueError(f"{what}: every q must be a number in [0, {SAXS_Q_LIMIT}] 1/A")
+    g1, g2 = _host(c1, np.float64).reshape(-1), _host(c2, np.float64).reshape(-1)
+    if not g1.shape[0] or not g2.shape[0] or g1.shape[0] * g2.shape[0] > SAXS_HYD_MAX_GRID:
+        raise ValueError(f"{what}: the grid of c1 and c2 must have 1 .. {SAXS_HYD_MAX_GRID} points, got {g1.shape[0]} x {g2.shape[0]}")
+    if not (np.isfinite(g1).all() and (g1 > 0).all() and np.isfinite(g2).all() and np.isfinite(float(r_m)) and float(r_m) >= 0):
+        raise ValueError(f"{what}: every c1 must be positive, every c2 a number and r_m non-negative")
+    return fw, expansion_factor(q64, g1, r_m), g1, g2
+
+
+def _fit_curves(Q, I_exp, sigma):
+    """I_exp and sigma of saxs_hydration_fit, checked -> float64 numpy [Q] each."""
+    exp, sig = _host(I_exp, np.float64).reshape(-1), _host(sigma, np.float64).reshape(-1)
+    if exp.shape[0] != Q or sig.shape[0] != Q or Q < 2:
+        raise ValueError(f"saxs_hydration_fit: I_exp and sigma must have the Q = {Q} >= 2 values of P, got {exp.shape[0]} and {sig.shape[0]}")
+    if not (sig > 0).all():
+        raise ValueError("saxs_hydration_fit: every sigma must be positive")
+    return exp, sig
+
+
+def _hydration_inputs(what, P, q, water, c1, c2, r_m):
+    """-> (P [B, 6, Q] float64, the shape of P before the 6-axis, f_w, G, c2 on the device of P, and the grids as numpy)."""
+    _inputs.need_cuda(P, f"{what}: P")
+    fw, G, g1, g2 = _hydration_tables(what, tuple(P.shape), q, water, c1, c2, r_m)
+    dev = P.device
+    up = lambda a: torch.from_numpy(np.array(a, dtype=np.float64)).to(dev)     # noqa: E731 (a copy: the caller's may be read-only)
+    Pb = P.detach().to(torch.float64).reshape(-1, SAXS_HYD_PARTIALS, P.shape[-1]).contiguous()
+    return Pb, tuple(P.shape[:-2]), up(fw), up(G), up(g2), g1, g2
+
+
+def saxs_combine(P, q, water, c1=1.0, c2=0.0, r_m=SAXS_R_M):
+    """I(q; c1, c2) of partial profiles P [..., 6, Q] (device; saxs_partials' P or mean) -> float64 [..., Q]:
+      I = P_tt + 2 (1 - G) P_td + (1 - G)^2 P_dd + 2 c2 f_w P_ts + 2 c2 f_w (1 - G) P_ds + c2^2 f_w^2 P_ss
+    with G = expansion_factor(q, c1, r_m) and f_w = water, in float64 in the order include/codlad_hip.h states.  c1 scales
+    the excluded volume (c1 = 1: as saxs_profile), c2 weighs the bound water on the exposed atoms.  (1, 0) returns P_tt."""
+    Pb, lead, fw, G, g2, _g1, _g2 = _hydration_inputs("saxs_combine", P, q, water, [float(c1)], [float(c2)], r_m)
+    I = torch.empty(Pb.shape[0], 1, Pb.shape[2], dtype=torch.float64, device=Pb.device)
+    p = _lib.ptr
+    rc = _lib.lib().codlad_saxs_hydration_fit(p(Pb), Pb.shape[0], Pb.shape[2], p(fw), p(G), 1, p(g2), 1, None, None, p(I), None,
+                                              None, None, None, _lib.stream_ptr(Pb.device))
+    _lib.check(rc, "codlad_saxs_hydration_fit")
+    return I.reshape(*lead, Pb.shape[2])
+
+
+def saxs_hydration_fit(P, q, water, I_exp, sigma, c1=None, c2=None, r_m=SAXS_R_M):
+    """The (c1, c2) of a grid at which partial profiles P [6, Q] or [B, 6, Q] (device) fit an experiment on the SAME q
+    grid best: for every grid point the scale and the reduced chi^2 of saxs_fit (sums over q ascending), then the smallest
+    chi^2 - the lowest flat index i1 * len(c2) + i2 of a tie; a chi^2 that is not finite never wins.  c1, c2: the grids
+    (default default_c1() x default_c2(), FoXS's ranges; at most SAXS_HYD_MAX_GRID points) -> dict of device tensors, with a
+    leading [B] for a batch:
+      c1, c2, scale, chi2 float64   at the best point (NaN when no chi^2 is finite)
+      index int32                   its flat index, -1 when there is none
+      I float64 [Q]                 the profile there (unscaled)
+      chi2_grid, scale_grid float64 [len(c1), len(c2)]
+    For an ensemble pass saxs_partials' mean: the fit is of the ensemble, not of a structure."""
+    Pb, lead, fw, G, g2d, g1, g2 = _hydration_inputs("saxs_hydration_fit", P, q, water, default_c1() if c1 is None else c1,
+                                                     default_c2() if c2 is None else c2, r_m)
+    if len(lead) > 1:
+        raise ValueError(f"saxs_hydration_fit: P must be [6, Q] or [B, 6, Q], got {tuple(P.shape)}")
+    B, Q, n1, n2 = Pb.shape[0], Pb.shape[2], g1.shape[0], g2.shape[0]
+    exp, sig = _fit_curves(Q, I_exp, sigma)
+    dev = Pb.device
+    exp_d, sig_d = torch.from_numpy(exp.copy()).to(dev), torch.from_numpy(sig.copy()).to(dev)
+    scale = torch.empty(B, n1 * n2, dtype=torch.float64, device=dev)
+    chi2 = torch.empty(B, n1 * n2, dtype=torch.float64, device=dev)
+    best = torch.empty(B, dtype=torch.int32, device=dev)
+    I = torch.empty(B, Q, dtype=torch.float64, device=dev)
+    p = _lib.ptr
+    rc = _lib.lib().codlad_saxs_hydration_fit(p(Pb), B, Q, p(fw), p(G), n1, p(g2d), n2, p(exp_d), p(sig_d), None, p(scale), p(chi2),
+                                              p(best), p(I), _lib.stream_ptr(dev))
+    _lib.check(rc, "codlad_saxs_hydration_fit")
+    at = best.to(torch.int64).clamp(min=0)
+    none = best < 0
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+    pick = lambda t: torch.where(none, nan, t)                                                      # noqa: E731
+    out = dict(c1=pick(torch.from_numpy(g1.copy()).to(dev)[at // n2]), c2=pick(g2d[at % n2]),
+               scale=pick(scale.gather(1, at[:, None])[:, 0]), chi2=pick(chi2.gather(1, at[:, None])[:, 0]), I=I, index=best,
+               chi2_grid=chi2.reshape(B, n1, n2), scale_grid=scale.reshape(B, n1, n2))
+    return out if lead else {k: v[0] for k, v in out.items()}

@@ -1156,6 +1156,62 @@ int codlad_selftest_gemm128_h(const void *W_split, const float *bias, const floa
 int codlad_saxs_debye(const float *xyz, int n_struct, int n_atoms, const int32_t *type, int n_types, const float *ff,
                       const float *q, int n_q, double *partial, double *I, double *mean, uint8_t *finite, void *stream);
 
+/* SAXS with a hydration shell and a fitted contrast (csrc/saxs_hydration_kernels.hip).  Added to ABI version 19 without
+ * changing the number: two new entry points, no existing signature, struct or option changes.  The amplitude of atom i is
+ *   F_i(k) = t_i(k) + (1 - G(k, c1)) d_i(k) + c2 f_w(k) s_i
+ * t_i = ff_t[type[i]][k] the in-solvent form factor (the ff of codlad_saxs_debye), d_i = ff_d[type[i]][k] the displaced
+ * solvent, s_i = weight[s][i] the exposed fraction of the atom IN THAT STRUCTURE (device float [n_struct][n_atoms]), f_w
+ * the form factor of a water, G the expansion factor of the excluded volume (G(k, 1) = 1).  codlad_saxs_partials computes
+ * the CODLAD_SAXS_HYD_PARTIALS = 6 partial profiles, in the order tt, td, dd, ts, ds, ss,
+ *   P_ab[s][k] = sum_i a_i b_i + sum_{i<j} (a_i b_j + b_i a_j) sinc(q_k r_ij)
+ * so that I(k; c1, c2) = sum_i sum_j F_i F_j sinc is the combination codlad_saxs_hydration_fit states below.
+ * Per pair i < j and per k ONE sinc, the fp32 sequence of codlad_saxs_debye above, and three fp32 terms t_j * sinc,
+ * d_j * sinc, s_j * sinc.  Accumulation: the decomposition of codlad_saxs_debye (blocks of 64, workgroup (s, p) owns the
+ * row blocks p and B - 1 - p, four waves, wave w the partner tiles block + w, block + w + 4, ...), with Q walked in chunks
+ * of CODLAD_SAXS_HYD_Q_CHUNK:
+ *   fp32:    per k three sums of a lane's terms of ONE tile, each added to 0 in ascending j; a partner j <= i adds 0
+ *   float64: DT, DD, DS = the tiles' fp32 sums, converted, added to 0 in ascending t
+ *            per row block, p first, with the row atom's t_i, d_i, s_i converted (an atom i >= n_atoms counts as 0) and
+ *            self_ab = a_i * b_i in wave 0 and 0 in the others:
+ *              E_tt += 2 * (t_i * DT) + self_tt      E_td += (t_i * DD + d_i * DT) + self_td
+ *              E_dd += 2 * (d_i * DD) + self_dd      E_ts += (t_i * DS + s_i * DT) + self_ts
+ *              E_ss += 2 * (s_i * DS) + self_ss      E_ds += (d_i * DS + s_i * DD) + self_ds
+ *            the lanes (stride 32, 16, .. 1: E[l] += E[l ^ stride]), the waves (((E_0 + E_1) + E_2) + E_3) and the
+ *            workgroups (ascending p, a second launch) as for codlad_saxs_debye
+ * The tt component is codlad_saxs_debye's sequence operation for operation: P[s][0][:] has the bits of its I[s][:] on the
+ * same xyz, type, ff = ff_t and q.
+ * partial: device double [n_struct][P][6][n_q], scratch of the call (written before it is read).  Outputs (device): P
+ * double [n_struct][6][n_q]; finite uint8 [n_struct]: a structure with a coordinate OR a weight that is NaN or +-inf gets
+ * finite = 0 and NaN in all six rows, the others keep their bits; mean_P double [6][n_q] (may be NULL): the finite
+ * structures' rows added to 0 in ascending s, divided by their number, NaN when there is none.  No atomics, sums in one
+ * order: bit-identical from call to call, and a structure's rows do not depend on n_struct or on its place in the call.
+ * A null pointer (mean_P excepted), n_struct / n_atoms / n_types / n_q <= 0, n_q > CODLAD_SAXS_MAX_Q, n_types >
+ * CODLAD_SAXS_MAX_TYPES, n_struct * P >= 2^31 or 3 * n_atoms >= 2^31 returns -1 (codlad_last_error) before any launch. */
+#define CODLAD_SAXS_HYD_PARTIALS 6
+#ifndef CODLAD_SAXS_HYD_Q_CHUNK          /* a build may try another value (CODLAD_CXXFLAGS=-D...) */
+#define CODLAD_SAXS_HYD_Q_CHUNK 8        /* the k values a lane carries at a time: 6 float64 and 3 fp32 sums each, no scratch */
+#endif
+int codlad_saxs_partials(const float *xyz, int n_struct, int n_atoms, const int32_t *type, int n_types, const float *ff_t,
+                         const float *ff_d, const float *weight, const float *q, int n_q, double *partial, double *P,
+                         double *mean_P, uint8_t *finite, void *stream);
+/* codlad_saxs_hydration_fit: profiles of n_batch curve sets P [n_batch][6][n_q] on a grid of n_c1 * n_c2 <=
+ * CODLAD_SAXS_HYD_MAX_GRID parameters, flat index g = a * n_c2 + b.  All arrays device double: f_w [n_q]; G [n_c1][n_q],
+ * the expansion factor the HOST tabulated (the device performs +, * and / only, each correctly rounded); c2 [n_c2].
+ * With u = 1 - G[a][k] and w = c2[b] * f_w[k], in this order:
+ *   I = ((((P_tt + (2 * u) * P_td) + (u * u) * P_dd) + (2 * w) * P_ts) + ((2 * w) * u) * P_ds) + (w * w) * P_ss
+ * I_exp == NULL (then sigma must be NULL too): I_grid [n_batch][n_c1 * n_c2][n_q] receives I and nothing else is touched.
+ * I_exp, sigma [n_q] given (n_q >= 2): I_grid is not touched; per (batch, g), every sum over k ascending from 0,
+ *   scale = sum((I_exp * I) * wk) / sum((I * I) * wk), wk = 1 / (sigma * sigma)
+ *   chi2  = sum(r * r) / (double)(n_q - 1), r = (scale * I - I_exp) / sigma
+ * into scale, chi2 [n_batch][n_c1 * n_c2]; best int32 [n_batch] = the g of the smallest chi2, the lowest g of a tie; a
+ * chi2 that is NaN or +inf never wins, and when none is left best = -1; I_best [n_batch][n_q] = I at best, NaN for -1.
+ * A null pointer among those the mode reads or writes, a count <= 0, n_q > CODLAD_SAXS_MAX_Q, n_c1 * n_c2 over the cap,
+ * or only one of I_exp / sigma returns -1 before any launch. */
+#define CODLAD_SAXS_HYD_MAX_GRID 4096
+int codlad_saxs_hydration_fit(const double *P, int n_batch, int n_q, const double *f_w, const double *G, int n_c1,
+                              const double *c2, int n_c2, const double *I_exp, const double *sigma, double *I_grid,
+                              double *scale, double *chi2, int32_t *best, double *I_best, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,6 +49,8 @@ Addition: `--saxs [N_Q]` (opt-in, wherever --observables is allowed; after --rel
 small-angle X-ray scattering profile of every written structure on the device (metrics.saxs_profile: the Debye sum over
 all atom pairs, united-atom form factors in a displaced solvent) on N_Q points of [0, 0.5] 1/A, or on the q grid of
 `--saxs_data FILE` (q, I, sigma columns), against which the ensemble mean is then scaled and its reduced chi^2 printed.
+`--saxs_hydration [C1 C2]` (only with --saxs) adds the hydration shell and the excluded-volume scale, given or fitted to
+--saxs_data (metrics.saxs_partials, saxs_hydration_fit).
 """
 import argparse
 import os
@@ -241,6 +243,24 @@ def check_saxs(args):
             raise SystemExit("--saxs needs the topology of the structures: --data_process pickles carry none "
                              "(use --pdb_files, --cg_pdb or --synthetic)")
     return n
+
+
+def check_saxs_hydration(args):
+    """Where --saxs_hydration applies: only with --saxs; without its two numbers it fits them, which needs --saxs_data.
+    Returns None (off), () (fit c1 and c2) or (c1, c2)."""
+    v = getattr(args, "saxs_hydration", None)
+    if v is None:
+        return None
+    if not getattr(args, "saxs", 0):
+        raise SystemExit("--saxs_hydration needs --saxs: it is the hydration shell and the contrast of the profile --saxs computes")
+    if len(v) not in (0, 2):
+        raise SystemExit(f"--saxs_hydration takes C1 and C2 or nothing (then both are fitted to --saxs_data), got {len(v)} number(s)")
+    if not v and not getattr(args, "saxs_data", None):
+        raise SystemExit("--saxs_hydration without C1 and C2 fits them: that needs the curve of --saxs_data")
+    if v and not (v[0] > 0 and np.isfinite(v).all()):
+        raise SystemExit(f"--saxs_hydration: C1 scales the excluded volume and must be positive, C2 a number, got {v[0]} {v[1]}")
+    args.saxs_hydration = tuple(float(c) for c in v)
+    return args.saxs_hydration
 
 
 def read_saxs_data(path):
@@ -596,18 +616,40 @@ def observables_report(name, obs):
     return stats
 
 
+def saxs_hydrated(xyz, top, q, hydration, data=None):
+    """--saxs_hydration: metrics.saxs_partials of the written structures, (c1, c2) as given or fitted to `data` on the
+    ensemble-mean partials (metrics.saxs_hydration_fit, the default grid) -> saxs_profile's dict with the hydrated
+    profiles of every structure at those parameters, and `partials`, `hydration` = what saxs_report prints."""
+    hp = metrics.saxs_partials(xyz, top, q=q)
+    info = {}
+    if hydration:
+        c1, c2 = hydration
+    else:
+        fit = metrics.saxs_hydration_fit(hp["mean"], hp["q"], hp["water"], data[1], data[2])
+        if int(fit["index"]) < 0:
+            raise SystemExit("--saxs_hydration: no point of the (c1, c2) grid has a finite chi^2 (is any structure finite?)")
+        c1, c2 = float(fit["c1"]), float(fit["c2"])
+        plain = metrics.saxs_fit(hp["mean"][0], data[0], data[1], data[2])
+        info = {"saxs_scale": float(fit["scale"]), "saxs_chi2": float(fit["chi2"]), "saxs_chi2_unhydrated": float(plain["chi2"])}
+    info = {"saxs_c1": c1, "saxs_c2": c2, **info}
+    combine = lambda P: metrics.saxs_combine(P, hp["q"], hp["water"], c1, c2)                    # noqa: E731
+    return dict(q=hp["q"], I=combine(hp["P"]), mean=combine(hp["mean"]), finite=hp["finite"], n_finite=hp["n_finite"],
+                partials=hp["P"], hydration=info)
+
+
 def saxs_report(name, sx, data=None):
-    """The printed summary of --saxs for one output file (sx: metrics.saxs_profile's dict; data: read_saxs_data's curve on
-    the same q grid, or None) -> the stats."""
+    """The printed summary of --saxs for one output file (sx: metrics.saxs_profile's dict, or saxs_hydrated's; data:
+    read_saxs_data's curve on the same q grid, or None) -> the stats."""
     q, mean = sx["q"].cpu().numpy(), sx["mean"].cpu().numpy()
     fin = sx["finite"]
     stats = {"data_name": name, "structures": int(fin.shape[0]), "saxs_non_finite": int((~fin).sum()), "saxs_I0": float(mean[0])}
     picks = sorted({len(q) // 4, len(q) // 2, len(q) - 1})
     for k in picks:
         stats[f"saxs_mean_q{float(q[k]):.4f}"] = float(mean[k])
-    if data is not None:
+    if data is not None and "saxs_scale" not in sx.get("hydration", {}):
         fit = metrics.saxs_fit(sx["mean"], data[0], data[1], data[2])
         stats["saxs_scale"], stats["saxs_chi2"] = float(fit["scale"]), float(fit["chi2"])
+    stats.update(sx.get("hydration", {}))
     print("############## vvvvvvvvv SAXS profile (Debye sum, ensemble mean; q in 1/A):")
     print(f"I({float(q[0]):.4f}) {stats['saxs_I0']:.6g}   " + "   ".join(f"I({float(q[k]):.4f}) {float(mean[k]):.6g}" for k in picks))
     for k, v in stats.items():
@@ -699,6 +741,7 @@ def main(args):
     check_relax(args)
     check_observables(args)
     check_saxs(args)
+    check_saxs_hydration(args)
     check_dssp(args)
     check_sampler(args)
     saxs_data = read_saxs_data(args.saxs_data) if getattr(args, "saxs_data", None) else None
@@ -895,8 +938,11 @@ def main(args):
         if getattr(args, "saxs", 0):
             if name not in _GEOMETRY_TOP:
                 raise SystemExit(f"--saxs: the topology of {name} is not known on this input route")
-            sx = metrics.saxs_profile(xyz.reshape(-1, xyz.shape[2], 3), _GEOMETRY_TOP[name],                # the written coordinates
-                                      q=saxs_data[0] if saxs_data is not None else np.linspace(0.0, 0.5, args.saxs))
+            saxs_q = saxs_data[0] if saxs_data is not None else np.linspace(0.0, 0.5, args.saxs)
+            if getattr(args, "saxs_hydration", None) is not None:
+                sx = saxs_hydrated(xyz.reshape(-1, xyz.shape[2], 3), _GEOMETRY_TOP[name], saxs_q, args.saxs_hydration, saxs_data)
+            else:
+                sx = metrics.saxs_profile(xyz.reshape(-1, xyz.shape[2], 3), _GEOMETRY_TOP[name], q=saxs_q)    # the written coordinates
         sec = None
         if getattr(args, "dssp", False):
             if name not in _GEOMETRY_TOP:
@@ -937,6 +983,8 @@ def main(args):
         if sx is not None:
             np.save(os.path.join(save_dir, f"{name}_saxs.npy"), sx["I"].cpu().numpy())                    # float64 [E * B, N_Q]
             np.save(os.path.join(save_dir, f"{name}_saxs_q.npy"), sx["q"].cpu().numpy())                  # float32 [N_Q]
+            if "partials" in sx:
+                np.save(os.path.join(save_dir, f"{name}_saxs_partials.npy"), sx["partials"].cpu().numpy())  # float64 [E * B, 6, N_Q]
             saxs_report(name, sx, saxs_data)
         if sec is not None:
             np.save(os.path.join(save_dir, f"{name}_dssp.npy"), sec["ss"].cpu().numpy())                  # uint8 [E * B, R]
@@ -1066,6 +1114,13 @@ if __name__ == "__main__":
                    help="an experimental curve for --saxs: three whitespace-separated columns q (1/A), I, sigma, `#` starts a "
                         "comment.  Its q values replace the grid of --saxs (there is no interpolation); the scale and the "
                         "reduced chi^2 of the ensemble mean against it are printed")
+    p.add_argument("--saxs_hydration", nargs="*", type=float, default=None, metavar="C",
+                   help="with --saxs: add the hydration shell and the excluded-volume scale to the profile (metrics.saxs_partials, "
+                        "saxs_combine): C1 C2 = the scale of the atomic volumes (1 = as --saxs alone) and the weight of the bound "
+                        "water on the solvent-exposed atoms (0 = none).  Without the two numbers both are fitted to --saxs_data on "
+                        "FoXS's grid (c1 0.95 .. 1.05, c2 -2 .. 4) for the ensemble mean; c1, c2, the scale and chi^2 are printed "
+                        "beside the chi^2 of the unhydrated mean.  <name>_saxs.npy then holds the hydrated profiles; also saves "
+                        "<name>_saxs_partials.npy float64 [structures, 6, N_Q] (tt, td, dd, ts, ds, ss)")
     p.add_argument("--dssp", action="store_true",
                    help="also assign the secondary structure of every written structure on the device (allowed wherever "
                         "--geometry_check is; after --relax when both are given): Kabsch-Sander hydrogen bonds and the DSSP "
