@@ -129,6 +129,7 @@ DSSP_KIND_PRO, DSSP_KIND_CHAIN_START, DSSP_GEOM_LINK, DSSP_GEOM_BEND, DSSP_UNDEF
 SAXS_MAX_Q, SAXS_MAX_TYPES, SAXS_Q_CHUNK = 512, 32, 16    # CODLAD_SAXS_MAX_Q, _MAX_TYPES, _Q_CHUNK
 SAXS_X_MAX, SAXS_X_SMALL, SAXS_SIN_ULPS = 25600.0, 0.125, 5   # CODLAD_SAXS_X_MAX, _X_SMALL, _SIN_ULPS
 SAXS_HYD_PARTIALS, SAXS_HYD_Q_CHUNK, SAXS_HYD_MAX_GRID = 6, 8, 4096   # CODLAD_SAXS_HYD_PARTIALS, _Q_CHUNK, _MAX_GRID
+PAIR_HIST_MAX_BINS, PAIR_HIST_MAX_ATOMS, PAIR_HIST_ITEM_WORDS, PAIR_HIST_ROWS = 4096, 65535, 5, 64   # CODLAD_PAIR_HIST_*
 ODE_NORM_WORDS = 257                                   # CODLAD_ODE_NORM_WORDS
 
 _JOB = [C.POINTER(DenoiserWeights), C.POINTER(JobDesc)]    # what every entry point that runs the denoiser starts with
@@ -159,6 +160,8 @@ _SIGS = {
     "codlad_saxs_debye": (C.c_int, [P, C.c_int, C.c_int, P, C.c_int, P, P, C.c_int, P, P, P, P, P]),
     "codlad_saxs_partials": (C.c_int, [P, C.c_int, C.c_int, P, C.c_int, P, P, P, P, C.c_int, P, P, P, P, P]),
     "codlad_saxs_hydration_fit": (C.c_int, [P, C.c_int, C.c_int, P, P, C.c_int, P, C.c_int, P, P, P, P, P, P, P, P]),
+    "codlad_pair_hist": (C.c_int, [P, C.c_int, C.c_int, P, P, C.c_int, C.c_float, C.c_int, P, C.c_int, P, P, P, P, P]),
+    "codlad_pair_hist_profile": (C.c_int, [P, P, P, P, C.c_int, C.c_int, C.c_int, P, P, P, C.c_int] + [P] * 11),
     "codlad_last_error": (C.c_char_p, []),
     "codlad_struct_sizes": (None, [C.POINTER(C.c_int)]),
     "codlad_pack_block_host": (None, [P, C.c_int, C.c_float, P]),

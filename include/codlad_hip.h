@@ -1212,6 +1212,69 @@ int codlad_saxs_hydration_fit(const double *P, int n_batch, int n_q, const doubl
                               const double *c2, int n_c2, const double *I_exp, const double *sigma, double *I_grid,
                               double *scale, double *chi2, int32_t *best, double *I_best, void *stream);
 
+/* Typed pair-distance histograms (csrc/pair_hist_kernels.hip).  Added to ABI version 19 without changing the number: two
+ * new entry points, no existing signature, struct or option changes.  For every structure of xyz [n_struct][n_atoms][3]
+ * (ONE topology) and every class c of atom types a <= b, the number of atom pairs per distance bin: q-independent, integer,
+ * and what P(r) and I(q) on any q grid are short float64 combinations of (codlad_pair_hist_profile).
+ * The class of (a <= b) among n_types = T types, C = T (T + 1) / 2 of them, rows a ascending and b ascending within a:
+ *   c = a * T - a * (a - 1) / 2 + (b - a)                        CODLAD_PAIR_HIST_CLASS
+ * The histogram does not depend on the order of the atoms, so the caller sorts them by type: order, device int32
+ * [n_atoms], holds the atom indices by type ascending, ties ascending, and type_start, device int32 [T + 1], the first
+ * sorted position of every type (type_start[T] = n_atoms).  `items`, device int32 [n_items][CODLAD_PAIR_HIST_ITEM_WORDS],
+ * is the caller's cut of the work, one workgroup per (structure, item): (a, b, row0, col0, col1) - the sorted positions
+ * row0 .. row0 + 63 of type a (those below type_start[a + 1]) against the sorted positions col0 .. col1 - 1 of type b;
+ * when a = b only the pairs with column position > row position count.  The items must cover every pair once; every
+ * word, every type_start and every order entry is clamped into its range before it is used, so a wrong table gives wrong
+ * counts and never an access out of bounds.
+ * The decision, per pair, fp32 with one rounding per operation in the written order (no contraction; sqrtf is the correctly
+ * rounded one), i the row atom and j the column atom:
+ *   d = x_j - x_i per component, r = sqrtf((dx*dx + dy*dy) + dz*dz), t = r * inv_dr
+ *   t < (float)n_bins: bin = (int)t (truncation; coincident atoms fall in bin 0); otherwise the pair is counted in `over`
+ * Accumulation: integer adds only - a workgroup's histogram of its one class in LDS (atomic adds on int), its non-zero
+ * bins added to H by integer atomics after a fill launch of the same call; d_bin by integer atomic max.  Integer addition
+ * commutes: the bits repeat from call to call and a structure's rows do not depend on n_struct or its place in the call.
+ * Outputs (device; the call writes every element): H int32 [n_struct][C][n_bins]; over int32 [n_struct][C], the pairs
+ * with t >= n_bins; d_bin int32 [n_struct], the highest occupied bin over all classes, -1 if there is none; finite uint8
+ * [n_struct]: a structure with a coordinate that is NaN or +-inf gets finite = 0 and -1 in every element of its H, over
+ * and d_bin, the others keep their bits.
+ * A null pointer, n_struct / n_atoms / n_items <= 0, n_bins outside 1 .. CODLAD_PAIR_HIST_MAX_BINS (16 KB of LDS), n_atoms >
+ * CODLAD_PAIR_HIST_MAX_ATOMS (a count fits an int32), n_types outside 1 .. CODLAD_SAXS_MAX_TYPES, inv_dr not a positive
+ * finite number, or n_struct * n_items >= 2^31 returns -1 (codlad_last_error) before any launch. */
+#define CODLAD_PAIR_HIST_MAX_BINS 4096
+#define CODLAD_PAIR_HIST_MAX_ATOMS 65535
+#define CODLAD_PAIR_HIST_ITEM_WORDS 5
+#define CODLAD_PAIR_HIST_ROWS 64          /* the rows of an item: one per lane */
+#define CODLAD_PAIR_HIST_CLASS(a, b, T) ((a) * (T) - (a) * ((a) - 1) / 2 + ((b) - (a)))
+int codlad_pair_hist(const float *xyz, int n_struct, int n_atoms, const int32_t *order, const int32_t *type_start,
+                     int n_types, float inv_dr, int n_bins, const int32_t *items, int n_items, int32_t *H, int32_t *over,
+                     int32_t *d_bin, uint8_t *finite, void *stream);
+/* codlad_pair_hist_profile: what codlad_pair_hist's counts give, in float64 with + and * only, every sum added to 0 in ONE
+ * order - classes ascending (a ascending, b ascending within a), bins ascending from 0 to the structure's d_bin - so
+ * that a restatement in the same order has the same bits.  count: device int32 [n_types], the atoms of every type.
+ * The profile (I != NULL; then ff, device double [n_types][n_q], sinc_table, device double [n_bins][n_q] = sinc(q_k (bin +
+ * 1/2) dr) tabulated by the HOST, and partial, device double [n_struct][C][n_q], scratch of the call, must be given):
+ *   partial[s][c][k] = sum_bin (double)H[s][c][bin] * sinc_table[bin][k]
+ *   self[k]  = sum_a (double)count[a] * (ff[a][k] * ff[a][k])
+ *   cross[k] = sum_c (ff[a][k] * ff[b][k]) * partial[s][c][k]
+ *   I[s][k]  = self[k] + 2 * cross[k]
+ * The pair distribution (P != NULL; then w, device double [n_types], r2, device double [n_bins] = ((bin + 1/2) dr)^2
+ * tabulated by the host, I0 and m2, device double [n_struct], must be given):
+ *   P[s][bin] = sum_c (w[a] * w[b]) * (double)H[s][c][bin]        for bin <= d_bin, 0 beyond
+ *   I0[s]     = sum_a (double)count[a] * (w[a] * w[a]) + 2 * sum_bin P[s][bin]
+ *   m2[s]     = sum_bin r2[bin] * P[s][bin]                       (Rg^2 = m2 / I0)
+ * complete uint8 [n_struct] is always written: 1 for a finite structure whose `over` is 0 in every class.  A structure
+ * that is finite and not complete lacks pairs: its row of I is NaN (never a silently truncated profile), its P, I0 and m2
+ * are written, as statements about r < n_bins dr.  A structure that is not finite gets NaN everywhere.  mean_I [n_q] and
+ * mean_P [n_bins] (each may be NULL): the rows of the finite and complete structures added to 0 in ascending s, divided
+ * by their number, NaN when there is none.
+ * A null pointer among those the mode reads or writes, neither I nor P, mean_I without I or mean_P without P, a count <=
+ * 0, n_bins > CODLAD_PAIR_HIST_MAX_BINS, n_types > CODLAD_SAXS_MAX_TYPES, n_q > CODLAD_SAXS_MAX_Q or n_struct * C >= 2^31
+ * returns -1 before any launch. */
+int codlad_pair_hist_profile(const int32_t *H, const int32_t *over, const int32_t *d_bin, const uint8_t *finite, int n_struct,
+                             int n_types, int n_bins, const int32_t *count, const double *ff, const double *sinc_table,
+                             int n_q, double *partial, double *I, double *mean_I, const double *w, const double *r2,
+                             double *P, double *I0, double *m2, double *mean_P, uint8_t *complete, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

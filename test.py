@@ -51,6 +51,10 @@ all atom pairs, united-atom form factors in a displaced solvent) on N_Q points o
 `--saxs_data FILE` (q, I, sigma columns), against which the ensemble mean is then scaled and its reduced chi^2 printed.
 `--saxs_hydration [C1 C2]` (only with --saxs) adds the hydration shell and the excluded-volume scale, given or fitted to
 --saxs_data (metrics.saxs_partials, saxs_hydration_fit).
+Addition: `--pr [DR]` (opt-in, wherever --observables is allowed; after --relax when both are given) computes the pair
+distribution P(r) of every written structure on the device (metrics.pair_distribution: the typed pair-distance histogram
+in bins of DR A, default 0.5, weighted with the forward amplitudes) and prints D_max, the real-space Rg and the number of
+structures with pairs beyond the contour-length bound.
 """
 import argparse
 import os
@@ -243,6 +247,23 @@ def check_saxs(args):
             raise SystemExit("--saxs needs the topology of the structures: --data_process pickles carry none "
                              "(use --pdb_files, --cg_pdb or --synthetic)")
     return n
+
+
+def check_pr(args):
+    """Where --pr applies: exactly where --observables does.  Returns the bin width in A, 0 = off."""
+    dr = getattr(args, "pr", None)
+    if dr is None:
+        args.pr = 0.0
+        return 0.0
+    if not (np.isfinite(dr) and dr > 0):
+        raise SystemExit(f"--pr takes a bin width in A, a positive number, got {dr}")
+    if not getattr(args, "cg_pdb", None):
+        if args.experiment in ("bpd", "fmloss"):
+            raise SystemExit(f"--pr describes generated structures: --experiment {args.experiment} generates none")
+        if args.data_process and not args.synthetic:
+            raise SystemExit("--pr needs the topology of the structures: --data_process pickles carry none "
+                             "(use --pdb_files, --cg_pdb or --synthetic)")
+    return dr
 
 
 def check_saxs_hydration(args):
@@ -442,7 +463,8 @@ def iter_batches(args):
             names = [synth.IDX2THR[int(z)] for z in prot["z_full"]]
             geom_top = None
             if getattr(args, "geometry_check", False) or getattr(args, "stereo_check", False) or getattr(args, "relax", 0) \
-                    or getattr(args, "observables", 0) or getattr(args, "dssp", False) or getattr(args, "saxs", 0):
+                    or getattr(args, "observables", 0) or getattr(args, "dssp", False) or getattr(args, "saxs", 0) \
+                    or getattr(args, "pr", 0):
                 from codlad_amd.utils.cg_input import template_topology
                 geom_top = template_topology(names[1:-1])             # one Topology (and one set of device tables) per protein
             for c, (a, b) in enumerate(plan):
@@ -658,6 +680,23 @@ def saxs_report(name, sx, data=None):
     return stats
 
 
+def pr_report(name, pr):
+    """The printed summary of --pr for one output file (pr: metrics.pair_distribution's dict) -> the stats."""
+    fin = pr["finite"]
+    d_max, rg = pr["d_max"][fin].cpu().numpy(), pr["rg"][fin].cpu().numpy()
+    msd = lambda v: (float(v.mean()), float(v.std())) if v.size else (float("nan"), float("nan"))    # noqa: E731
+    stats = {"data_name": name, "structures": int(fin.shape[0]), "pr_non_finite": int((~fin).sum()),
+             "pr_overflow": int(pr["overflow"].sum()), "pr_bins": int(pr["r"].shape[0]),
+             "pr_d_max_mean": msd(d_max)[0], "pr_d_max_sd": msd(d_max)[1], "pr_rg_mean": msd(rg)[0], "pr_rg_sd": msd(rg)[1]}
+    print("############## vvvvvvvvv pair distribution P(r) (typed pair-distance histogram; A):")
+    print(f"D_max {stats['pr_d_max_mean']:.2f} +- {stats['pr_d_max_sd']:.2f}   Rg {stats['pr_rg_mean']:.3f} +- "
+          f"{stats['pr_rg_sd']:.3f}   structures with overflow {stats['pr_overflow']}")
+    for k, v in stats.items():
+        print(k, v)
+    print("############## ^^^^^^^^^ pair distribution P(r)")
+    return stats
+
+
 def dssp_report(name, sec, propensity):
     """The printed summary of --dssp for one output file (sec: metrics.dssp's dict, propensity: metrics.ss_propensity of its
     labels) -> the stats: the mean share of helix (H + G + I), strand (E + B) and coil (the rest) over residues and finite
@@ -742,6 +781,7 @@ def main(args):
     check_observables(args)
     check_saxs(args)
     check_saxs_hydration(args)
+    check_pr(args)
     check_dssp(args)
     check_sampler(args)
     saxs_data = read_saxs_data(args.saxs_data) if getattr(args, "saxs_data", None) else None
@@ -943,6 +983,14 @@ def main(args):
                 sx = saxs_hydrated(xyz.reshape(-1, xyz.shape[2], 3), _GEOMETRY_TOP[name], saxs_q, args.saxs_hydration, saxs_data)
             else:
                 sx = metrics.saxs_profile(xyz.reshape(-1, xyz.shape[2], 3), _GEOMETRY_TOP[name], q=saxs_q)    # the written coordinates
+        pr = None
+        if getattr(args, "pr", 0):
+            if name not in _GEOMETRY_TOP:
+                raise SystemExit(f"--pr: the topology of {name} is not known on this input route")
+            try:
+                pr = metrics.pair_distribution(xyz.reshape(-1, xyz.shape[2], 3), _GEOMETRY_TOP[name], dr=args.pr)   # the written coordinates
+            except ValueError as e:                               # more bins than the kernel holds: a wider bin is the way out
+                raise SystemExit(f"--pr {args.pr}: {e}") from None
         sec = None
         if getattr(args, "dssp", False):
             if name not in _GEOMETRY_TOP:
@@ -986,6 +1034,10 @@ def main(args):
             if "partials" in sx:
                 np.save(os.path.join(save_dir, f"{name}_saxs_partials.npy"), sx["partials"].cpu().numpy())  # float64 [E * B, 6, N_Q]
             saxs_report(name, sx, saxs_data)
+        if pr is not None:
+            np.save(os.path.join(save_dir, f"{name}_pr.npy"), pr["P"].cpu().numpy())                      # float64 [E * B, BINS]
+            np.save(os.path.join(save_dir, f"{name}_pr_r.npy"), pr["r"].cpu().numpy())                    # float64 [BINS]
+            pr_report(name, pr)
         if sec is not None:
             np.save(os.path.join(save_dir, f"{name}_dssp.npy"), sec["ss"].cpu().numpy())                  # uint8 [E * B, R]
             np.save(os.path.join(save_dir, f"{name}_dssp_propensity.npy"), sec_prop.cpu().numpy())       # float64 [R, 8]
@@ -1121,6 +1173,12 @@ if __name__ == "__main__":
                         "FoXS's grid (c1 0.95 .. 1.05, c2 -2 .. 4) for the ensemble mean; c1, c2, the scale and chi^2 are printed "
                         "beside the chi^2 of the unhydrated mean.  <name>_saxs.npy then holds the hydrated profiles; also saves "
                         "<name>_saxs_partials.npy float64 [structures, 6, N_Q] (tt, td, dd, ts, ds, ss)")
+    p.add_argument("--pr", nargs="?", type=float, const=0.5, default=None, metavar="DR",
+                   help="compute the pair distribution P(r) of every written structure on the device (allowed wherever "
+                        "--observables is; after --relax when both are given): the typed pair-distance histogram in bins of DR A "
+                        "(default 0.5) up to the contour-length bound of the topology, weighted with the forward amplitudes "
+                        "(metrics.pair_distribution).  Prints D_max, the real-space Rg and the number of structures with pairs "
+                        "beyond the bound; saves <name>_pr.npy float64 [structures, BINS] and <name>_pr_r.npy (the bin centres)")
     p.add_argument("--dssp", action="store_true",
                    help="also assign the secondary structure of every written structure on the device (allowed wherever "
                         "--geometry_check is; after --relax when both are given): Kabsch-Sander hydrogen bonds and the DSSP "
