@@ -130,6 +130,8 @@ SAXS_MAX_Q, SAXS_MAX_TYPES, SAXS_Q_CHUNK = 512, 32, 16    # CODLAD_SAXS_MAX_Q, _
 SAXS_X_MAX, SAXS_X_SMALL, SAXS_SIN_ULPS = 25600.0, 0.125, 5   # CODLAD_SAXS_X_MAX, _X_SMALL, _SIN_ULPS
 SAXS_HYD_PARTIALS, SAXS_HYD_Q_CHUNK, SAXS_HYD_MAX_GRID = 6, 8, 4096   # CODLAD_SAXS_HYD_PARTIALS, _Q_CHUNK, _MAX_GRID
 PAIR_HIST_MAX_BINS, PAIR_HIST_MAX_ATOMS, PAIR_HIST_ITEM_WORDS, PAIR_HIST_ROWS = 4096, 65535, 5, 64   # CODLAD_PAIR_HIST_*
+REWEIGHT_LADDER, REWEIGHT_SCALARS, REWEIGHT_MAX_PROBLEMS, REWEIGHT_MAX_ITER = 16, 4, 4096, 1000   # CODLAD_REWEIGHT_*
+REWEIGHT_STATUS = ("converged", "cap", "stalled", "failed", "none")   # CODLAD_REWEIGHT_CONVERGED .. _NONE = 0 .. 4
 ODE_NORM_WORDS = 257                                   # CODLAD_ODE_NORM_WORDS
 
 _JOB = [C.POINTER(DenoiserWeights), C.POINTER(JobDesc)]    # what every entry point that runs the denoiser starts with
@@ -162,6 +164,10 @@ _SIGS = {
     "codlad_saxs_hydration_fit": (C.c_int, [P, C.c_int, C.c_int, P, P, C.c_int, P, C.c_int, P, P, P, P, P, P, P, P]),
     "codlad_pair_hist": (C.c_int, [P, C.c_int, C.c_int, P, P, C.c_int, C.c_float, C.c_int, P, C.c_int, P, P, P, P, P]),
     "codlad_pair_hist_profile": (C.c_int, [P, P, P, P, C.c_int, C.c_int, C.c_int, P, P, P, C.c_int] + [P] * 11),
+    "codlad_reweight_scratch_bytes": (C.c_longlong, [C.c_int] * 3),
+    "codlad_reweight_solve": (C.c_int, [P, P, P, P, C.c_int, C.c_int, P, P, C.c_int, P, C.c_double, C.c_int, P, C.c_longlong] +
+                              [P] * 8),
+    "codlad_weighted_mean": (C.c_int, [P, P, C.c_int, C.c_int, C.c_int, P, P]),
     "codlad_last_error": (C.c_char_p, []),
     "codlad_struct_sizes": (None, [C.POINTER(C.c_int)]),
     "codlad_pack_block_host": (None, [P, C.c_int, C.c_float, P]),

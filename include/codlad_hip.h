@@ -1275,6 +1275,64 @@ int codlad_pair_hist_profile(const int32_t *H, const int32_t *over, const int32_
                              int n_q, double *partial, double *I, double *mean_I, const double *w, const double *r2,
                              double *P, double *I0, double *m2, double *mean_P, uint8_t *complete, void *stream);
 
+/* Maximum-entropy reweighting of an ensemble against data (csrc/reweight_kernels.hip; BME, Bottaro, Bengtsen and
+ * Lindorff-Larsen).  Added to ABI version 19 without changing the number: two new entry points, no existing signature,
+ * struct or option changes.  Y, device double [n_struct][n_obs], holds n_obs observables of every structure; y, sigma,
+ * device double [n_obs], the experiment and its error (the CALLER checks that both are finite and sigma > 0); w0, device
+ * double [n_struct] or NULL (uniform), the prior weights, normalised here.  theta and scale are HOST double [n_problems]:
+ * problem p is solved at the regularisation theta[p] with the calculated observables multiplied by c = scale[p], and is
+ * independent of the others.  With U = Y / sigma, v = y / sigma and z_jk = c * U_jk - v_k the call minimises
+ *   Gamma(mu) = log sum_j w0_j exp(-mu . z_j) + (theta / 2) |mu|^2
+ * whose weights are w_j = w0_j exp(-mu . z_j) / Z, gradient g = theta mu - <z>_w and Hessian H = c^2 Cov_w(U) + theta I,
+ * by a damped Newton iteration from mu0 (device double [n_problems][n_obs], NULL = 0), per iteration:
+ *   1. a_j = log w0_j - mu . z_j, log Z by the maximum and the sum of exp(a_j - max), w, <U>_w, g;
+ *      gscale = max_k sum_j w_j |z_jk| + theta |mu|_inf; |g|_inf <= gtol * gscale ends the problem as CONVERGED; otherwise
+ *      n_iter >= max_iter ends it as CAP
+ *   2. Cov_w(U) = sum_j w_j (U_jk - <U>_k)(U_jl - <U>_l), lower triangle; H; its Cholesky factor - a pivot that is <= 0 or
+ *      not finite ends the problem as FAILED; p = -H^-1 g
+ *   3. s_j = p . z_j; for t = 2^0 .. 2^-(CODLAD_REWEIGHT_LADDER - 1), from the logits a_j - t s_j alone:
+ *      Gamma(mu + t p) <= Gamma(mu) + 1e-4 t (g . p) + 8 * 2^-52 * (1 + |Gamma(mu)|); the largest passing t gives
+ *      mu += t p and n_iter += 1, none ends the problem as STALLED
+ * The host enqueues max_iter rounds of this fixed sequence and one more of step 1 and never waits: status[p] is -1 while
+ * problem p runs, and every launch returns at once for a problem whose status is set.  No kernel waits for another.
+ * Sums over the structures: blocks of 256 consecutive rows whatever n_struct and n_problems; a block's rows by the xor
+ * butterfly of each wave (strides 32 .. 1) and ((w0 + w1) + w2) + w3 over its waves, the blocks added to 0 in ascending
+ * order.  The covariance: 64 x 64 tiles, the rows cut into at most 32 chunks whose size depends on n_struct alone, a
+ * chunk's rows in ascending order by fused multiply-adds, the chunks added to 0 in ascending order.  No atomics: the
+ * bits repeat from call to call and a problem's results do not depend on the other problems of the call.
+ * A row of Y that holds a NaN or an infinity, or whose w0 is not a positive finite number, is excluded: used = 0, weight
+ * exactly 0, and it adds exact zeros to every sum, so the other rows' results do not depend on what it holds.
+ * Outputs (device; the call writes every element): mu double [n_problems][n_obs]; w double [n_problems][n_struct]; mean
+ * double [n_problems][n_obs] = sigma_k * <U_k>_w, the reweighted average of Y; scalars double [n_problems]
+ * [CODLAD_REWEIGHT_SCALARS]: chi2_prior = sum_k (c <U_k>_w0 - v_k)^2 / (n_obs - 1), chi2 the same under w (both 0 for
+ * n_obs = 1), s_rel = sum_{w_j > 0} w_j (log w_j - log w0_j) and phi_eff = exp(-s_rel); n_iter, status int32
+ * [n_problems]; used uint8 [n_struct].  When no row is usable every problem gets status NONE, n_iter 0 and NaN elsewhere.
+ * scratch: device, codlad_reweight_scratch_bytes(n_struct, n_obs, n_problems) bytes (8-byte aligned; written before it
+ * is read): U, the logits, the blocks' partials, and per problem the chunks' covariance tiles and the n_obs^2 matrix.
+ * A null pointer (w0 and mu0 excepted), a count <= 0, n_obs > CODLAD_SAXS_MAX_Q, n_problems > CODLAD_REWEIGHT_MAX_PROBLEMS,
+ * max_iter > CODLAD_REWEIGHT_MAX_ITER, a theta, scale or gtol that is not a positive finite number, or a scratch that is
+ * too small returns -1 (codlad_last_error) before any launch; codlad_reweight_scratch_bytes returns -1 likewise. */
+#define CODLAD_REWEIGHT_LADDER 16
+#define CODLAD_REWEIGHT_SCALARS 4
+#define CODLAD_REWEIGHT_MAX_PROBLEMS 4096
+#define CODLAD_REWEIGHT_MAX_ITER 1000
+#define CODLAD_REWEIGHT_CONVERGED 0
+#define CODLAD_REWEIGHT_CAP 1
+#define CODLAD_REWEIGHT_STALLED 2
+#define CODLAD_REWEIGHT_FAILED 3
+#define CODLAD_REWEIGHT_NONE 4
+long long codlad_reweight_scratch_bytes(int n_struct, int n_obs, int n_problems);
+int codlad_reweight_solve(const double *Y, const double *y, const double *sigma, const double *w0, int n_struct, int n_obs,
+                          const double *theta, const double *scale, int n_problems, const double *mu0, double gtol,
+                          int max_iter, void *scratch, long long scratch_bytes, double *mu, double *w, double *mean,
+                          double *scalars, int32_t *n_iter, int32_t *status, uint8_t *used, void *stream);
+/* The reweighted average of any per-structure quantity: values device double [n_struct][n_values], w device double
+ * [n_sets][n_struct] (the w of codlad_reweight_solve) -> out device double [n_sets][n_values], out[t][d] = the products
+ * w[t][s] * values[s][d] added to 0 in ascending s; a structure whose weight is 0 is skipped, whatever its values hold.  A
+ * null pointer, a count <= 0 or n_sets > 65535 returns -1 before any launch. */
+int codlad_weighted_mean(const double *values, const double *w, int n_struct, int n_values, int n_sets, double *out,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,8 @@ all atom pairs, united-atom form factors in a displaced solvent) on N_Q points o
 `--saxs_data FILE` (q, I, sigma columns), against which the ensemble mean is then scaled and its reduced chi^2 printed.
 `--saxs_hydration [C1 C2]` (only with --saxs) adds the hydration shell and the excluded-volume scale, given or fitted to
 --saxs_data (metrics.saxs_partials, saxs_hydration_fit).
+`--saxs_reweight THETA [THETA ...]` (with --saxs and --saxs_data) reweights the written structures against the curve by
+maximum entropy at every THETA (metrics.saxs_reweight, the scale fitted along) and prints the L-curve.
 Addition: `--pr [DR]` (opt-in, wherever --observables is allowed; after --relax when both are given) computes the pair
 distribution P(r) of every written structure on the device (metrics.pair_distribution: the typed pair-distance histogram
 in bins of DR A, default 0.5, weighted with the forward amplitudes) and prints D_max, the real-space Rg and the number of
@@ -282,6 +284,45 @@ def check_saxs_hydration(args):
         raise SystemExit(f"--saxs_hydration: C1 scales the excluded volume and must be positive, C2 a number, got {v[0]} {v[1]}")
     args.saxs_hydration = tuple(float(c) for c in v)
     return args.saxs_hydration
+
+
+def check_saxs_reweight(args):
+    """Where --saxs_reweight applies: with --saxs and --saxs_data; every THETA a positive finite number.  Returns the
+    thetas as a tuple, () = off."""
+    v = getattr(args, "saxs_reweight", None)
+    if v is None:
+        args.saxs_reweight = ()
+        return ()
+    if not getattr(args, "saxs", 0):
+        raise SystemExit("--saxs_reweight needs --saxs: it reweights the structures against the profiles --saxs computes")
+    if not getattr(args, "saxs_data", None):
+        raise SystemExit("--saxs_reweight needs --saxs_data: the curve the weighted mean is to agree with")
+    if not v:
+        raise SystemExit("--saxs_reweight takes one THETA or more (the confidence in the prior; try 1000 100 10 1)")
+    for t in v:
+        if not (t > 0 and t == t and t != float("inf")):
+            raise SystemExit(f"--saxs_reweight: every THETA must be a positive finite number, got {t}")
+    args.saxs_reweight = tuple(float(t) for t in v)
+    return args.saxs_reweight
+
+
+def saxs_reweight_report(name, sx, data, thetas):
+    """--saxs_reweight for one output file: metrics.saxs_reweight of the profiles sx["I"] (hydrated under --saxs_hydration)
+    against `data` at every theta; prints the L-curve (chi^2 before and after, phi_eff, scale, status per theta) ->
+    (weights float64 numpy [n_theta, S], reweighted mean profiles [n_theta, N_Q], the stats)."""
+    rw = metrics.saxs_reweight(sx["I"], data[0], data[1], data[2], list(thetas), finite=sx["finite"])
+    col = {k: rw[k].cpu().numpy() for k in ("chi2_prior", "chi2", "phi_eff", "scale", "status", "n_iter", "rounds", "scale_converged")}
+    stats = {"data_name": name}
+    print("############## vvvvvvvvv SAXS reweighting (maximum entropy; chi^2 at the fitted scale, before -> after):")
+    for t, theta in enumerate(thetas):
+        status = metrics.REWEIGHT_STATUS[int(col["status"][t])] + ("" if col["scale_converged"][t] else ", scale not converged")
+        print(f"theta {theta:g}   chi2 {col['chi2_prior'][t]:.6g} -> {col['chi2'][t]:.6g}   phi_eff {col['phi_eff'][t]:.4f}   "
+              f"scale {col['scale'][t]:.6g}   {status} ({int(col['n_iter'][t])} Newton steps, {int(col['rounds'][t])} rounds)")
+        for k in ("chi2_prior", "chi2", "phi_eff", "scale"):
+            stats[f"saxs_reweight_{k}_theta{theta:g}"] = float(col[k][t])
+        stats[f"saxs_reweight_status_theta{theta:g}"] = int(col["status"][t])
+    print("############## ^^^^^^^^^ SAXS reweighting")
+    return rw["w"].cpu().numpy(), rw["mean"].cpu().numpy(), stats
 
 
 def read_saxs_data(path):
@@ -781,6 +822,7 @@ def main(args):
     check_observables(args)
     check_saxs(args)
     check_saxs_hydration(args)
+    check_saxs_reweight(args)
     check_pr(args)
     check_dssp(args)
     check_sampler(args)
@@ -1034,6 +1076,10 @@ def main(args):
             if "partials" in sx:
                 np.save(os.path.join(save_dir, f"{name}_saxs_partials.npy"), sx["partials"].cpu().numpy())  # float64 [E * B, 6, N_Q]
             saxs_report(name, sx, saxs_data)
+            if getattr(args, "saxs_reweight", ()):
+                weights, rw_mean, _stats = saxs_reweight_report(name, sx, saxs_data, args.saxs_reweight)
+                np.save(os.path.join(save_dir, f"{name}_saxs_weights.npy"), weights)                      # float64 [n_theta, E * B]
+                np.save(os.path.join(save_dir, f"{name}_saxs_reweighted.npy"), rw_mean)                   # float64 [n_theta, N_Q]
         if pr is not None:
             np.save(os.path.join(save_dir, f"{name}_pr.npy"), pr["P"].cpu().numpy())                      # float64 [E * B, BINS]
             np.save(os.path.join(save_dir, f"{name}_pr_r.npy"), pr["r"].cpu().numpy())                    # float64 [BINS]
@@ -1166,6 +1212,14 @@ if __name__ == "__main__":
                    help="an experimental curve for --saxs: three whitespace-separated columns q (1/A), I, sigma, `#` starts a "
                         "comment.  Its q values replace the grid of --saxs (there is no interpolation); the scale and the "
                         "reduced chi^2 of the ensemble mean against it are printed")
+    p.add_argument("--saxs_reweight", nargs="*", type=float, default=None, metavar="THETA",
+                   help="with --saxs and --saxs_data: reweight the written structures so that their weighted mean profile agrees "
+                        "with the curve while staying close to uniform weights (maximum entropy / BME, metrics.saxs_reweight; the "
+                        "scale of the intensities is fitted along), once per THETA: a large THETA keeps the ensemble as it is, a "
+                        "small one trusts the data.  Prints chi^2 before and after, the kept share phi_eff, the scale and the "
+                        "status per THETA - the L-curve to pick THETA from; saves <name>_saxs_weights.npy float64 [n_theta, "
+                        "structures] and <name>_saxs_reweighted.npy [n_theta, N_Q].  With --saxs_hydration the hydrated profiles "
+                        "are reweighted")
     p.add_argument("--saxs_hydration", nargs="*", type=float, default=None, metavar="C",
                    help="with --saxs: add the hydration shell and the excluded-volume scale to the profile (metrics.saxs_partials, "
                         "saxs_combine): C1 C2 = the scale of the atomic volumes (1 = as --saxs alone) and the weight of the bound "
