@@ -131,6 +131,8 @@ SAXS_X_MAX, SAXS_X_SMALL, SAXS_SIN_ULPS = 25600.0, 0.125, 5   # CODLAD_SAXS_X_MA
 SAXS_HYD_PARTIALS, SAXS_HYD_Q_CHUNK, SAXS_HYD_MAX_GRID = 6, 8, 4096   # CODLAD_SAXS_HYD_PARTIALS, _Q_CHUNK, _MAX_GRID
 PAIR_HIST_MAX_BINS, PAIR_HIST_MAX_ATOMS, PAIR_HIST_ITEM_WORDS, PAIR_HIST_ROWS = 4096, 65535, 5, 64   # CODLAD_PAIR_HIST_*
 REWEIGHT_LADDER, REWEIGHT_SCALARS, REWEIGHT_MAX_PROBLEMS, REWEIGHT_MAX_ITER = 16, 4, 4096, 1000   # CODLAD_REWEIGHT_*
+CLUSTER_MAX_N, CLUSTER_MAX_ROUNDS, CLUSTER_STATE_WORDS = 65536, 4096, 8   # CODLAD_CLUSTER_MAX_N, _MAX_ROUNDS, _STATE_WORDS
+CLUSTER_ST_PHASE, CLUSTER_ST_ACTIVE, CLUSTER_ST_CLUSTERS, CLUSTER_ST_ROUNDS = 0, 1, 2, 3   # CODLAD_CLUSTER_ST_*
 REWEIGHT_STATUS = ("converged", "cap", "stalled", "failed", "none")   # CODLAD_REWEIGHT_CONVERGED .. _NONE = 0 .. 4
 ODE_NORM_WORDS = 257                                   # CODLAD_ODE_NORM_WORDS
 
@@ -168,6 +170,11 @@ _SIGS = {
     "codlad_reweight_solve": (C.c_int, [P, P, P, P, C.c_int, C.c_int, P, P, C.c_int, P, C.c_double, C.c_int, P, C.c_longlong] +
                               [P] * 8),
     "codlad_weighted_mean": (C.c_int, [P, P, C.c_int, C.c_int, C.c_int, P, P]),
+    "codlad_rmsd_matrix_scratch_bytes": (C.c_longlong, [C.c_int] * 2),
+    "codlad_rmsd_matrix": (C.c_int, [P, P, C.c_int, C.c_int, P, C.c_int, C.c_double, C.c_int, P, P, P, P, P]),
+    "codlad_cluster_scratch_bytes": (C.c_longlong, [C.c_int]),
+    "codlad_cluster_daura": (C.c_int, [P, P, C.c_int, C.c_int, P, P, P, P, P, P]),
+    "codlad_cluster_populations": (C.c_int, [P, P, C.c_int, C.c_int, P, P]),
     "codlad_last_error": (C.c_char_p, []),
     "codlad_struct_sizes": (None, [C.POINTER(C.c_int)]),
     "codlad_pack_block_host": (None, [P, C.c_int, C.c_float, P]),

@@ -1333,6 +1333,56 @@ int codlad_reweight_solve(const double *Y, const double *y, const double *sigma,
 int codlad_weighted_mean(const double *values, const double *w, int n_struct, int n_values, int n_sets, double *out,
                          void *stream);
 
+/* Clustering of an ensemble (csrc/cluster_kernels.hip).  Added to ABI version 19 without changing the number: five new
+ * entry points, no existing signature, struct or option changes.
+ *
+ * codlad_rmsd_matrix: the superposed MSD of every pair of the N conformations of ONE pool x [N][n_atoms][3] (device fp32)
+ * over the atoms sel [n_sel] (NULL with n_sel 0: all), mom from codlad_ens_moments with the same sel.  1 <= N <=
+ * CODLAD_CLUSTER_MAX_N.  The nine sums of every pair are one float64 matrix product (v_mfma_f64_16x16x4_f64 over the
+ * centred coordinates, atoms in ascending order in blocks of 4), the tail is the one of codlad_ens_pair_msd (msd = max(Ga
+ * + Gb - 2 lambda, 0) / n); the bits are NOT codlad_ens_pair_msd's, whose sums have another order.  msd_ij is a function
+ * of the coordinates of i and j alone, and a replay is bit-identical.
+ *   msd     device double [N][N] or NULL: the msd (squared != 0) or its square root; symmetric to the bit, the diagonal 0;
+ *           the row and the column of a structure that is not finite, diagonal included, NaN
+ *   bits    device uint64 [N][W], W = ceil(N / 64), or NULL: bit j & 63 of word j >> 6 of row i is set iff both structures
+ *           are finite and msd_ij <= cut2 (the SQUARED cut-off, a finite number >= 0; no square root in the decision); the
+ *           diagonal bit of a finite structure is set; bits at j >= N are 0.  With msd NULL no N x N table exists.
+ *   finite  device uint8 [N]: 0 for a structure with a NaN or an infinity among its selected atoms
+ *   scratch device, codlad_rmsd_matrix_scratch_bytes(N, n_sel) bytes (n_sel = the atoms summed over; written before read)
+ * At least one of msd and bits is given.  A null pointer otherwise, a size outside its range, sel and n_sel that disagree
+ * or a cut2 that is not finite and >= 0 returns -1 (codlad_last_error) before any launch; the scratch size likewise.
+ *
+ * codlad_cluster_daura: Daura's (GROMOS) clustering of N structures from such a bitmap (any bitmap may be given: row i
+ * lists the neighbours of i; the diagonal bit is taken as set and bits at j >= N are ignored).  Among the active
+ * structures - at the start those whose finite byte is not 0, all when finite is NULL - the one with the most active
+ * neighbours, itself included, the lowest index among equals, is the centre of the next cluster; it and its active
+ * neighbours are the members and leave the pool; until the pool is empty.  state, device int32
+ * [CODLAD_CLUSTER_STATE_WORDS], is zeroed by the caller before the first call: a call enqueues the set-up, which runs
+ * only when the state says new (phase 0), then `rounds` rounds (0 .. CODLAD_CLUSTER_MAX_ROUNDS) of two launches - pick
+ * and update - and never waits; every launch of a finished problem returns at once.  A pick whose maximum is 1 numbers
+ * every structure left as its own cluster in ascending order and finishes.  The caller repeats the call until
+ * state[CODLAD_CLUSTER_ST_ACTIVE] is 0 (with phase 3).  labels int32 [N]: the cluster of every structure in the order
+ * the clusters were picked, -1 for one that was never active; centres, sizes int32 [N], of which the first
+ * state[CODLAD_CLUSTER_ST_CLUSTERS] are written; scratch: codlad_cluster_scratch_bytes(N) bytes, the same over the calls
+ * of one problem.  Integer arithmetic only, no atomics.
+ *
+ * codlad_cluster_populations: pop [K] (device double) = the weights w [N] (device double) of the structures labelled k
+ * added to 0 in ascending index; label -1 is skipped.  1 <= K <= N. */
+#define CODLAD_CLUSTER_MAX_N 65536
+#define CODLAD_CLUSTER_MAX_ROUNDS 4096
+#define CODLAD_CLUSTER_STATE_WORDS 8
+#define CODLAD_CLUSTER_ST_PHASE 0
+#define CODLAD_CLUSTER_ST_ACTIVE 1
+#define CODLAD_CLUSTER_ST_CLUSTERS 2
+#define CODLAD_CLUSTER_ST_ROUNDS 3
+long long codlad_rmsd_matrix_scratch_bytes(int N, int n_sel);
+int codlad_rmsd_matrix(const float *x, const double *mom, int N, int n_atoms, const int32_t *sel, int n_sel, double cut2,
+                       int squared, double *msd, uint64_t *bits, uint8_t *finite, void *scratch, void *stream);
+long long codlad_cluster_scratch_bytes(int N);
+int codlad_cluster_daura(const uint64_t *bits, const uint8_t *finite, int N, int rounds, int32_t *state, int32_t *labels,
+                         int32_t *centres, int32_t *sizes, void *scratch, void *stream);
+int codlad_cluster_populations(const int32_t *labels, const double *w, int N, int K, double *pop, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -53,6 +53,8 @@ all atom pairs, united-atom form factors in a displaced solvent) on N_Q points o
 --saxs_data (metrics.saxs_partials, saxs_hydration_fit).
 `--saxs_reweight THETA [THETA ...]` (with --saxs and --saxs_data) reweights the written structures against the curve by
 maximum entropy at every THETA (metrics.saxs_reweight, the scale fitted along) and prints the L-curve.
+`--cluster CUTOFF` clusters the written structures of every data file (Daura / GROMOS, metrics.cluster) at the RMSD
+CUTOFF in A over the CA atoms (`--cluster_atoms all`: every atom).
 Addition: `--pr [DR]` (opt-in, wherever --observables is allowed; after --relax when both are given) computes the pair
 distribution P(r) of every written structure on the device (metrics.pair_distribution: the typed pair-distance histogram
 in bins of DR A, default 0.5, weighted with the forward amplitudes) and prints D_max, the real-space Rg and the number of
@@ -304,6 +306,35 @@ def check_saxs_reweight(args):
             raise SystemExit(f"--saxs_reweight: every THETA must be a positive finite number, got {t}")
     args.saxs_reweight = tuple(float(t) for t in v)
     return args.saxs_reweight
+
+
+def check_cluster(args):
+    """--cluster CUTOFF: a positive finite RMSD in A; it describes generated structures.  Returns the cut-off, 0 = off."""
+    c = getattr(args, "cluster", None)
+    if c is None:
+        args.cluster = 0.0
+        return 0.0
+    if not (np.isfinite(c) and c > 0):
+        raise SystemExit(f"--cluster takes an RMSD cut-off in A, a positive number, got {c}")
+    if getattr(args, "experiment", "latent") in ("bpd", "fmloss"):
+        raise SystemExit(f"--cluster describes generated structures: --experiment {args.experiment} generates none")
+    return c
+
+
+def cluster_report(name, cl):
+    """The printed summary of --cluster for one output file (cl: metrics.cluster's dict) -> the stats."""
+    pop = cl["populations"].cpu().numpy()
+    cr = cl["centre_rmsd"][cl["labels"] >= 0]
+    stats = {"data_name": name, "structures": int(cl["labels"].shape[0]), "cluster_non_finite": int((cl["labels"] < 0).sum()),
+             "clusters": int(cl["n_clusters"]), "cluster_top5_share": float(pop[:5].sum()) if pop.size else float("nan"),
+             "cluster_centre_rmsd_mean": float(cr.mean()) if cr.numel() else float("nan")}
+    print("############## vvvvvvvvv clustering (Daura / GROMOS; RMSD in A):")
+    print(f"{stats['clusters']} clusters of {stats['structures']} structures   share of the largest five "
+          f"{stats['cluster_top5_share']:.3f}   mean RMSD to the centre {stats['cluster_centre_rmsd_mean']:.3f}")
+    for k, v in stats.items():
+        print(k, v)
+    print("############## ^^^^^^^^^ clustering")
+    return stats
 
 
 def saxs_reweight_report(name, sx, data, thetas):
@@ -824,6 +855,7 @@ def main(args):
     check_saxs_hydration(args)
     check_saxs_reweight(args)
     check_pr(args)
+    check_cluster(args)
     check_dssp(args)
     check_sampler(args)
     saxs_data = read_saxs_data(args.saxs_data) if getattr(args, "saxs_data", None) else None
@@ -1033,6 +1065,14 @@ def main(args):
                 pr = metrics.pair_distribution(xyz.reshape(-1, xyz.shape[2], 3), _GEOMETRY_TOP[name], dr=args.pr)   # the written coordinates
             except ValueError as e:                               # more bins than the kernel holds: a wider bin is the way out
                 raise SystemExit(f"--pr {args.pr}: {e}") from None
+        cl = None
+        if getattr(args, "cluster", 0):
+            cl_sel = None
+            if getattr(args, "cluster_atoms", "ca") == "ca":
+                cl_sel = ca_indices(_TOPOLOGY[name]) if name in _TOPOLOGY else None
+                if not cl_sel:
+                    raise SystemExit(f"--cluster: the CA atoms of {name} are not known on this input route (use --cluster_atoms all)")
+            cl = metrics.cluster(xyz.reshape(-1, xyz.shape[2], 3), args.cluster, sel=cl_sel)    # members x frames: one pool
         sec = None
         if getattr(args, "dssp", False):
             if name not in _GEOMETRY_TOP:
@@ -1084,6 +1124,15 @@ def main(args):
             np.save(os.path.join(save_dir, f"{name}_pr.npy"), pr["P"].cpu().numpy())                      # float64 [E * B, BINS]
             np.save(os.path.join(save_dir, f"{name}_pr_r.npy"), pr["r"].cpu().numpy())                    # float64 [BINS]
             pr_report(name, pr)
+        if cl is not None:
+            np.save(os.path.join(save_dir, f"{name}_cluster_labels.npy"), cl["labels"].cpu().numpy())     # int32 [E * B], -1 = not finite
+            np.save(os.path.join(save_dir, f"{name}_cluster_centres.npy"), cl["centres"].cpu().numpy())   # int32 [K]: indices into the pool
+            np.save(os.path.join(save_dir, f"{name}_cluster_sizes.npy"), cl["sizes"].cpu().numpy())       # int32 [K]
+            cluster_report(name, cl)
+            if getattr(args, "save_pdb", False) and name in _TOPOLOGY and cl["n_clusters"]:
+                from codlad_amd.utils.protein_module import write_pdb
+                centres = xyz.reshape(-1, xyz.shape[2], 3)[cl["centres"].to(torch.int64)].cpu().numpy()
+                write_pdb(os.path.join(save_dir, f"cluster_centres_{name}.pdb"), centres, *_TOPOLOGY[name])
         if sec is not None:
             np.save(os.path.join(save_dir, f"{name}_dssp.npy"), sec["ss"].cpu().numpy())                  # uint8 [E * B, R]
             np.save(os.path.join(save_dir, f"{name}_dssp_propensity.npy"), sec_prop.cpu().numpy())       # float64 [R, 8]
@@ -1233,6 +1282,15 @@ if __name__ == "__main__":
                         "(default 0.5) up to the contour-length bound of the topology, weighted with the forward amplitudes "
                         "(metrics.pair_distribution).  Prints D_max, the real-space Rg and the number of structures with pairs "
                         "beyond the bound; saves <name>_pr.npy float64 [structures, BINS] and <name>_pr_r.npy (the bin centres)")
+    p.add_argument("--cluster", type=float, default=None, metavar="CUTOFF",
+                   help="cluster the written structures of every data file, members x frames as one pool, on the device (Daura / "
+                        "GROMOS, metrics.cluster; after --relax when both are given): structures within the RMSD CUTOFF in A "
+                        "of a centre, after superposition, form its cluster.  Prints the number of clusters, the share of the "
+                        "largest five and the mean RMSD to the centre; saves <name>_cluster_labels.npy int32 [structures] "
+                        "(-1 = a structure that is not finite), <name>_cluster_centres.npy (indices into the pool) and "
+                        "<name>_cluster_sizes.npy; with --save_pdb also cluster_centres_<name>.pdb, one model per centre")
+    p.add_argument("--cluster_atoms", choices=("ca", "all"), default="ca",
+                   help="the atoms --cluster superposes and measures: the CA atoms (default) or every written atom")
     p.add_argument("--dssp", action="store_true",
                    help="also assign the secondary structure of every written structure on the device (allowed wherever "
                         "--geometry_check is; after --relax when both are given): Kabsch-Sander hydrogen bonds and the DSSP "
