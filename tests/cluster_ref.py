@@ -12,6 +12,7 @@ import numpy as np
 from tests import ensemble_ref as er
 
 PLANTED_CUTOFF, CONTINUUM_CUTOFF = 1.0, 2.0
+MAX_N = 65536                                             # CODLAD_CLUSTER_MAX_N
 POOL_SIZES = (1, 2, 15, 16, 17, 63, 64, 65, 130)          # at n = 65
 ATOM_COUNTS = (1, 2, 3, 4, 5, 63, 64, 65, 257, 1000)      # at N = 17
 LARGE = (1025, 5)
@@ -134,6 +135,78 @@ def daura(nb, finite=None):
         sizes.append(int(members.sum()))
         active &= ~members
     return dict(labels=labels, centres=np.array(centres, dtype=np.int32), sizes=np.array(sizes, dtype=np.int32), n_clusters=len(centres))
+
+
+# ------------------------------------------------------------------------------------------ block-structured bitmaps --
+def clique_members(cliques):
+    """A clique is (first index, size) - consecutive structures - or an explicit list of indices -> a list of sorted lists."""
+    out = [list(range(c[0], c[0] + c[1])) if isinstance(c, tuple) else sorted(int(i) for i in c) for c in cliques]
+    flat = [i for m in out for i in m]
+    assert len(flat) == len(set(flat)), "the cliques overlap"
+    return out
+
+
+def clique_matrix(N, cliques):
+    """bool [N, N]: every member of a clique is the neighbour of every other; nothing else is set (no diagonal either)."""
+    nb = np.zeros((N, N), dtype=bool)
+    for m in clique_members(cliques):
+        nb[np.ix_(m, m)] = True
+    nb[np.arange(N), np.arange(N)] = False
+    return nb
+
+
+def clique_answer(N, cliques, finite=None):
+    """Daura's rule on clique_matrix in closed form: among disjoint cliques a structure counts the members of its own
+    clique that are still in the pool, so the cliques leave in descending size (of their finite members), the one with the
+    lowest first finite member among equals, each centred on that member; when the largest count is 1 the closing launch
+    numbers what is left - the structures of no clique and the cliques of one finite member - in ascending order.
+    -> daura()'s dict plus rounds, the picks it took."""
+    fin = np.ones(N, dtype=bool) if finite is None else np.asarray(finite, dtype=bool)
+    groups = [[i for i in m if fin[i]] for m in clique_members(cliques)]
+    big = sorted((g for g in groups if len(g) > 1), key=lambda g: (-len(g), g[0]))
+    labels = np.full(N, -1, dtype=np.int32)
+    for k, g in enumerate(big):
+        labels[g] = k
+    rest = np.nonzero(fin & (labels < 0))[0]
+    labels[rest] = len(big) + np.arange(rest.shape[0])
+    centres = np.array([g[0] for g in big] + rest.tolist(), dtype=np.int32)
+    sizes = np.array([len(g) for g in big] + [1] * rest.shape[0], dtype=np.int32)
+    return dict(labels=labels, centres=centres, sizes=sizes, n_clusters=int(centres.shape[0]),
+                rounds=len(big) + (1 if rest.shape[0] else 0))
+
+
+def limit_cliques(N, fill=False):
+    """The cliques of the size-limit cases (tests/test_size_limits.py) for a pool of N structures, W = ceil(N / 64) words:
+    cliques across the borders of the words 0, 63, 64, W / 2 - 1 and W - 1 (where N has them), one of the last structure
+    with members of word 0, a run of pairs (more non-singleton cliques than one batch of rounds), and equal sizes with
+    the lower first index winning.  Everything else is a singleton - or, with fill, all but every 41st of the rest goes
+    into cliques of 389 that reach over six or seven words each (the plain loop takes a pass over the matrix per cluster:
+    thousands of singletons are for the closed form alone)."""
+    W = (N + 63) // 64
+    out = [[0, 1, 2, N - 1]]                                        # the last structure with three of word 0
+    used = {0, 1, 2, N - 1}
+
+    def add(first, size):
+        idx = [i for i in range(first, first + size) if 0 <= i < N and i not in used]
+        if len(idx) > 1:
+            out.append(idx)
+            used.update(idx)
+
+    for w, size in ((1, 9), (63, 7), (64, 11), (65, 5), (W // 2, 13), (W - 1, 6)):      # across the border before word w
+        if 1 <= w < W:
+            add(64 * w - size // 2, size)
+    add(64 * (W - 1) - 40, 5)                                       # inside the word before the last: equal in size to (65, 5)
+    add(10, 30)                                                     # the largest, inside word 0
+    # four inside word 4: it ties with the first clique, which must win on its lower index - and loses to this one as soon
+    # as a count leaves out the last word, where the first clique has its fourth member
+    add(300, 4)
+    for k in range(80):                                             # pairs: a second batch of rounds
+        add(N // 3 + 3 * k if N < 2000 else 1000 + 37 * k, 2)
+    if fill:
+        free = [i for i in range(N) if i not in used]
+        rest = [i for k, i in enumerate(free) if k % 41]            # every 41st of them stays a singleton
+        out += [rest[a:a + 389] for a in range(0, len(rest), 389) if len(rest[a:a + 389]) > 1]
+    return out
 
 
 def from_edges(N, edges):

@@ -21,6 +21,7 @@ from tests import stereo_ref as sr
 CODES = " HBEGITS"
 LOOP, H, B, E, G, I, T, S = range(8)
 UNDEFINED = 255
+MAX_RES = 4096                                   # CODLAD_DSSP_MAX_RES
 KIND_PRO, KIND_CHAIN_START = 1, 2
 GEOM_LINK, GEOM_BEND = 1, 2
 KS_Q, E_MIN, E_BOND, R_MIN, LINK_MAX, BEND_ABOVE = 27.888, -9.9, -0.5, 0.5, 2.5, 70.0
@@ -149,11 +150,20 @@ def unpack_bits(words, R):
 
 
 # ---------------------------------------------------------------------------------------------------------- stage 2
-def assign(hb, link, bend):
+def assign(hb, link, bend, sparse=False):
     """hb bool [R, R] (hb[i, j] = Hbond(i -> j)), link bool [R] (r to r+1), bend bool [R] -> (ss uint8 [R], bridge int32
-    [R, 2], counts int32 [8]).  Plain loops, in the order of the rule."""
+    [R, 2], counts int32 [8]).  Plain loops, in the order of the rule.  sparse: the bridge loop of residue i visits only
+    the j that can pass its test - every term of Bridge(i, j) is a bond between one of i - 1, i, i + 1 and one of j - 1, j,
+    j + 1 - which makes R = 4096 a matter of seconds; tests/test_size_limits_host.py holds it to the full loop."""
     hb, link, bend = np.asarray(hb, bool), np.asarray(link, bool), np.asarray(bend, bool)
     R = hb.shape[0]
+
+    def partners(i):
+        if not sparse:
+            return range(R)
+        rows = slice(max(i - 1, 0), i + 2)
+        near = np.nonzero(hb[rows].any(0) | hb[:, rows].any(1))[0]
+        return sorted({int(j) + d for j in near for d in (-1, 0, 1) if 0 <= j + d < R})
 
     def bond(i, j):
         return 0 <= i < R and 0 <= j < R and bool(hb[i, j])
@@ -171,7 +181,7 @@ def assign(hb, link, bend):
     for i in range(R):
         if not (lk(i - 1) and lk(i)):
             continue
-        for j in range(R):
+        for j in partners(i):
             if abs(i - j) < 3 or not (lk(j - 1) and lk(j)):
                 continue
             if (bond(i - 1, j) and bond(j, i + 1)) or (bond(j - 1, i) and bond(i, j + 1)):
@@ -206,14 +216,14 @@ def assign(hb, link, bend):
     return ss, bridge.reshape(R, 2), np.bincount(ss, minlength=8).astype(np.int32)
 
 
-def assign_batch(hb, geom, finite):
+def assign_batch(hb, geom, finite, sparse=False):
     """The pattern stage for S structures from bitmaps-as-matrices hb [S, R, R], geom [S, R], finite [S]."""
     S_, R = geom.shape
     ss, bridge, counts = (np.full((S_, R), UNDEFINED, np.uint8), np.full((S_, R, 2), -1, np.int32),
                           np.full((S_, 8), -1, np.int32))
     for s in range(S_):
         if finite[s]:
-            ss[s], bridge[s], counts[s] = assign(hb[s], (geom[s] & GEOM_LINK) > 0, (geom[s] & GEOM_BEND) > 0)
+            ss[s], bridge[s], counts[s] = assign(hb[s], (geom[s] & GEOM_LINK) > 0, (geom[s] & GEOM_BEND) > 0, sparse)
     return ss, bridge, counts
 
 
@@ -328,7 +338,10 @@ def planted():
 # cases by size: what the first stage is held to on the device
 SIZES = (5, 63, 64, 65, 130)
 NOISE, NOISE_COPIES = 0.3, 4
-SIZED_SEED = {5: 1, 63: 1, 64: 1, 65: 1, 130: 1}
+SIZED_SEED = {5: 1, 63: 1, 64: 1, 65: 1, 130: 1, 257: 1, 513: 1, 1025: 1, 4096: 1}
+# beyond one trip of the kernels' per-residue loops (256 threads), and CODLAD_DSSP_MAX_RES itself (tests/test_size_limits.py):
+# size -> noisy copies beside the planted structure.  4096 takes 2 GB of host memory per structure in margins()
+LIMIT_SIZES = {257: NOISE_COPIES, 1025: NOISE_COPIES, 4096: 1}
 
 
 @functools.lru_cache(maxsize=None)
@@ -365,6 +378,16 @@ def noisy(x, seed, copies=NOISE_COPIES):
     """float32 [copies, n_atoms, 3]: x + N(0, NOISE A) per coordinate."""
     rng = np.random.default_rng(seed)
     return (x[None].astype(np.float64) + rng.normal(0.0, NOISE, (copies,) + x.shape)).astype(np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def limit_call(R):
+    """The inputs of one call at a size of LIMIT_SIZES, with the references: (Topology, xyz [1 + copies, n_atoms, 3] read-only,
+    margins).  Computed once per session."""
+    top, x = sized(R)
+    xyz = np.concatenate([x[None], noisy(x, 7 * R, LIMIT_SIZES[R])])
+    xyz.setflags(write=False)
+    return top, xyz, margins(xyz, top)
 
 
 def margins(xyz, top):
@@ -431,6 +454,60 @@ def handmade(R):
     hb[30, 34] = True
     bend[32] = bend[45] = True
     checks.update({30: " ", 31: "T", 32: "T", 33: "T", 34: " ", 45: "S"})
+    return hb, link, bend, checks
+
+
+HIGH_KINDS = ("a", "b")
+
+
+def handmade_high(R, kind):
+    """R >= 4040, kind "a" or "b" -> (hb, link, bend, checks) as handmade(): the word logic at high word indices and the
+    borders between the trips of the kernel's per-residue loops (256 residues a trip).
+      a: an antiparallel ladder between word 0 and words 62 / 63 whose partners straddle bits 4031 / 4032, a parallel one
+         whose partners straddle 255 / 256, a G run across 511 / 512, an I run across 767 / 768, an H run across 1023 / 1024
+      b: the parallel ladder at 4031 / 4032 and the antiparallel one at 1279 / 1280, an H run across 255 / 256 and one across
+         2047 / 2048, a G run across 511 / 512, a lone 4-turn at 767 whose T lie in the next trip (768 .. 770, a bend inside
+         it stays T), a bend that gives S at 3000"""
+    assert R >= 4040 and kind in HIGH_KINDS
+    b_anti, b_par = (4032, 256) if kind == "a" else (1280, 4032)
+    hb = np.zeros((R, R), bool)
+    link = np.ones(R, bool)
+    link[R - 1] = False
+    bend = np.zeros(R, bool)
+    checks = {}
+    # the two ladders of handmade(): rows 10 .. 16 and 20 .. 24, both in word 0
+    for k in (0, 2, 4, 6):
+        i, j = 10 + k, b_anti + 2 - k
+        hb[i, j] = hb[j, i] = True
+    for k in range(7):
+        checks[10 + k] = checks[b_anti + 2 - k] = "E"
+    checks[9] = checks[17] = checks[b_anti + 3] = checks[b_anti - 5] = " "
+    for k in (0, 2, 4):
+        i, j = 20 + k, b_par - 4 + k
+        hb[i - 1, j] = hb[j, i + 1] = True
+    for k in range(5):
+        checks[20 + k] = checks[b_par - 4 + k] = "E"
+    checks[b_par - 5] = checks[b_par + 1] = " "
+
+    def run(first, last, n, code):
+        """n-turns at first .. last: the run of `code` over first + 1 .. last + n - 1, loop on both sides of the turns' reach."""
+        for i in range(first, last + 1):
+            hb[i, i + n] = True
+        checks.update({r: code for r in range(first + 1, last + n)})
+        checks[first] = " "
+        checks[last + n] = " "
+
+    if kind == "a":
+        run(508, 512, 3, "G")
+        run(764, 768, 5, "I")
+        run(1019, 1027, 4, "H")
+    else:
+        run(250, 258, 4, "H")
+        run(508, 512, 3, "G")
+        run(2043, 2051, 4, "H")
+        hb[767, 771] = True                    # a lone 4-turn: T 768 .. 770
+        bend[769] = bend[3000] = True
+        checks.update({767: " ", 768: "T", 769: "T", 770: "T", 771: " ", 3000: "S"})
     return hb, link, bend, checks
 
 

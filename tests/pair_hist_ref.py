@@ -223,6 +223,27 @@ def case(key):
                            d64=d64))
 
 
+def lattice(n):
+    """n atoms of one type at (i, 0, 0), float32 [1, n, 3]."""
+    x = np.zeros((1, n, 3), dtype=F)
+    x[0, :, 0] = np.arange(n, dtype=F)
+    return x
+
+
+def lattice_hist(n, dr, B):
+    """The histogram of lattice(n) at an integer bin width dr in closed form -> (H int64 [B], over int, d_bin): there are
+    n - d pairs at distance d = 1 .. n - 1 and bin b holds the distances dr b .. dr b + dr - 1.  For n <= 65535 and dr a
+    power of two the header's fp32 sequence gives exactly d / dr: dx = d is a float32 number, dx * dx is d^2 (1 + e) with
+    |e| < 2^-24, its correctly rounded root lies within d 2^-25 of d, less than half a unit in the last place of d, so it
+    IS d; and d * (1 / dr) is exact (tests/test_size_limits_host.py runs this sequence in numpy for every d)."""
+    d = np.arange(1, n, dtype=np.int64)
+    count = n - d
+    inside = d // dr < B
+    H = np.bincount(d[inside] // dr, weights=count[inside], minlength=B).astype(np.int64)
+    occupied = np.nonzero(H)[0]
+    return H, int(count[~inside].sum()), int(occupied[-1]) if occupied.size else -1
+
+
 def sandwich(H, c_of_pair, ts64, delta, B):
     """For every class and every bin edge b = 0 .. B: #64{t < b - delta} <= sum_{bin < b} H[c] <= #64{t < b + delta}.
     H [C, B] of one structure -> the number of (class, edge) pairs that break it."""
