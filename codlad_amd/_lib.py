@@ -133,6 +133,10 @@ PAIR_HIST_MAX_BINS, PAIR_HIST_MAX_ATOMS, PAIR_HIST_ITEM_WORDS, PAIR_HIST_ROWS = 
 REWEIGHT_LADDER, REWEIGHT_SCALARS, REWEIGHT_MAX_PROBLEMS, REWEIGHT_MAX_ITER = 16, 4, 4096, 1000   # CODLAD_REWEIGHT_*
 CLUSTER_MAX_N, CLUSTER_MAX_ROUNDS, CLUSTER_STATE_WORDS = 65536, 4096, 8   # CODLAD_CLUSTER_MAX_N, _MAX_ROUNDS, _STATE_WORDS
 CLUSTER_ST_PHASE, CLUSTER_ST_ACTIVE, CLUSTER_ST_CLUSTERS, CLUSTER_ST_ROUNDS = 0, 1, 2, 3   # CODLAD_CLUSTER_ST_*
+PCA_MAX_N, PCA_MAX_DIM, PCA_MAX_COMPONENTS, PCA_MAX_ITER = 65536, 4096, 64, 4096   # CODLAD_PCA_MAX_*
+PCA_STATE_WORDS, PCA_ST_PHASE, PCA_ST_ITER, PCA_ST_STATUS, PCA_ST_START = 8, 0, 1, 2, 3   # CODLAD_PCA_STATE_WORDS, _ST_*
+PCA_SCALARS, PCA_SC_W, PCA_SC_STEP = 4, 0, 1           # CODLAD_PCA_SCALARS, _SC_*
+PCA_STATUS = ("converged", "limit", "no_weight")       # CODLAD_PCA_CONVERGED, _LIMIT, _NO_WEIGHT = 0 .. 2
 REWEIGHT_STATUS = ("converged", "cap", "stalled", "failed", "none")   # CODLAD_REWEIGHT_CONVERGED .. _NONE = 0 .. 4
 ODE_NORM_WORDS = 257                                   # CODLAD_ODE_NORM_WORDS
 
@@ -175,6 +179,15 @@ _SIGS = {
     "codlad_cluster_scratch_bytes": (C.c_longlong, [C.c_int]),
     "codlad_cluster_daura": (C.c_int, [P, P, C.c_int, C.c_int, P, P, P, P, P, P]),
     "codlad_cluster_populations": (C.c_int, [P, P, C.c_int, C.c_int, P, P]),
+    "codlad_pca_fit_scratch_bytes": (C.c_longlong, [C.c_int] * 2),
+    "codlad_pca_fit": (C.c_int, [P, P, C.c_int, C.c_int, P, C.c_int, P, C.c_int, C.c_double, C.c_int, C.c_int] + [P] * 8),
+    "codlad_pca_align": (C.c_int, [P, P, C.c_int, C.c_int, P, C.c_int, P, P, P, P, P]),
+    "codlad_pca_deviations": (C.c_int, [P, P, P, P, C.c_int, C.c_int, P, C.c_int, P, P, P, P, P]),
+    "codlad_pca_covariance_scratch_bytes": (C.c_longlong, [C.c_int] * 2),
+    "codlad_pca_covariance": (C.c_int, [P, P, P, C.c_int, C.c_int, P, P, P, P, P, P]),
+    "codlad_pca_eigen_scratch_bytes": (C.c_longlong, [C.c_int] * 2),
+    "codlad_pca_eigen": (C.c_int, [P, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, P, P, P, P, P, P]),
+    "codlad_pca_project": (C.c_int, [P, P, C.c_int, C.c_int, C.c_int, P, P]),
     "codlad_last_error": (C.c_char_p, []),
     "codlad_struct_sizes": (None, [C.POINTER(C.c_int)]),
     "codlad_pack_block_host": (None, [P, C.c_int, C.c_float, P]),

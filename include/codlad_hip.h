@@ -1383,6 +1383,109 @@ int codlad_cluster_daura(const uint64_t *bits, const uint8_t *finite, int N, int
                          int32_t *centres, int32_t *sizes, void *scratch, void *stream);
 int codlad_cluster_populations(const int32_t *labels, const double *w, int N, int K, double *pop, void *stream);
 
+/* Essential dynamics of an ensemble (csrc/pca_kernels.hip): the mean structure after mutual superposition, the deviations
+ * from it and their RMSF, the covariance of the aligned coordinates, its largest eigenpairs, the projections.  Added to ABI
+ * version 19 without changing the number: nine new entry points, no existing signature, struct or option changes.
+ *
+ * Input: ONE pool x [N][n_atoms][3] (device fp32), 1 <= N <= CODLAD_PCA_MAX_N; the atoms sel [n_sel] (NULL with n_sel 0:
+ * all), m of them, d = 3 m; mom from codlad_ens_moments with the same sel; weights w [N] (device double, finite and >= 0,
+ * which the CALLER checks; NULL: all 1).  The mean and the RMSF take any m; the covariance and what follows it take d <=
+ * CODLAD_PCA_MAX_DIM.  A structure with a NaN or an infinity among its selected atoms has finite = 0, takes part with
+ * weight exactly 0 (it is skipped in every sum, as is a structure whose weight is 0) and gets NaN in its own rows of Rt, D
+ * and the projections; the other structures' results do not depend on what it holds.  W = the weights of the finite
+ * structures added to 0 in ascending index.
+ *
+ * codlad_pca_fit: the mean structure by generalised Procrustes.  M_0 = structure `start` minus its centroid (start -1: the
+ * first finite structure of positive weight).  Iteration t: every structure is superposed on M_{t-1} over sel - proper
+ * rotation plus translation, S = sum (x - c)(M - cM)^T with lane l of 256 adding atoms l, l + 256, .. and the lanes added by
+ * codlad_ens_pair_msd's tree, then its Horn tail; the target stays float64 and is never rounded to fp32 - giving A_s = R_s
+ * x_s + t_s (each coordinate ((R0 x + R1 y) + R2 z) + t, codlad_ens_apply's rounding before its conversion);
+ *   M_t = sum_s w_s A_s / W: the structures are cut into at most 32 chunks whose size depends on N alone (n = min(32,
+ *         ceil(N / 512)) chunks, each ceil(N / n) rounded up to a multiple of 16), a chunk is added to 0 in ascending order by
+ *         fused multiply-adds, the chunks are added to 0 in ascending order, then one division
+ *   step_t = sqrt(sum over the 3 m coordinates of (M_t - M_{t-1})^2 / m)
+ * and the fit ends CONVERGED when step_t <= tol, else at LIMIT when t = max_iter.  state, device int32
+ * [CODLAD_PCA_STATE_WORDS], is zeroed by the caller before the first call: a call enqueues the set-up, which runs only when
+ * the state says new (phase 0), then `iters` iterations of three launches, and never waits; every launch of a finished
+ * problem returns at once.  The caller repeats the call until state[CODLAD_PCA_ST_PHASE] is 2, reading one word per call.
+ * Results: mean [m][3] = M_t; target [m][3] = M_{t-1}, what the last alignment superposed on; Rt [N][12] (R row-major, then
+ * t) of the last iteration, so that mean is the weighted average of the A_s of exactly these transforms; finite uint8 [N];
+ * scal double [CODLAD_PCA_SCALARS]: W and the last step; state: the iterations, the status and the start structure.  When
+ * W is 0 or not finite, or `start` names a structure that is not finite or has weight 0, the status is NO_WEIGHT and mean,
+ * target and Rt are NaN.  scratch: codlad_pca_fit_scratch_bytes(N, m) bytes, the same over the calls of one problem.
+ *
+ * codlad_pca_align: the same superposition of every structure of a pool on a given float64 target [m][3] -> Rt, finite;
+ * tmom double [4] receives the target's centroid and sum of squares.
+ *
+ * codlad_pca_deviations: D [N][d] (or NULL) = A_s - mean from the transforms Rt; rmsf [m] (or NULL) = sqrt(sum_s w_s
+ * |D_sk|^2 / W) from its own sum - D recomputed, the structures in ascending order by fused multiply-adds, W = scal[0].
+ *
+ * codlad_pca_covariance: C [d][d] = sum_s w_s D_s D_s^T / W, the POPULATION covariance with divisor W (what GROMACS covar
+ * computes with equal weights: no N - 1).  One float64 matrix product on v_mfma_f64_16x16x4_f64 over 64 x 64 tiles of the
+ * lower triangle; w_s multiplies the COLUMN operand D_sj when it is staged (one rounding), the products of a chunk of
+ * structures (the chunks of the fit) are added in ascending order by the fused multiply-adds of the MFMA, the chunks are
+ * added to 0 in ascending order, then one division; an element and its mirror are written from the one value, so C is
+ * symmetric to the bit.  With T_ij = sum_s w_s |D_si| |D_sj| / W an element is within (c + n + 3) 2^-52 T_ij of the exact
+ * value for chunks of c structures (one rounding for the weight, c for the chunk, n for the chunks, one for the division,
+ * first order), which is at most (N + 34) 2^-52 T_ij.  corr [m][m]: the trace of the 3 x 3 block (a, b) over the root of
+ * the product of the diagonal traces of a and b; its diagonal is exactly 1 where the trace is positive and NaN where it is
+ * 0.  total [1] = trace(C), the diagonal added to 0 in ascending order.  No atomics; a replay returns the same bits.
+ *
+ * codlad_pca_eigen: the k <= min(CODLAD_PCA_MAX_COMPONENTS, d) largest eigenpairs of a symmetric C [d][d] by blocked
+ * subspace iteration on b = min(k + 8, d) columns.  The start block is fixed: entry (column j, row r) = (h >> 8) 2^-24 -
+ * 1/2 with h = r * 2654435761 + j * 40503 + 12345 (mod 2^32); h ^= h >> 15; h *= 2246822519; h ^= h >> 13; h *= 3266489917;
+ * h ^= h >> 16 - no random numbers, so a replay is bit-identical.  A block is orthonormalised column by column by
+ * Gram-Schmidt applied twice (each pass: all dot products with the earlier columns, then the subtractions in ascending
+ * order).  A column has vanished when nothing is left after the first pass, or when the second pass still takes more
+ * than half of the length the first one left; then the unit vectors e_0, e_1, .. in turn (never one twice within a block)
+ * stand in, and the first whose remainder after both passes is at least 1 / 128 long is taken - one exists while fewer
+ * than d columns are placed.  So a rank-deficient C gives orthonormal components and eigenvalues that are zero within
+ * rounding, never NaN.  Iteration: Z = C Q; H = Q^T Z (lower triangle, mirrored); H = S diag(theta) S^T by cyclic Jacobi in
+ * the round-robin order, theta descending; V = Q S, Y = Z S; r_i = |Y_i - theta_i V_i|_2; CONVERGED when r_i <= rtol *
+ * theta_1 for every i < k, else LIMIT at max_iter iterations, else Q = orthonormalised Y.  state as for the fit.  On the
+ * last iteration: evals [k] = theta, comps [k][d] = V_i times the sign that makes its entry of largest magnitude (the
+ * lowest index among equals) positive, resid [k] = r.  scratch: codlad_pca_eigen_scratch_bytes(d, k) bytes.
+ *
+ * codlad_pca_project: P [N][k] = D V^T, element (s, i) the products D_sr V_ir added to 0 in ascending r by fused
+ * multiply-adds.
+ *
+ * Every scratch buffer is written before it is read.  A null pointer (w, sel, and one of D and rmsf excepted), a size
+ * outside its range, sel and n_sel that disagree, a k outside 1 .. min(CODLAD_PCA_MAX_COMPONENTS, d), a tol or rtol that
+ * is not a positive finite number, or an iteration count outside its range returns -1 (codlad_last_error) before any HIP
+ * call; the scratch sizes likewise. */
+#define CODLAD_PCA_MAX_N 65536
+#define CODLAD_PCA_MAX_DIM 4096
+#define CODLAD_PCA_MAX_COMPONENTS 64
+#define CODLAD_PCA_MAX_ITER 4096
+#define CODLAD_PCA_STATE_WORDS 8
+#define CODLAD_PCA_ST_PHASE 0
+#define CODLAD_PCA_ST_ITER 1
+#define CODLAD_PCA_ST_STATUS 2
+#define CODLAD_PCA_ST_START 3
+#define CODLAD_PCA_SCALARS 4
+#define CODLAD_PCA_SC_W 0
+#define CODLAD_PCA_SC_STEP 1
+#define CODLAD_PCA_RUNNING -1
+#define CODLAD_PCA_CONVERGED 0
+#define CODLAD_PCA_LIMIT 1
+#define CODLAD_PCA_NO_WEIGHT 2
+long long codlad_pca_fit_scratch_bytes(int N, int n_sel);
+int codlad_pca_fit(const float *x, const double *mom, int N, int n_atoms, const int32_t *sel, int n_sel, const double *w,
+                   int start, double tol, int max_iter, int iters, int32_t *state, double *scal, double *target, double *mean,
+                   double *Rt, uint8_t *finite, void *scratch, void *stream);
+int codlad_pca_align(const float *x, const double *mom, int N, int n_atoms, const int32_t *sel, int n_sel,
+                     const double *target, double *tmom, double *Rt, uint8_t *finite, void *stream);
+int codlad_pca_deviations(const float *x, const double *Rt, const uint8_t *finite, const double *w, int N, int n_atoms,
+                          const int32_t *sel, int n_sel, const double *mean, const double *scal, double *D, double *rmsf,
+                          void *stream);
+long long codlad_pca_covariance_scratch_bytes(int N, int d);
+int codlad_pca_covariance(const double *D, const double *w, const uint8_t *finite, int N, int d, const double *scal,
+                          double *cov, double *corr, double *total, void *scratch, void *stream);
+long long codlad_pca_eigen_scratch_bytes(int d, int k);
+int codlad_pca_eigen(const double *cov, int d, int k, double rtol, int max_iter, int iters, int32_t *state, double *evals,
+                     double *comps, double *resid, void *scratch, void *stream);
+int codlad_pca_project(const double *D, const double *comps, int N, int d, int k, double *P, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,6 +55,9 @@ all atom pairs, united-atom form factors in a displaced solvent) on N_Q points o
 maximum entropy at every THETA (metrics.saxs_reweight, the scale fitted along) and prints the L-curve.
 `--cluster CUTOFF` clusters the written structures of every data file (Daura / GROMOS, metrics.cluster) at the RMSD
 CUTOFF in A over the CA atoms (`--cluster_atoms all`: every atom).
+`--pca [K]` (default 10) describes how the written structures of every data file move (metrics.pca): the mean structure
+after mutual superposition, the RMSF and the K largest principal components of the covariance, over the CA atoms
+(`--pca_atoms all`: every written atom, while 3 x atoms <= 4096).
 Addition: `--pr [DR]` (opt-in, wherever --observables is allowed; after --relax when both are given) computes the pair
 distribution P(r) of every written structure on the device (metrics.pair_distribution: the typed pair-distance histogram
 in bins of DR A, default 0.5, weighted with the forward amplitudes) and prints D_max, the real-space Rg and the number of
@@ -319,6 +322,54 @@ def check_cluster(args):
     if getattr(args, "experiment", "latent") in ("bpd", "fmloss"):
         raise SystemExit(f"--cluster describes generated structures: --experiment {args.experiment} generates none")
     return c
+
+
+def check_pca(args):
+    """--pca [K]: the number of principal components, 1 .. 64; it describes generated structures.  Returns K, 0 = off."""
+    k = getattr(args, "pca", None)
+    if k is None:
+        args.pca = 0
+        return 0
+    if not 1 <= k <= 64:
+        raise SystemExit(f"--pca takes the number of components, 1 .. 64, got {k}")
+    if getattr(args, "experiment", "latent") in ("bpd", "fmloss"):
+        raise SystemExit(f"--pca describes generated structures: --experiment {args.experiment} generates none")
+    return k
+
+
+def pca_selection(name, n_atoms, atoms, ca):
+    """The atoms --pca runs over for one output file: the CA indices `ca` (atoms "ca") or None for all -> sel; SystemExit
+    when they are not known or hold more coordinates than one covariance takes."""
+    if atoms == "ca":
+        if not ca:
+            raise SystemExit(f"--pca: the CA atoms of {name} are not known on this input route (use --pca_atoms all)")
+        sel = list(ca)
+    else:
+        sel = None
+    m = n_atoms if sel is None else len(sel)
+    if 3 * m > metrics.PCA_MAX_DIM:
+        raise SystemExit(f"--pca: {name} has 3 x {m} = {3 * m} coordinates over the chosen atoms, at most {metrics.PCA_MAX_DIM} "
+                         f"(--pca_atoms ca runs over the CA atoms)")
+    return sel
+
+
+def pca_report(name, pc):
+    """The printed summary of --pca for one output file (pc: metrics.pca's dict) -> the stats."""
+    ex = pc["explained"].cpu().numpy()
+    fl = pc["rmsf"].cpu().numpy()
+    stats = {"data_name": name, "structures": int(pc["finite"].shape[0]), "pca_non_finite": int((~pc["finite"]).sum()),
+             "pca_fit_iterations": int(pc["n_iter"]), "pca_fit_status": pc["status"], "pca_eig_iterations": int(pc["eig_iter"]),
+             "pca_eig_status": pc["eig_status"], "pca_total_variance": float(pc["total_variance"]),
+             "pca_explained_first3": [float(v) for v in ex[:3]], "rmsf_mean": float(fl.mean()), "rmsf_max": float(fl.max())}
+    print("############## vvvvvvvvv essential dynamics (mean structure, RMSF, PCA; A and A^2):")
+    print(f"fit in {stats['pca_fit_iterations']} iterations ({stats['pca_fit_status']})   total variance "
+          f"{stats['pca_total_variance']:.3f}   explained by the first three " +
+          " ".join(f"{v:.3f}" for v in stats["pca_explained_first3"]) +
+          f"   RMSF mean {stats['rmsf_mean']:.3f} max {stats['rmsf_max']:.3f}")
+    for k, v in stats.items():
+        print(k, v)
+    print("############## ^^^^^^^^^ essential dynamics")
+    return stats
 
 
 def cluster_report(name, cl):
@@ -856,6 +907,7 @@ def main(args):
     check_saxs_reweight(args)
     check_pr(args)
     check_cluster(args)
+    check_pca(args)
     check_dssp(args)
     check_sampler(args)
     saxs_data = read_saxs_data(args.saxs_data) if getattr(args, "saxs_data", None) else None
@@ -1073,6 +1125,12 @@ def main(args):
                 if not cl_sel:
                     raise SystemExit(f"--cluster: the CA atoms of {name} are not known on this input route (use --cluster_atoms all)")
             cl = metrics.cluster(xyz.reshape(-1, xyz.shape[2], 3), args.cluster, sel=cl_sel)    # members x frames: one pool
+        pc = None
+        if getattr(args, "pca", 0):
+            pc_atoms = getattr(args, "pca_atoms", "ca")
+            pc_sel = pca_selection(name, xyz.shape[2], pc_atoms, ca_indices(_TOPOLOGY[name]) if name in _TOPOLOGY else None)
+            pool = xyz.reshape(-1, xyz.shape[2], 3)                                             # members x frames: one pool
+            pc = metrics.pca(pool, n_components=min(args.pca, 3 * (len(pc_sel) if pc_sel else xyz.shape[2])), sel=pc_sel)
         sec = None
         if getattr(args, "dssp", False):
             if name not in _GEOMETRY_TOP:
@@ -1133,6 +1191,17 @@ def main(args):
                 from codlad_amd.utils.protein_module import write_pdb
                 centres = xyz.reshape(-1, xyz.shape[2], 3)[cl["centres"].to(torch.int64)].cpu().numpy()
                 write_pdb(os.path.join(save_dir, f"cluster_centres_{name}.pdb"), centres, *_TOPOLOGY[name])
+        if pc is not None:
+            np.save(os.path.join(save_dir, f"{name}_pca_mean.npy"), pc["mean"].cpu().numpy())                # float64 [m, 3]
+            np.save(os.path.join(save_dir, f"{name}_pca_eigenvalues.npy"), pc["eigenvalues"].cpu().numpy())  # float64 [K], descending
+            np.save(os.path.join(save_dir, f"{name}_pca_components.npy"), pc["components"].cpu().numpy())    # float64 [K, m, 3]
+            np.save(os.path.join(save_dir, f"{name}_pca_projections.npy"), pc["projections"].cpu().numpy())  # float64 [E * B, K]
+            np.save(os.path.join(save_dir, f"{name}_rmsf.npy"), pc["rmsf"].cpu().numpy())                    # float64 [m]
+            pca_report(name, pc)
+            if getattr(args, "save_pdb", False) and name in _TOPOLOGY and pc_sel is None:
+                from codlad_amd.utils.protein_module import write_pdb
+                write_pdb(os.path.join(save_dir, f"pca_mean_{name}.pdb"), pc["mean"].cpu().numpy()[None].astype(np.float32),
+                          *_TOPOLOGY[name])
         if sec is not None:
             np.save(os.path.join(save_dir, f"{name}_dssp.npy"), sec["ss"].cpu().numpy())                  # uint8 [E * B, R]
             np.save(os.path.join(save_dir, f"{name}_dssp_propensity.npy"), sec_prop.cpu().numpy())       # float64 [R, 8]
@@ -1289,6 +1358,17 @@ if __name__ == "__main__":
                         "largest five and the mean RMSD to the centre; saves <name>_cluster_labels.npy int32 [structures] "
                         "(-1 = a structure that is not finite), <name>_cluster_centres.npy (indices into the pool) and "
                         "<name>_cluster_sizes.npy; with --save_pdb also cluster_centres_<name>.pdb, one model per centre")
+    p.add_argument("--pca", type=int, nargs="?", const=10, default=None, metavar="K",
+                   help="essential dynamics of the written structures of every data file, members x frames as one pool, on the "
+                        "device (metrics.pca; after --relax when both are given): the mean structure after mutual superposition, "
+                        "the RMSF about it and the K (default 10, at most 64) largest principal components of the covariance of "
+                        "the superposed coordinates.  Prints the iterations of the fit, the total variance, the share the first "
+                        "three components explain and the mean and largest RMSF; saves <name>_pca_mean.npy [m, 3], "
+                        "<name>_pca_eigenvalues.npy [K], <name>_pca_components.npy [K, m, 3], <name>_pca_projections.npy "
+                        "[structures, K] and <name>_rmsf.npy [m]; with --save_pdb and --pca_atoms all also pca_mean_<name>.pdb")
+    p.add_argument("--pca_atoms", choices=("ca", "all"), default="ca",
+                   help="the atoms --pca superposes and analyses: the CA atoms (default) or every written atom (refused when "
+                        "3 x atoms > 4096)")
     p.add_argument("--cluster_atoms", choices=("ca", "all"), default="ca",
                    help="the atoms --cluster superposes and measures: the CA atoms (default) or every written atom")
     p.add_argument("--dssp", action="store_true",
