@@ -137,6 +137,7 @@ PCA_MAX_N, PCA_MAX_DIM, PCA_MAX_COMPONENTS, PCA_MAX_ITER = 65536, 4096, 64, 4096
 PCA_STATE_WORDS, PCA_ST_PHASE, PCA_ST_ITER, PCA_ST_STATUS, PCA_ST_START = 8, 0, 1, 2, 3   # CODLAD_PCA_STATE_WORDS, _ST_*
 PCA_SCALARS, PCA_SC_W, PCA_SC_STEP = 4, 0, 1           # CODLAD_PCA_SCALARS, _SC_*
 PCA_STATUS = ("converged", "limit", "no_weight")       # CODLAD_PCA_CONVERGED, _LIMIT, _NO_WEIGHT = 0 .. 2
+COMPARE_MAX_ROWS, COMPARE_MAX_BINS, DIST_HIST_MAX_SEL, DIVERGENCE_MAX_COLS = 1048576, 256, 2048, 4098   # CODLAD_COMPARE_MAX_*, ..
 REWEIGHT_STATUS = ("converged", "cap", "stalled", "failed", "none")   # CODLAD_REWEIGHT_CONVERGED .. _NONE = 0 .. 4
 ODE_NORM_WORDS = 257                                   # CODLAD_ODE_NORM_WORDS
 
@@ -188,6 +189,11 @@ _SIGS = {
     "codlad_pca_eigen_scratch_bytes": (C.c_longlong, [C.c_int] * 2),
     "codlad_pca_eigen": (C.c_int, [P, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, P, P, P, P, P, P]),
     "codlad_pca_project": (C.c_int, [P, P, C.c_int, C.c_int, C.c_int, P, P]),
+    "codlad_dist_hist_bytes": (C.c_longlong, [C.c_int] * 2),
+    "codlad_column_hist_bytes": (C.c_longlong, [C.c_int] * 2),
+    "codlad_dist_hist": (C.c_int, [P, C.c_int, C.c_int, P, C.c_int, C.c_float, C.c_int, P, P, P, P]),
+    "codlad_column_hist": (C.c_int, [P, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, P, P, P]),
+    "codlad_hist_divergence": (C.c_int, [P, P, C.c_int, C.c_int, P, P, P, P]),
     "codlad_last_error": (C.c_char_p, []),
     "codlad_struct_sizes": (None, [C.POINTER(C.c_int)]),
     "codlad_pack_block_host": (None, [P, C.c_int, C.c_float, P]),

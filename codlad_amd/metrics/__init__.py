@@ -3,8 +3,8 @@
 diversity; geometry, stereo: the reference-free checks; relax: the clash relaxation; observables: SASA, Rg, contact maps;
 dssp: secondary structure; saxs: scattering profiles; pair_distribution: typed pair-distance histograms, P(r) and the
 profiles made from them; reweight: maximum-entropy weights against data; cluster: the all-pairs RMSD matrix of a pool and
-Daura's clustering; pca: the mean structure after mutual superposition, RMSF, covariance and principal components; _inputs:
-what they share."""
+Daura's clustering; pca: the mean structure after mutual superposition, RMSF, covariance and principal components; compare: distance,
+torsion, Rg and cluster-population divergences of two ensembles; _inputs: what they share."""
 from .. import _lib   # noqa: F401
 from ._inputs import COV_CUTOFF, exclusion_csr   # noqa: F401
 from .recon import *   # noqa: F401,F403 (every public name of a module, C and torch among them as in the module this replaced)
@@ -23,3 +23,4 @@ from .pair_distribution import *   # noqa: F401,F403 (pair_distribution the func
 from .reweight import *   # noqa: F401,F403
 from .cluster import *   # noqa: F401,F403
 from .pca import *   # noqa: F401,F403 (pca the function takes the module's name here)
+from .compare import *   # noqa: F401,F403

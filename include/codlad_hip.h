@@ -1486,6 +1486,81 @@ int codlad_pca_eigen(const double *cov, int d, int k, double rtol, int max_iter,
                      double *comps, double *resid, void *scratch, void *stream);
 int codlad_pca_project(const double *D, const double *comps, int N, int d, int k, double *P, void *stream);
 
+/* Comparing two ensembles (csrc/compare_kernels.hip): integer count tables over the STRUCTURES of a pool and the
+ * divergences of two such tables.  Added to ABI version 19 without changing the number: three new entry points and two
+ * size helpers, no existing signature, struct or option changes.  Both kinds of table share one layout, int32
+ * [rows][n_bins + 2]: column 0 = "below" the first bin, columns 1 .. n_bins the bins, column n_bins + 1 = "above".
+ *
+ * codlad_dist_hist: per atom pair the histogram of its distance over the pool x [N][n_atoms][3] (device fp32, ONE
+ * topology).  sel, device int32 [n_sel], picks m = n_sel atoms (NULL with n_sel 0: all, m = n_atoms); every entry is
+ * clamped into [0, n_atoms) before it is used, so a wrong table gives wrong counts and never an access out of bounds.
+ * The rows are the P = m (m - 1) / 2 pairs (i < j) of selection POSITIONS, i ascending and j ascending within i:
+ *   p = i * m - i * (i + 1) / 2 + (j - i - 1)                    CODLAD_DIST_HIST_PAIR
+ * The decision is codlad_pair_hist's: fp32, one rounding per operation in the written order (no contraction; sqrtf is the
+ * correctly rounded one), i the atom at the lower position:
+ *   d = x_j - x_i per component, r = sqrtf((dx*dx + dy*dy) + dz*dz), t = r * inv_dr
+ *   t < (float)n_bins: column 1 + (int)t (truncation; coincident atoms fall in column 1); otherwise column n_bins + 1
+ * Column 0 is always 0 here.  finite uint8 [N]: a structure with a NaN or +-inf coordinate among its SELECTED atoms gets 0
+ * and takes no part; n_counted int32 [1] = the number of structures that take part, and every row of H sums to it.  The
+ * call writes every element of H, finite and n_counted.
+ * Accumulation: integer adds only.  A workgroup owns a tile of pairs whose histograms live in LDS (adds on int) and a
+ * chunk of the structures; its non-zero counts are added to H by integer atomics after a fill launch of the same call.
+ * Integer addition commutes: the bits repeat from call to call, do not depend on how the structures are cut into chunks
+ * (a function of N, m and n_bins alone in any case) nor on where a structure stands in the pool.  No floating-point
+ * atomics.
+ * A null pointer (sel excepted), N outside 1 .. CODLAD_COMPARE_MAX_ROWS, n_atoms < 1, sel and n_sel that disagree, m
+ * outside 2 .. CODLAD_DIST_HIST_MAX_SEL, n_bins outside 1 .. CODLAD_COMPARE_MAX_BINS, inv_dr not a positive finite number
+ * or P * (n_bins + 2) >= 2^31 returns -1 (codlad_last_error) before any launch.
+ *
+ * codlad_column_hist: per column of values [N][C] (device double, one row per structure) its histogram over the
+ * structures.  In float64, one rounding per operation: t = (v - lo) * inv_width, k = floor(t).
+ *   periodic 0: t < 0 -> column 0; k >= n_bins -> column n_bins + 1; otherwise column 1 + k.  Every finite v is counted.
+ *   periodic 1: column 1 + (k mod n_bins), the modulus taken on the integer k and made non-negative.  The admissible
+ *               values are those with |t| < 2^31 (k fits an int32); a value outside is invalid.
+ * A NaN or +-inf value is invalid in both modes; an invalid value is not counted.  H int32 [C][n_bins + 2]; n_valid int32
+ * [C] = the values counted, the sum of the row.  The call writes every element.  Integer adds only, as above.
+ * A null pointer, N or C outside 1 .. CODLAD_COMPARE_MAX_ROWS, n_bins outside 1 .. CODLAD_COMPARE_MAX_BINS, lo not finite,
+ * inv_width not a positive finite number or periodic outside {0, 1} returns -1 before any launch.
+ *
+ * codlad_hist_divergence: HA, HB int32 [rows][cols] -> js, tv, w1 double [rows].  Per row, in float64, one rounding per
+ * operation, k ascending, every sum added to 0 in that order (a = HA[r][k], b = HB[r][k]):
+ *   nA = sum a, nB = sum b as int64;  p_k = (double)a / (double)nA, q_k = (double)b / (double)nB, m_k = 0.5 * (p_k + q_k)
+ *   js = 0.5 * sum_k (tp + tq), tp = p_k * log2(p_k / m_k) if a > 0 else 0, tq likewise with q    (bits; 0 .. 1)
+ *   tv = 0.5 * sum_k |p_k - q_k|
+ *   w1 = sum_{k < cols - 1} |cA_k - cB_k|, cA_k = p_0 + .. + p_k added in this order, in units of one column
+ * A row with nA = 0 or nB = 0, or with a negative count, gives NaN in all three.  Equal proportions give p_k == q_k ==
+ * m_k to the bit (a correctly rounded quotient of equal ratios), p / m = 1 and log2(1) = 0: js = tv = w1 = 0 exactly,
+ * whatever nA and nB are.  Every operation that mixes A and B commutes, so swapping HA and HB returns the same bits.  One
+ * wave per row: the lanes compute the terms of 64 columns, one lane adds them in ascending k.  No atomics.
+ * Bounds against the exact value, first order, with e = 2^-52 and log2 within 1 unit in the last place (what the
+ * device's float64 log2 documents): the ratio p / m carries four roundings, so log2 is off by at most 4 e / ln 2 + e
+ * |log2|, a term p log2(p / m) by at most e p (6 + 3 |log2(p / m)|) with p |log2(p / m)| <= 1 / (e_euler ln 2) < 0.54, and a
+ * running sum of cols terms whose magnitudes add up to at most 4 by cols * 4 e:
+ *   |js - exact| <= (4 cols + 8) 2^-52        CODLAD_DIVERGENCE_JS_BOUND
+ *   |tv - exact| <= (cols + 2) 2^-52          (p - q within e (p + q) + e |p - q|, cols additions of partial sums <= 2)
+ *   |w1 - exact| <= (2 cols^2 + 2 cols) 2^-52 (cA_k within (k + 1) e; cols additions of partial sums <= cols)
+ * A null pointer, cols outside 2 .. CODLAD_DIVERGENCE_MAX_COLS or rows outside 1 .. (2^31 - 1) / cols returns -1 before
+ * the launch.
+ *
+ * The kernels need no scratch memory; the two helpers return the bytes of the table H a caller allocates, 4 * P *
+ * (n_bins + 2) and 4 * C * (n_bins + 2), or -1 (codlad_last_error) for sizes the entry points refuse. */
+#define CODLAD_COMPARE_MAX_ROWS 1048576
+#define CODLAD_COMPARE_MAX_BINS 256
+#define CODLAD_DIST_HIST_MAX_SEL 2048
+#define CODLAD_DIVERGENCE_MAX_COLS 4098
+#define CODLAD_DIST_HIST_PAIR(i, j, m) ((i) * (m) - (i) * ((i) + 1) / 2 + ((j) - (i) - 1))
+#define CODLAD_DIVERGENCE_JS_BOUND(cols) ((4.0 * (cols) + 8.0) * 2.220446049250313e-16)
+#define CODLAD_DIVERGENCE_TV_BOUND(cols) (((cols) + 2.0) * 2.220446049250313e-16)
+#define CODLAD_DIVERGENCE_W1_BOUND(cols) ((2.0 * (cols) * (cols) + 2.0 * (cols)) * 2.220446049250313e-16)
+long long codlad_dist_hist_bytes(int m, int n_bins);
+long long codlad_column_hist_bytes(int C, int n_bins);
+int codlad_dist_hist(const float *x, int N, int n_atoms, const int32_t *sel, int n_sel, float inv_dr, int n_bins, int32_t *H,
+                     uint8_t *finite, int32_t *n_counted, void *stream);
+int codlad_column_hist(const double *values, int N, int C, double lo, double inv_width, int n_bins, int periodic, int32_t *H,
+                       int32_t *n_valid, void *stream);
+int codlad_hist_divergence(const int32_t *HA, const int32_t *HB, int rows, int cols, double *js, double *tv, double *w1,
+                           void *stream);
+
 #ifdef __cplusplus
 }
 #endif

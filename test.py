@@ -58,6 +58,10 @@ CUTOFF in A over the CA atoms (`--cluster_atoms all`: every atom).
 `--pca [K]` (default 10) describes how the written structures of every data file move (metrics.pca): the mean structure
 after mutual superposition, the RMSF and the K largest principal components of the covariance, over the CA atoms
 (`--pca_atoms all`: every written atom, while 3 x atoms <= 4096).
+`--compare [N_BINS]` (default 50) compares the written structures of every data file, as one ensemble, with the file's
+true frames (metrics.ensemble_compare): Jensen-Shannon divergences of every CA-CA distance distribution, of Rg and, when
+the topology is known and no atom is masked, of the backbone and side-chain torsions; `--compare_cluster CUTOFF` adds
+the cluster-population similarity (ENCORE's CES).
 Addition: `--pr [DR]` (opt-in, wherever --observables is allowed; after --relax when both are given) computes the pair
 distribution P(r) of every written structure on the device (metrics.pair_distribution: the typed pair-distance histogram
 in bins of DR A, default 0.5, weighted with the forward amplitudes) and prints D_max, the real-space Rg and the number of
@@ -337,6 +341,67 @@ def check_pca(args):
     return k
 
 
+def check_compare(args):
+    """--compare [N_BINS]: the number of distance bins, 1 .. 256; it compares generated structures with the true frames.
+    --compare_cluster CUTOFF (only with --compare): a positive finite RMSD in A.  Returns N_BINS, 0 = off."""
+    k = getattr(args, "compare", None)
+    c = getattr(args, "compare_cluster", None)
+    if c is not None and not (np.isfinite(c) and c > 0):
+        raise SystemExit(f"--compare_cluster takes an RMSD cut-off in A, a positive number, got {c}")
+    if k is None:
+        if c is not None:
+            raise SystemExit("--compare_cluster needs --compare")
+        args.compare = 0
+        return 0
+    if not 1 <= k <= metrics.COMPARE_MAX_BINS:
+        raise SystemExit(f"--compare takes the number of distance bins, 1 .. {metrics.COMPARE_MAX_BINS}, got {k}")
+    if getattr(args, "experiment", "latent") in ("bpd", "fmloss"):
+        raise SystemExit(f"--compare compares generated structures with the true ones: --experiment {args.experiment} generates none")
+    return k
+
+
+def compare_truth(name, batch):
+    """The true coordinates --compare measures against: batch["nxyz"][:, 1:], [frames * n_atoms, 3]; SystemExit when the
+    input route has none (--cg_pdb)."""
+    if "nxyz" not in batch:
+        raise SystemExit(f"--compare: {name} has no true frames to compare with (nxyz; a CA-only input such as --cg_pdb has none)")
+    return batch["nxyz"][:, 1:]
+
+
+def compare_no_atom_masked(batch):
+    """True when mask_xyz_list (a boolean mask or an index list over the atoms) masks nothing: the torsions of the true frames
+    are then those of real atoms."""
+    m = batch.get("mask_xyz_list")
+    if m is None:
+        return True
+    m = torch.as_tensor(m)
+    return not bool(m.any()) if m.dtype == torch.bool else m.numel() == 0
+
+
+def compare_report(name, cmp):
+    """The printed summary of --compare for one output file (cmp: metrics.ensemble_compare's dict) -> the stats."""
+    stats = {"data_name": name, "compare_generated": cmp["n_a"], "compare_true": cmp["n_b"], "compare_r_max": cmp["r_max"],
+             "compare_js_dist_mean": float(cmp["js_dist_mean"]), "compare_js_dist_median": float(cmp["js_dist_median"]),
+             "compare_js_rg": float(cmp["js_rg"]), "compare_w1_rg": float(cmp["w1_rg"])}
+    line = (f"compare {name}: distance JS mean {stats['compare_js_dist_mean']:.4f} median {stats['compare_js_dist_median']:.4f}   "
+            f"Rg JS {stats['compare_js_rg']:.4f} W1 {stats['compare_w1_rg']:.3f} A")
+    if "js_torsion_mean" in cmp:
+        per = [float(v) for v in cmp["js_torsion_mean"].cpu()]
+        stats.update({f"compare_js_{n}": v for n, v in zip(metrics.TORSION_NAMES, per)})
+        line += "   torsion JS " + " ".join(f"{n} {v:.4f}" for n, v in zip(metrics.TORSION_NAMES, per))
+    else:
+        line += "   torsions skipped (the topology is not known, or the batch masks atoms)"
+    if "js_cluster" in cmp:
+        stats.update(compare_js_cluster=float(cmp["js_cluster"]), compare_clusters=cmp["n_clusters"])
+        line += f"   cluster JS {stats['compare_js_cluster']:.4f} ({cmp['n_clusters']} clusters)"
+    print("############## vvvvvvvvv generated against true ensemble (Jensen-Shannon divergences in bits, 0 = same distribution):")
+    print(line)
+    for k, v in stats.items():
+        print(k, v)
+    print("############## ^^^^^^^^^ generated against true ensemble")
+    return stats
+
+
 def pca_selection(name, n_atoms, atoms, ca):
     """The atoms --pca runs over for one output file: the CA indices `ca` (atoms "ca") or None for all -> sel; SystemExit
     when they are not known or hold more coordinates than one covariance takes."""
@@ -587,7 +652,7 @@ def iter_batches(args):
             geom_top = None
             if getattr(args, "geometry_check", False) or getattr(args, "stereo_check", False) or getattr(args, "relax", 0) \
                     or getattr(args, "observables", 0) or getattr(args, "dssp", False) or getattr(args, "saxs", 0) \
-                    or getattr(args, "pr", 0):
+                    or getattr(args, "pr", 0) or getattr(args, "compare", 0):
                 from codlad_amd.utils.cg_input import template_topology
                 geom_top = template_topology(names[1:-1])             # one Topology (and one set of device tables) per protein
             for c, (a, b) in enumerate(plan):
@@ -596,8 +661,10 @@ def iter_batches(args):
                 if geom_top is not None:
                     _GEOMETRY_TOP[out] = geom_top
                 batch = synth.make_batch(prot, range(a, b))
-                # the encoder reads the all-atom side of the batch (recon; the known latents of --fix_residues)
-                if getattr(args, "experiment", "latent") in ("recon", "bpd", "fmloss") or getattr(args, "fix_residues", None) is not None:
+                # the encoder reads the all-atom side of the batch (recon; the known latents of --fix_residues); --compare its
+                # true coordinates
+                if getattr(args, "experiment", "latent") in ("recon", "bpd", "fmloss") or getattr(args, "fix_residues", None) is not None \
+                        or getattr(args, "compare", 0):
                     batch.update(synth.make_atoms(prot, range(a, b), seed=1000 + i))
                 yield out, batch, prot["info"]
         return
@@ -908,6 +975,7 @@ def main(args):
     check_pr(args)
     check_cluster(args)
     check_pca(args)
+    check_compare(args)
     check_dssp(args)
     check_sampler(args)
     saxs_data = read_saxs_data(args.saxs_data) if getattr(args, "saxs_data", None) else None
@@ -1131,6 +1199,15 @@ def main(args):
             pc_sel = pca_selection(name, xyz.shape[2], pc_atoms, ca_indices(_TOPOLOGY[name]) if name in _TOPOLOGY else None)
             pool = xyz.reshape(-1, xyz.shape[2], 3)                                             # members x frames: one pool
             pc = metrics.pca(pool, n_components=min(args.pca, 3 * (len(pc_sel) if pc_sel else xyz.shape[2])), sel=pc_sel)
+        cmp = None
+        if getattr(args, "compare", 0):
+            truth = compare_truth(name, batch).reshape(-1, xyz.shape[2], 3)
+            cmp_sel = ca_indices(_TOPOLOGY[name]) if name in _TOPOLOGY else None
+            if not cmp_sel or len(cmp_sel) < 2:
+                raise SystemExit(f"--compare: the CA atoms of {name} are not known on this input route")
+            cmp_top = _GEOMETRY_TOP[name] if name in _GEOMETRY_TOP and compare_no_atom_masked(batch) else None
+            cmp = metrics.ensemble_compare(xyz.reshape(-1, xyz.shape[2], 3), truth, top=cmp_top, sel=cmp_sel, n_bins=args.compare,
+                                           cluster_cutoff=getattr(args, "compare_cluster", None))   # members x frames: one pool
         sec = None
         if getattr(args, "dssp", False):
             if name not in _GEOMETRY_TOP:
@@ -1202,6 +1279,11 @@ def main(args):
                 from codlad_amd.utils.protein_module import write_pdb
                 write_pdb(os.path.join(save_dir, f"pca_mean_{name}.pdb"), pc["mean"].cpu().numpy()[None].astype(np.float32),
                           *_TOPOLOGY[name])
+        if cmp is not None:
+            np.save(os.path.join(save_dir, f"{name}_compare_js_dist.npy"), cmp["js_dist"].cpu().numpy())          # float64 [R, R]
+            if "js_torsion" in cmp:
+                np.save(os.path.join(save_dir, f"{name}_compare_js_torsion.npy"), cmp["js_torsion"].cpu().numpy())  # float64 [R, 7]
+            compare_report(name, cmp)
         if sec is not None:
             np.save(os.path.join(save_dir, f"{name}_dssp.npy"), sec["ss"].cpu().numpy())                  # uint8 [E * B, R]
             np.save(os.path.join(save_dir, f"{name}_dssp_propensity.npy"), sec_prop.cpu().numpy())       # float64 [R, 8]
@@ -1366,6 +1448,15 @@ if __name__ == "__main__":
                         "three components explain and the mean and largest RMSF; saves <name>_pca_mean.npy [m, 3], "
                         "<name>_pca_eigenvalues.npy [K], <name>_pca_components.npy [K, m, 3], <name>_pca_projections.npy "
                         "[structures, K] and <name>_rmsf.npy [m]; with --save_pdb and --pca_atoms all also pca_mean_<name>.pdb")
+    p.add_argument("--compare", type=int, nargs="?", const=50, default=None, metavar="N_BINS",
+                   help="compare the written structures of every data file, members x frames as one ensemble, with the file's "
+                        "true frames on the device (metrics.ensemble_compare; after --relax when both are given): the "
+                        "Jensen-Shannon divergence of every CA-CA distance distribution on N_BINS bins (default 50), of Rg and, "
+                        "when the topology is known and no atom is masked, of phi, psi, omega and chi1-4 per residue.  Prints one "
+                        "line; saves <name>_compare_js_dist.npy [R, R] and <name>_compare_js_torsion.npy [R, 7]")
+    p.add_argument("--compare_cluster", type=float, default=None, metavar="CUTOFF",
+                   help="with --compare: cluster generated and true structures as one pool at the RMSD CUTOFF in A (CA atoms) and "
+                        "print the Jensen-Shannon divergence of the two cluster populations (ENCORE's CES)")
     p.add_argument("--pca_atoms", choices=("ca", "all"), default="ca",
                    help="the atoms --pca superposes and analyses: the CA atoms (default) or every written atom (refused when "
                         "3 x atoms > 4096)")
