@@ -138,6 +138,7 @@ PCA_STATE_WORDS, PCA_ST_PHASE, PCA_ST_ITER, PCA_ST_STATUS, PCA_ST_START = 8, 0, 
 PCA_SCALARS, PCA_SC_W, PCA_SC_STEP = 4, 0, 1           # CODLAD_PCA_SCALARS, _SC_*
 PCA_STATUS = ("converged", "limit", "no_weight")       # CODLAD_PCA_CONVERGED, _LIMIT, _NO_WEIGHT = 0 .. 2
 COMPARE_MAX_ROWS, COMPARE_MAX_BINS, DIST_HIST_MAX_SEL, DIVERGENCE_MAX_COLS = 1048576, 256, 2048, 4098   # CODLAD_COMPARE_MAX_*, ..
+LDDT_MAX_THRESHOLDS, LDDT_MAX_ATOMS = 8, 46340         # CODLAD_LDDT_MAX_THRESHOLDS, _MAX_ATOMS
 REWEIGHT_STATUS = ("converged", "cap", "stalled", "failed", "none")   # CODLAD_REWEIGHT_CONVERGED .. _NONE = 0 .. 4
 ODE_NORM_WORDS = 257                                   # CODLAD_ODE_NORM_WORDS
 
@@ -194,6 +195,8 @@ _SIGS = {
     "codlad_dist_hist": (C.c_int, [P, C.c_int, C.c_int, P, C.c_int, C.c_float, C.c_int, P, P, P, P]),
     "codlad_column_hist": (C.c_int, [P, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, P, P, P]),
     "codlad_hist_divergence": (C.c_int, [P, P, C.c_int, C.c_int, P, P, P, P]),
+    "codlad_lddt": (C.c_int, [P, C.c_int, P, C.c_int, P, C.c_int, P, C.c_int, P, C.c_int, P, P, P, P, C.c_int, C.c_float, P, C.c_int,
+                              C.c_int] + [P] * 11),
     "codlad_last_error": (C.c_char_p, []),
     "codlad_struct_sizes": (None, [C.POINTER(C.c_int)]),
     "codlad_pack_block_host": (None, [P, C.c_int, C.c_float, P]),

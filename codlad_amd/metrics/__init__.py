@@ -4,7 +4,8 @@ diversity; geometry, stereo: the reference-free checks; relax: the clash relaxat
 dssp: secondary structure; saxs: scattering profiles; pair_distribution: typed pair-distance histograms, P(r) and the
 profiles made from them; reweight: maximum-entropy weights against data; cluster: the all-pairs RMSD matrix of a pool and
 Daura's clustering; pca: the mean structure after mutual superposition, RMSF, covariance and principal components; compare: distance,
-torsion, Rg and cluster-population divergences of two ensembles; _inputs: what they share."""
+torsion, Rg and cluster-population divergences of two ensembles; lddt: the local distance difference test against the true
+frames; _inputs: what they share."""
 from .. import _lib   # noqa: F401
 from ._inputs import COV_CUTOFF, exclusion_csr   # noqa: F401
 from .recon import *   # noqa: F401,F403 (every public name of a module, C and torch among them as in the module this replaced)
@@ -24,3 +25,4 @@ from .reweight import *   # noqa: F401,F403
 from .cluster import *   # noqa: F401,F403
 from .pca import *   # noqa: F401,F403 (pca the function takes the module's name here)
 from .compare import *   # noqa: F401,F403
+from .lddt import *   # noqa: F401,F403 (lddt the function takes the module's name here)

@@ -1561,6 +1561,65 @@ int codlad_column_hist(const double *values, int N, int C, double lo, double inv
 int codlad_hist_divergence(const int32_t *HA, const int32_t *HB, int rows, int cols, double *js, double *tv, double *w1,
                            void *stream);
 
+/* lDDT, the local distance difference test (Mariani et al. 2013), of generated structures against the true frames their CA
+ * traces came from (csrc/lddt_kernels.hip): superposition-free, all-atom, per atom, per residue and per structure.  Added
+ * to ABI version 19 without changing the number: one new entry point, no existing signature, struct or option changes.
+ *
+ * xyz [n_struct][n_atoms][3] models and ref [n_ref][n_atoms][3] reference frames (device fp32, ONE topology); ref_index
+ * int32 [n_struct] (device): model s is scored against frame ref_index[s].  sel, device int32 [n_sel], picks the m = n_sel
+ * atoms that take part (NULL with n_sel 0: all, m = n_atoms); an atom that is not selected is never read.  Everything
+ * below is indexed by the POSITION p of an atom in the selection:
+ *   res      int32 [m]         the residue of position p, in [0, n_res)
+ *   res_ptr  int32 [n_res + 1], res_pos int32 [m]: the positions of residue r are res_pos[res_ptr[r] .. res_ptr[r + 1] - 1]
+ *   partner  int32 [m]         the position that p exchanges coordinates with when its residue is swapped (a symmetric
+ *                              side chain: ASP OD1/OD2, PHE CD1/CD2 with CE1/CE2, ..); p itself for every other atom.  An
+ *                              involution within a residue.  moved int32 [n_moved]: the positions with partner[p] != p, all
+ *                              of them, each once.  n_moved 0 (partner, moved, scratch may be NULL): no symmetry.
+ * ref_index, sel, res, res_ptr, res_pos, partner and moved are checked on the HOST by the Python layer (metrics.lddt_lists),
+ * not here; every entry is clamped into its range before it is used, so a wrong table gives wrong counts and never an
+ * access out of bounds.  thresholds is a HOST array of n_thresholds floats, read before the call returns.
+ *
+ * In unfused fp32, one rounding per operation (sqrtf the correctly rounded one), for every ordered pair of positions
+ * i != j with |res[i] - res[j]| >= seq_sep (chains are not treated specially):
+ *   d_ref = sqrtf((dx*dx + dy*dy) + dz*dz), dx = x_i - x_j on the reference frame    (codlad_geometry_check's distance)
+ *   the pair is INCLUDED iff d_ref < cutoff          (the kernel compares the squared distance with the smallest float whose
+ *                                                     root is >= cutoff: the same decision for every input, see the source)
+ *   d_mod   the same sequence on the model;  the pair is PRESERVED at k iff fabsf(d_mod - d_ref) < thresholds[k]
+ * Both inequalities are strict.  Per structure s:
+ *   atom_total     int32 [S][m]        the included partners j of position i
+ *   atom_preserved int32 [S][m][T]     of those, the ones preserved at k
+ *   residue_total  int32 [S][n_res], residue_preserved int32 [S][n_res][T]: their sums over the positions of a residue
+ *                  (n_atoms <= CODLAD_LDDT_MAX_ATOMS = 46340 = floor(sqrt(2^31)) keeps m (m - 1), the largest possible sum, below 2^31)
+ *   counts         int64 [S][1 + T]    total, then preserved at each k, summed over all positions
+ *   residue_score  double [S][n_res] = sum_k residue_preserved / (T * residue_total): int64 sums, ONE correctly rounded
+ *                  float64 division; NaN where residue_total is 0.  score double [S]: the same from counts.
+ * Symmetry (n_moved > 0), decided per (structure, residue) independently of every other residue: the residue is scored
+ * with the MODEL coordinates of its positions read through `partner` while every other position keeps its own; it is
+ * swapped iff that makes the sum of its atom_preserved over positions and k STRICTLY greater (a tie keeps the naming).
+ * A pair never lies within one residue, so only the moved positions of a residue can change its sum, and the decision is
+ * taken on their sums alone.  swapped uint8 [S][n_res]; the reported counts are those of a final pass in which every
+ * model coordinate is read through the chosen swaps.  Totals never depend on the model, nor on the swaps.
+ * finite uint8 [S]: 0 when a selected coordinate of the model or of ITS reference frame is NaN or +-inf; then every
+ * count of the structure is -1, every score NaN and swapped 0.  Every other structure keeps its bits.
+ * scratch: int64 [S][n_res][2] (device), needed when n_moved > 0: the two sums of every residue's decision, zeroed by
+ * the call.  The call writes every element of every output.
+ * The reported counts have one writer each and are summed in index order or in a fixed integer tree; only the decision
+ * sums are integer atomics, on the table the call zeroes.  Integer addition commutes and nothing floating-point is ever
+ * accumulated: results repeat from call to call and a structure's rows do not depend on the other structures of the
+ * call.  Everything runs on `stream`; no host synchronisation.
+ * A null pointer, n_struct, n_ref, n_atoms or n_res < 1, n_atoms > CODLAD_LDDT_MAX_ATOMS, sel and n_sel that disagree,
+ * n_thresholds outside 1 .. CODLAD_LDDT_MAX_THRESHOLDS, a cutoff or threshold that is not a positive finite number,
+ * seq_sep < 1, or 2^31 workgroups or more (n_struct * ceil(m / 128); for the decision n_struct * ceil(n_moved / 128) *
+ * ceil(m / 512) * 2) returns -1 (codlad_last_error) before any launch. */
+#define CODLAD_LDDT_MAX_THRESHOLDS 8
+#define CODLAD_LDDT_MAX_ATOMS 46340
+int codlad_lddt(const float *xyz, int n_struct, const float *ref, int n_ref, const int32_t *ref_index, int n_atoms,
+                const int32_t *sel, int n_sel, const int32_t *res, int n_res, const int32_t *res_ptr, const int32_t *res_pos,
+                const int32_t *partner, const int32_t *moved, int n_moved, float cutoff, const float *thresholds,
+                int n_thresholds, int seq_sep, int32_t *atom_total, int32_t *atom_preserved, int32_t *residue_total,
+                int32_t *residue_preserved, double *residue_score, long long *counts, double *score, uint8_t *swapped,
+                uint8_t *finite, long long *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,6 +62,9 @@ after mutual superposition, the RMSF and the K largest principal components of t
 true frames (metrics.ensemble_compare): Jensen-Shannon divergences of every CA-CA distance distribution, of Rg and, when
 the topology is known and no atom is masked, of the backbone and side-chain torsions; `--compare_cluster CUTOFF` adds
 the cluster-population similarity (ENCORE's CES).
+`--lddt` (wherever --compare applies) scores every written structure against the true frame its CA trace came from
+(metrics.lddt): the local distance difference test per structure and per residue, superposition-free, with symmetric side
+chains in the better naming; masked atoms take no part.
 Addition: `--pr [DR]` (opt-in, wherever --observables is allowed; after --relax when both are given) computes the pair
 distribution P(r) of every written structure on the device (metrics.pair_distribution: the typed pair-distance histogram
 in bins of DR A, default 0.5, weighted with the forward amplitudes) and prints D_max, the real-space Rg and the number of
@@ -360,11 +363,11 @@ def check_compare(args):
     return k
 
 
-def compare_truth(name, batch):
-    """The true coordinates --compare measures against: batch["nxyz"][:, 1:], [frames * n_atoms, 3]; SystemExit when the
-    input route has none (--cg_pdb)."""
+def compare_truth(name, batch, flag="--compare"):
+    """The true coordinates --compare and --lddt measure against: batch["nxyz"][:, 1:], [frames * n_atoms, 3]; SystemExit when
+    the input route has none (--cg_pdb)."""
     if "nxyz" not in batch:
-        raise SystemExit(f"--compare: {name} has no true frames to compare with (nxyz; a CA-only input such as --cg_pdb has none)")
+        raise SystemExit(f"{flag}: {name} has no true frames to compare with (nxyz; a CA-only input such as --cg_pdb has none)")
     return batch["nxyz"][:, 1:]
 
 
@@ -376,6 +379,42 @@ def compare_no_atom_masked(batch):
         return True
     m = torch.as_tensor(m)
     return not bool(m.any()) if m.dtype == torch.bool else m.numel() == 0
+
+
+def check_lddt(args):
+    """--lddt scores generated structures against the true frames."""
+    if getattr(args, "lddt", False) and getattr(args, "experiment", "latent") in ("bpd", "fmloss"):
+        raise SystemExit(f"--lddt scores generated structures against the true ones: --experiment {args.experiment} generates none")
+
+
+def lddt_selection(batch, n_frames, n_atoms):
+    """The atoms --lddt scores: those mask_xyz_list (a boolean mask or an index list over frames * n_atoms) masks in no frame,
+    as an index list; None when nothing is masked."""
+    m = batch.get("mask_xyz_list")
+    if m is None:
+        return None
+    m = torch.as_tensor(m).cpu()
+    masked = torch.zeros(n_frames * n_atoms, dtype=torch.bool)
+    masked[m.reshape(-1) if m.dtype == torch.bool else m.reshape(-1).long()] = True
+    masked = masked.reshape(n_frames, n_atoms).any(0)
+    return None if not bool(masked.any()) else torch.nonzero(~masked).reshape(-1).tolist()
+
+
+def lddt_report(name, ld):
+    """The printed summary of --lddt for one output file (ld: metrics.lddt's dict) -> the stats."""
+    g, res = ld["global"].cpu().numpy(), ld["residue"].cpu().numpy()
+    scored = res[~np.isnan(res)]
+    stats = {"data_name": name, "lddt_mean": float(np.nanmean(g)), "lddt_median": float(np.nanmedian(g)), "lddt_min": float(np.nanmin(g)),
+             "lddt_residues_below_0.7": float((scored < 0.7).mean()) if scored.size else float("nan"),
+             "lddt_swapped_residues": int(ld["swapped"].sum()), "lddt_not_finite": int((~ld["finite"]).sum())}
+    print("############## vvvvvvvvv lDDT of the generated structures against their true frames (1 = every local distance kept):")
+    print(f"lddt {name}: global mean {stats['lddt_mean']:.4f} median {stats['lddt_median']:.4f} min {stats['lddt_min']:.4f}   "
+          f"residues below 0.7: {100.0 * stats['lddt_residues_below_0.7']:.1f} %   swapped symmetric residues: "
+          f"{stats['lddt_swapped_residues']}")
+    for k, v in stats.items():
+        print(k, v)
+    print("############## ^^^^^^^^^ lDDT")
+    return stats
 
 
 def compare_report(name, cmp):
@@ -652,7 +691,7 @@ def iter_batches(args):
             geom_top = None
             if getattr(args, "geometry_check", False) or getattr(args, "stereo_check", False) or getattr(args, "relax", 0) \
                     or getattr(args, "observables", 0) or getattr(args, "dssp", False) or getattr(args, "saxs", 0) \
-                    or getattr(args, "pr", 0) or getattr(args, "compare", 0):
+                    or getattr(args, "pr", 0) or getattr(args, "compare", 0) or getattr(args, "lddt", False):
                 from codlad_amd.utils.cg_input import template_topology
                 geom_top = template_topology(names[1:-1])             # one Topology (and one set of device tables) per protein
             for c, (a, b) in enumerate(plan):
@@ -661,10 +700,10 @@ def iter_batches(args):
                 if geom_top is not None:
                     _GEOMETRY_TOP[out] = geom_top
                 batch = synth.make_batch(prot, range(a, b))
-                # the encoder reads the all-atom side of the batch (recon; the known latents of --fix_residues); --compare its
-                # true coordinates
+                # the encoder reads the all-atom side of the batch (recon; the known latents of --fix_residues); --compare and
+                # --lddt its true coordinates
                 if getattr(args, "experiment", "latent") in ("recon", "bpd", "fmloss") or getattr(args, "fix_residues", None) is not None \
-                        or getattr(args, "compare", 0):
+                        or getattr(args, "compare", 0) or getattr(args, "lddt", False):
                     batch.update(synth.make_atoms(prot, range(a, b), seed=1000 + i))
                 yield out, batch, prot["info"]
         return
@@ -976,6 +1015,7 @@ def main(args):
     check_cluster(args)
     check_pca(args)
     check_compare(args)
+    check_lddt(args)
     check_dssp(args)
     check_sampler(args)
     saxs_data = read_saxs_data(args.saxs_data) if getattr(args, "saxs_data", None) else None
@@ -1208,6 +1248,15 @@ def main(args):
             cmp_top = _GEOMETRY_TOP[name] if name in _GEOMETRY_TOP and compare_no_atom_masked(batch) else None
             cmp = metrics.ensemble_compare(xyz.reshape(-1, xyz.shape[2], 3), truth, top=cmp_top, sel=cmp_sel, n_bins=args.compare,
                                            cluster_cutoff=getattr(args, "compare_cluster", None))   # members x frames: one pool
+        ld = None
+        if getattr(args, "lddt", False):
+            if name not in _GEOMETRY_TOP:
+                raise SystemExit(f"--lddt: the topology of {name} is not known on this input route")
+            truth = compare_truth(name, batch, "--lddt").reshape(-1, xyz.shape[2], 3)
+            # member k of frame f against true frame f; atoms the batch masks in a frame take no part
+            ld = metrics.lddt(xyz.reshape(-1, xyz.shape[2], 3), truth, _GEOMETRY_TOP[name],
+                              ref_index=torch.arange(truth.shape[0]).repeat(xyz.shape[0]),
+                              sel=lddt_selection(batch, truth.shape[0], xyz.shape[2]))
         sec = None
         if getattr(args, "dssp", False):
             if name not in _GEOMETRY_TOP:
@@ -1284,6 +1333,10 @@ def main(args):
             if "js_torsion" in cmp:
                 np.save(os.path.join(save_dir, f"{name}_compare_js_torsion.npy"), cmp["js_torsion"].cpu().numpy())  # float64 [R, 7]
             compare_report(name, cmp)
+        if ld is not None:
+            np.save(os.path.join(save_dir, f"{name}_lddt.npy"), ld["global"].cpu().numpy())              # float64 [E * B]
+            np.save(os.path.join(save_dir, f"{name}_lddt_residue.npy"), ld["residue"].cpu().numpy())     # float64 [E * B, R]
+            lddt_report(name, ld)
         if sec is not None:
             np.save(os.path.join(save_dir, f"{name}_dssp.npy"), sec["ss"].cpu().numpy())                  # uint8 [E * B, R]
             np.save(os.path.join(save_dir, f"{name}_dssp_propensity.npy"), sec_prop.cpu().numpy())       # float64 [R, 8]
@@ -1457,6 +1510,12 @@ if __name__ == "__main__":
     p.add_argument("--compare_cluster", type=float, default=None, metavar="CUTOFF",
                    help="with --compare: cluster generated and true structures as one pool at the RMSD CUTOFF in A (CA atoms) and "
                         "print the Jensen-Shannon divergence of the two cluster populations (ENCORE's CES)")
+    p.add_argument("--lddt", action="store_true",
+                   help="score the written structures of every data file against the file's true frames on the device "
+                        "(metrics.lddt; after --relax when both are given): member k of frame f against true frame f, all "
+                        "atoms the batch does not mask, symmetric side chains in the better naming; prints the mean / median / "
+                        "minimum global lDDT, the share of residues below 0.7 and the number of swapped residues; saves "
+                        "<name>_lddt.npy [structures] and <name>_lddt_residue.npy [structures, R]")
     p.add_argument("--pca_atoms", choices=("ca", "all"), default="ca",
                    help="the atoms --pca superposes and analyses: the CA atoms (default) or every written atom (refused when "
                         "3 x atoms > 4096)")
