@@ -43,11 +43,10 @@
 // The diagonal bit is taken as set and bits at j >= N are masked here, whatever the bitmap holds.
 #include "common.h"
 #include "ensemble_math.h"
-#include "../../include/codlad_hip.h"
+#include "host_util.h"
+#include "reduce_math.h"
 
 namespace {
-typedef double double4_t __attribute__((ext_vector_type(4)));
-
 constexpr int MAX_N = CODLAD_CLUSTER_MAX_N;
 constexpr int BLK = 64;                     // conformations of a block = bits of a word
 constexpr int OP_ATOMS = 16;                // operand kernel: atoms of a workgroup
@@ -58,9 +57,6 @@ constexpr int MT = NW * 64;
 constexpr int PANEL = KC * 3 * BLK;         // doubles of a chunk of one block
 constexpr int LOADS = 2 * PANEL / MT;       // per thread and chunk
 static_assert(2 * PANEL % MT == 0 && NW * TJ == 16, "the chunk is spread evenly; 16 wave tiles");
-
-__device__ inline double nan64() { return __longlong_as_double(0x7ff8000000000000ll); }
-__device__ inline bool fin64(double x) { return fabs(x) < __longlong_as_double(0x7ff0000000000000ll); }
 
 // grid (N_pad / 64, ceil(n_pad / 16)): 64 conformations x 16 atoms through LDS, read along the atoms, written along the
 // conformations
@@ -244,21 +240,6 @@ __device__ inline unsigned long long word_mask(int N, int w) {          // the b
     const int left = N - w * 64;
     return left >= 64 ? ~0ull : left <= 0 ? 0ull : (1ull << left) - 1ull;
 }
-__device__ inline int wave_sum_int(int v) {
-#pragma unroll
-    for (int st = 32; st > 0; st >>= 1) v += __shfl_xor(v, st);
-    return v;
-}
-// the workgroup's sum of one int per thread; every thread gets it
-__device__ inline int block_sum_int(int v, int *red) {
-    v = wave_sum_int(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int s = 0;
-    for (int k = 0; k < CT / 64; ++k) s += red[k];
-    return s;
-}
 
 __global__ __launch_bounds__(CT) void init_kernel(Cl c) {
     if (c.state[CODLAD_CLUSTER_ST_PHASE] != PH_NEW) return;
@@ -275,7 +256,7 @@ __global__ __launch_bounds__(CT) void init_kernel(Cl c) {
         n = __popcll(a);
     }
     for (int i = t; i < c.N; i += CT) c.labels[i] = -1;
-    n = block_sum_int(n, red);
+    n = block_sum(n, red);
     if (t == 0) {
         c.state[CODLAD_CLUSTER_ST_ACTIVE] = n;
         c.state[CODLAD_CLUSTER_ST_CLUSTERS] = 0;
@@ -311,7 +292,7 @@ template <int MODE> __global__ __launch_bounds__(256) void count_kernel(Cl c) {
             if (w == (i >> 6)) r |= 1ull << (i & 63);
             n += __popcll(r & s);
         }
-        n = wave_sum_int(n);
+        n = wave_sum(n);
         if (lane == 0) c.count[i] = MODE == 0 ? n : c.count[i] - n;
     }
 }
@@ -378,7 +359,7 @@ __global__ __launch_bounds__(CT) void pick_kernel(Cl c) {
         c.active[t] = a & ~r;
         for (unsigned long long m = r; m; m &= m - 1) c.labels[t * 64 + __ffsll((long long)m) - 1] = K;
     }
-    const int size = block_sum_int(__popcll(r), red);
+    const int size = block_sum((int)__popcll(r), red);
     if (t == 0) {
         c.centres[K] = centre;
         c.sizes[K] = size;
@@ -403,10 +384,6 @@ struct Pads {
     long long n_pad, N_pad;
 };
 Pads pads(int N, int m) { return Pads{((long long)m + 3) / 4 * 4, ((long long)N + BLK - 1) / BLK * BLK}; }
-int subset_size(const int32_t *sel, int n_sel, int n_atoms) {
-    if (sel) return n_sel > 0 ? n_sel : -1;
-    return n_sel == 0 ? n_atoms : -1;
-}
 long long cluster_words(int N) { return ((long long)N + 63) / 64; }
 }  // namespace
 

@@ -20,6 +20,7 @@
 // codlad_hist_divergence: one wave per row; the lanes compute the terms of 64 columns, lane 0 adds them in ascending k.
 // -ffp-contract=off: one rounding per operation, in fp32 and in float64.
 #include "common.h"
+#include "reduce_math.h"
 #include "structure_math.h"
 
 namespace {
@@ -33,8 +34,7 @@ constexpr int COL_ROWS = THREADS / COL_TILE;           // structures in flight p
 constexpr int TARGET_GROUPS = 1024;                    // workgroups that fill the device: 4 per compute unit
 constexpr int FILL_BLOCKS = 2048;
 
-__device__ inline int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
-__device__ inline double nan64() { return __longlong_as_double(0x7ff8000000000000ll); }
+// NaN or +-inf by the exponent bits, structure_math.h's non_finite for a double (another body than reduce_math.h's fin64)
 __device__ inline bool non_finite64(double v) {
     return ((unsigned long long)__double_as_longlong(v) & 0x7ff0000000000000ull) == 0x7ff0000000000000ull;
 }
@@ -187,8 +187,7 @@ __global__ __launch_bounds__(WAVE) void hist_divergence_kernel(const int32_t *HA
     long long nA = 0, nB = 0;
     int neg = 0;
     for (int k = threadIdx.x; k < cols; k += WAVE) nA += a[k], nB += b[k], neg |= (a[k] < 0) | (b[k] < 0);
-#pragma unroll
-    for (int st = WAVE / 2; st > 0; st >>= 1) nA += __shfl_xor(nA, st), nB += __shfl_xor(nB, st);
+    nA = wave_sum(nA), nB = wave_sum(nB);
     neg = __syncthreads_or(neg);
     if (neg || nA == 0 || nB == 0) {                              // uniform
         if (threadIdx.x == 0) js[blockIdx.x] = tv[blockIdx.x] = w1[blockIdx.x] = nan64();

@@ -16,7 +16,7 @@
 // add fuse must not depend on the kernel the shared code was inlined into.
 #include "common.h"
 #include "ensemble_math.h"
-#include "../../include/codlad_hip.h"
+#include "host_util.h"
 
 namespace {
 constexpr int BLOCK = 256;
@@ -182,10 +182,6 @@ __global__ __launch_bounds__(BLOCK) void ens_apply_kernel(const float *x, const 
 }
 
 // The atoms summed over: n_sel of sel, or all n_atoms when sel is null.  -1: inconsistent.
-int subset_size(const int32_t *sel, int n_sel, int n_atoms) {
-    if (sel) return n_sel > 0 ? n_sel : -1;
-    return n_sel == 0 ? n_atoms : -1;
-}
 constexpr int MAX_GRID = 0x7fffffff;
 }  // namespace
 

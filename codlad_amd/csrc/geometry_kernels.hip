@@ -39,11 +39,6 @@ constexpr uint32_t NAN_BITS = 0xffc00000u;   // a quiet NaN, negative as an int3
 
 struct Cuts { float scale, clash, near; };
 
-__device__ inline float dist2(float xi, float yi, float zi, float xj, float yj, float zj) {
-    const float dx = xi - xj, dy = yi - yj, dz = zi - zj;
-    return (dx * dx + dy * dy) + dz * dz;
-}
-
 // sqrtf(d2 + EPS) < clash: sqrtf(d2 + EPS) >= sqrtf(d2) (both roundings are monotonic), so d < clash is necessary and
 // the second root is taken for the few pairs that pass it
 __device__ inline bool is_clash(float d2, float d, float clash) { return d < clash && sqrtf(d2 + EPS) < clash; }

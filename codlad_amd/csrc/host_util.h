@@ -1,4 +1,5 @@
-// What the translation units share on the HOST, declared once: the process-wide helpers of host_util.hip, the options
+// What the translation units share on the HOST, declared once: the process-wide helpers of host_util.hip, two small inline
+// helpers of the analysis entry points (subset_size, align256), the options
 // (include/codlad_hip.h says what each means) and the launchers through which denoiser_forward.hip and the encoder reach
 // the kernel units.  Kernels need none of this; their argument structs are in edge_args.h / node_args.h / sampler_args.h.
 #pragma once
@@ -22,6 +23,13 @@ inline int codlad_hip_failed(const char *what, hipError_t e) {
     codlad_set_error("%s: %s", what, hipGetErrorString(e));
     return (int)e;
 }
+// the atoms a fit runs over: n_sel with a selection, all n_atoms without one; -1 when sel and n_sel disagree
+inline int subset_size(const int32_t *sel, int n_sel, int n_atoms) {
+    if (sel) return n_sel > 0 ? n_sel : -1;
+    return n_sel == 0 ? n_atoms : -1;
+}
+// a byte count up to the next multiple of 256: where the next piece of a scratch buffer starts
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 // denoiser_forward.hip: every launcher below reports the grid it launches to the dispatch record (codlad_dispatch_read);
 // node_kernel_h's also its waves per workgroup and whether it takes the XCD-chunked placement
 void dispatch_note(int grid, int stream_waves = 0, bool chunked = false);

@@ -32,7 +32,7 @@
 // in LDS), divides once in float64, and gives such a structure -1 in every count and NaN in every score.
 //
 // Every index a table supplies is clamped before it is used: a wrong table gives wrong counts, never an access out of
-// bounds.  Compiled with -ffp-contract=off: distances round as geometry_kernels.hip's dist2 does.
+// bounds.  Compiled with -ffp-contract=off: distances are structure_math.h's dist2, as geometry_kernels.hip's.
 #include <cmath>
 
 #include "common.h"
@@ -55,7 +55,6 @@ struct Tables {
     int n, m, R;
 };
 
-__device__ inline int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 __device__ inline int atom_of(const Tables &tb, int p) { return tb.sel ? clampi(tb.sel[p], 0, tb.n - 1) : p; }
 __device__ inline int residue_of(const Tables &tb, int p) { return clampi(tb.res[p], 0, tb.R - 1); }
 // the position whose MODEL coordinates position p (of residue r, structure s) reads
@@ -63,11 +62,6 @@ __device__ inline int model_pos(const Tables &tb, int mode, int s, int p, int r)
     if (mode == PLAIN || !tb.partner) return p;
     if (mode == CHOSEN && !tb.swapped[(size_t)s * tb.R + r]) return p;
     return clampi(tb.partner[p], 0, tb.m - 1);
-}
-
-__device__ inline float dist2(float xi, float yi, float zi, float xj, float yj, float zj) {
-    const float dx = xi - xj, dy = yi - yj, dz = zi - zj;
-    return (dx * dx + dy * dy) + dz * dz;
 }
 
 // DECIDE: blockIdx.x = ((s * row_blocks + rb) * tiles + column tile) * 2 + naming, sums to dec [S][R][2]; otherwise

@@ -4,7 +4,8 @@
 // gyration needs no kernel: it is sqrt(G / m) of codlad_ens_moments.
 //
 // SASA, three launches on the caller's stream:
-//   finite_kernel   one workgroup per structure: is any coordinate NaN or +-inf (an integer test on the bit pattern)
+//   finite_kernel   structure_math.h's: one workgroup per structure, is any coordinate NaN or +-inf (an integer test on
+//                   the bit pattern)
 //   sasa_kernel     one WAVE per atom i.  Lane l owns the sphere points l, l + 64, ... (at most 16) as R_i * u_k in
 //                   registers and one alive bit per point.  The structure's atoms are walked in chunks of 64, one candidate
 //                   j per lane: the lane forms x_j - x_i and the conservative overlap test, the wave ballots, and a
@@ -27,6 +28,7 @@
 // Contacts: one thread per pair (a, b) of a 16 x 16 tile of the selection, a loop over the structures; tiles below the
 // diagonal do nothing, the others write (a, b) and (b, a), the diagonal 0: every element is written exactly once.
 #include "common.h"
+#include "reduce_math.h"
 #include "structure_math.h"
 
 namespace {
@@ -36,14 +38,6 @@ constexpr int SUM_THREADS = 256;
 constexpr int RES_CHUNK = 512;               // residue boundaries per launch: 2 KiB of kernel arguments
 constexpr int TILE = 16;
 constexpr float SLACK = 1.0f + 0x1p-10f;
-
-__global__ __launch_bounds__(SUM_THREADS) void finite_kernel(const float *xyz, int n3, uint8_t *finite) {
-    const float *x = xyz + (size_t)blockIdx.x * n3;
-    int bad = 0;
-    for (int k = threadIdx.x; k < n3; k += SUM_THREADS) bad |= non_finite(x[k]);
-    bad = __syncthreads_or(bad);
-    if (threadIdx.x == 0) finite[blockIdx.x] = bad ? 0 : 1;
-}
 
 __device__ inline float lane_read(float v, int lane) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
@@ -99,9 +93,7 @@ __global__ __launch_bounds__(WAVE * WAVES) void sasa_kernel(const float *xyz, in
         }
         if (!__any(alive != 0)) break;
     }
-    int count = __popc(alive);
-#pragma unroll
-    for (int st = WAVE / 2; st > 0; st >>= 1) count += __shfl_xor(count, st);
+    const int count = wave_sum((int)__popc(alive));
     if (lane == 0) {
         exposed[row + i] = count;
         atom_area[row + i] = (float)count * unit_area[i];
@@ -114,7 +106,7 @@ struct ResChunk { int32_t ptr[RES_CHUNK + 1]; };
 __global__ __launch_bounds__(SUM_THREADS) void sasa_sum_kernel(const float *atom_area, int n, int n_struct, const uint8_t *finite,
                                                                ResChunk res, int res0, int res_count, int n_res,
                                                                int res_blocks, float *res_area, double *total) {
-    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    const double nan = nan64();
     if ((int)blockIdx.x < res_blocks) {
         const int k = blockIdx.x * SUM_THREADS + threadIdx.x;
         if (k >= n_struct * res_count) return;
@@ -184,7 +176,7 @@ extern "C" int codlad_sasa(const float *xyz, int n_struct, int n_atoms, const fl
     CODLAD_REQUIRE(blocks * n_struct < (int64_t)1 << 31 && (int64_t)n_atoms * 3 < (int64_t)1 << 31 &&
                    (int64_t)n_struct * RES_CHUNK < (int64_t)1 << 31, "too many workgroups for one launch");
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(finite_kernel, dim3((unsigned)n_struct), dim3(SUM_THREADS), 0, st, xyz, n_atoms * 3, finite);
+    hipLaunchKernelGGL(finite_kernel<SUM_THREADS>, dim3((unsigned)n_struct), dim3(SUM_THREADS), 0, st, xyz, n_atoms * 3, finite);
     int rc = codlad_check_launch("codlad_sasa");
     if (rc) return rc;
     const unsigned grid = (unsigned)(blocks * n_struct);

@@ -4,7 +4,7 @@
 // second moment, and I(q) on any q grid from a host-tabulated sinc.
 //
 // codlad_pair_hist, three launches on the caller's stream:
-//   finite_kernel     one workgroup per structure: is any coordinate NaN or +-inf (as in saxs_kernels.hip)
+//   finite_kernel     structure_math.h's: one workgroup per structure, is any coordinate NaN or +-inf
 //   fill_kernel       H, over = 0 (-1 for a structure that is not finite), d_bin = -1: the call writes every element
 //   pair_hist_kernel  one workgroup of four waves per (structure, item).  The atoms are walked in the caller's order by
 //                     type, so an item has ONE class: the histogram in LDS is n_bins ints.  Lane l owns row position
@@ -17,6 +17,7 @@
 // codlad_pair_hist_profile: plain float64 loops, every sum in the header's one order.  -ffp-contract=off: one rounding per
 // operation, in fp32 and in float64.
 #include "common.h"
+#include "reduce_math.h"
 #include "saxs_math.h"
 #include "structure_math.h"
 
@@ -26,17 +27,6 @@ constexpr int WAVES = 4;
 constexpr int THREADS = WAVE * WAVES;
 constexpr int ITEM = CODLAD_PAIR_HIST_ITEM_WORDS;
 constexpr int FILL_BLOCKS = 2048;
-
-__device__ inline int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
-__device__ inline double nan64() { return __longlong_as_double(0x7ff8000000000000ll); }
-
-__global__ __launch_bounds__(THREADS) void finite_kernel(const float *xyz, int n3, uint8_t *finite) {
-    const float *x = xyz + (size_t)blockIdx.x * n3;
-    int bad = 0;
-    for (int k = threadIdx.x; k < n3; k += THREADS) bad |= non_finite(x[k]);
-    bad = __syncthreads_or(bad);
-    if (threadIdx.x == 0) finite[blockIdx.x] = bad ? 0 : 1;
-}
 
 __global__ __launch_bounds__(THREADS) void fill_kernel(const uint8_t *finite, int n_struct, int64_t per_h, int n_class,
                                                        int32_t *H, int32_t *over, int32_t *d_bin) {
@@ -88,8 +78,7 @@ __global__ __launch_bounds__(THREADS) void pair_hist_kernel(const float *xyz, in
             }
         }
     }
-#pragma unroll
-    for (int st = WAVE / 2; st > 0; st >>= 1) ov += __shfl_xor(ov, st);
+    ov = wave_sum(ov);
     if (lane == 0 && ov) atomicAdd(&over[(size_t)s * n_class + c], ov);
     __syncthreads();
     int32_t *out = H + ((size_t)s * n_class + c) * n_bins;
@@ -232,7 +221,7 @@ extern "C" int codlad_pair_hist(const float *xyz, int n_struct, int n_atoms, con
     const int n_class = n_types * (n_types + 1) / 2;
     const int64_t per_h = (int64_t)n_class * n_bins;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(finite_kernel, dim3((unsigned)n_struct), dim3(THREADS), 0, st, xyz, n_atoms * 3, finite);
+    hipLaunchKernelGGL(finite_kernel<THREADS>, dim3((unsigned)n_struct), dim3(THREADS), 0, st, xyz, n_atoms * 3, finite);
     int rc = codlad_check_launch("codlad_pair_hist");
     if (rc) return rc;
     const int64_t fill = (per_h * n_struct + THREADS - 1) / THREADS;

@@ -24,7 +24,7 @@
 //                   A row of a panel is 64 + 16 doubles, so the four k of an operand start on other banks.
 //   cov_reduce_kernel  the chunks of an element in ascending order, / W, the element and its mirror from the one value
 //   corr_kernel     the per-atom cross-correlation and the trace
-// The structures are cut into at most 32 chunks whose size depends on N alone.  No atomics, no scratch memory.
+// The structures are cut into at most 32 chunks whose size depends on N alone (reduce_math.h's chunks_of).  No atomics, no scratch memory.
 //
 // The eigenpairs: blocked subspace iteration with a Rayleigh-Ritz step on b = min(k + 8, d) <= 72 columns, every block
 // stored column by column ([b][d], the layout of `components`):
@@ -37,52 +37,17 @@
 //   rot_kernel      V = Q S, Y = Z S (= C V), |Y_i - theta_i V_i|, the sign of the largest entry
 //   status_kernel   the stop rule; on the last iteration the results
 // All sums have one order: ascending index per thread, the xor butterfly per wave (strides 32 .. 1), the waves in ascending
-// order.  Compiled with -ffp-contract=off; fused multiply-adds are asked for by name.
+// order (reduce_math.h).  Compiled with -ffp-contract=off; fused multiply-adds are asked for by name.
 #include "common.h"
 #include "ensemble_math.h"
-#include "../../include/codlad_hip.h"
+#include "host_util.h"
+#include "reduce_math.h"
 
 namespace {
-typedef double double4_t __attribute__((ext_vector_type(4)));
-
 constexpr int MAX_N = CODLAD_PCA_MAX_N, MAX_D = CODLAD_PCA_MAX_DIM, MAX_K = CODLAD_PCA_MAX_COMPONENTS;
 constexpr int MAX_B = MAX_K + 8;            // columns of the iterated block
-constexpr int MAX_CHUNKS = 32, CHUNK_ROWS = 512;
 constexpr int BLOCK = 256;
 enum { PH_NEW = 0, PH_RUNNING = 1, PH_DONE = 2 };
-
-__device__ inline double nan64() { return __longlong_as_double(0x7ff8000000000000ll); }
-__device__ inline bool fin64(double x) { return fabs(x) < __longlong_as_double(0x7ff0000000000000ll); }
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int st = 32; st > 0; st >>= 1) v += __shfl_xor(v, st);
-    return v;
-}
-// the workgroup's sum (any multiple of 64 threads up to 1024): the butterfly per wave, the waves in ascending order; every
-// thread gets it.  red holds 16 doubles.
-__device__ __forceinline__ double block_sum(double v, double *red) {
-    v = wave_sum(v);
-    __syncthreads();                                   // the previous use of red has been read
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = 0.0;
-    for (int k = 0; k < (int)(blockDim.x >> 6); ++k) s += red[k];
-    return s;
-}
-
-// the chunks of structures: their number and size depend on N alone
-struct Chunks {
-    int nch, chunk;
-};
-Chunks chunks_of(int N) {
-    int nch = (N + CHUNK_ROWS - 1) / CHUNK_ROWS;
-    nch = nch > MAX_CHUNKS ? MAX_CHUNKS : nch;
-    Chunks c;
-    c.chunk = ((N + nch - 1) / nch + 15) / 16 * 16;
-    c.nch = (N + c.chunk - 1) / c.chunk;
-    return c;
-}
 
 // ------------------------------------------------------------------------------------------------------------ the fit --
 struct Fit {
@@ -343,12 +308,6 @@ struct Cov {
     double *part, *C;
 };
 
-__device__ __forceinline__ void tile_of(int t, int &I, int &J) {      // tile t of the lower triangle, row by row
-    I = 0;
-    while ((I + 1) * (I + 2) / 2 <= t) ++I;
-    J = t - I * (I + 1) / 2;
-}
-
 // element e of a step's 2 * KC * TILE doubles: block I's rows, then block J's times the weight
 __device__ __forceinline__ double cov_load(const Cov &p, int I, int J, int s0, int s1, int e) {
     const int which = e / (KC * TILE), r = (e % (KC * TILE)) / TILE, c = e % TILE;
@@ -363,7 +322,7 @@ __device__ __forceinline__ double cov_load(const Cov &p, int I, int J, int s0, i
 __global__ __launch_bounds__(CT) void pca_cov_kernel(Cov p) {
     __shared__ double panel[2][KC * ROW];
     int I, J;
-    tile_of(blockIdx.x, I, J);
+    tri_tile_of(blockIdx.x, I, J);
     const int ch = blockIdx.y, t = threadIdx.x, lane = t & 63, ti = t >> 6;
     const int lr = lane & 15, lk = lane >> 4;
     const int s_begin = ch * p.chunk, s_end = min(p.N, s_begin + p.chunk);
@@ -411,7 +370,7 @@ __global__ __launch_bounds__(CT) void pca_cov_kernel(Cov p) {
 // a workgroup per tile: element (i, j), i >= j, = the chunks in ascending order / W, written with its mirror
 __global__ __launch_bounds__(BLOCK) void pca_cov_reduce_kernel(Cov p) {
     int I, J;
-    tile_of(blockIdx.x, I, J);
+    tri_tile_of(blockIdx.x, I, J);
     const double W = p.scal[CODLAD_PCA_SC_W];
     for (int e = threadIdx.x; e < TILE * TILE; e += BLOCK) {
         const int i = I * TILE + e / TILE, j = J * TILE + e % TILE;
@@ -578,10 +537,13 @@ __global__ __launch_bounds__(BLOCK) void pca_h_kernel(Eig g) {
     if (g.state[CODLAD_PCA_ST_PHASE] != PH_RUNNING) return;
     __shared__ double red[16];
     int p, q;
-    tile_of(blockIdx.x, p, q);
+    tri_tile_of(blockIdx.x, p, q);
     double acc = 0.0;
     for (int r = threadIdx.x; r < g.d; r += BLOCK) acc = fma(g.Q[(size_t)p * g.d + r], g.Z[(size_t)q * g.d + r], acc);
-    acc = block_sum(acc, red);
+    // 0.0 +: when every product underflows to -0.0 the waves' sum is -0.0, and its sign would reach H, a diagonal element
+    // the Jacobi never rotates and so an eigenvalue; every other block_sum of this file adds squares or plain coordinates
+    // from +0.0 and cannot be -0.0
+    acc = 0.0 + block_sum(acc, red);
     if (threadIdx.x == 0) g.H[p * g.b + q] = g.H[q * g.b + p] = acc;
 }
 
@@ -742,15 +704,7 @@ __global__ __launch_bounds__(BLOCK) void pca_project_kernel(const double *D, con
     P[e] = acc;
 }
 
-int subset_size(const int32_t *sel, int n_sel, int n_atoms) {
-    if (sel) return n_sel > 0 ? n_sel : -1;
-    return n_sel == 0 ? n_atoms : -1;
-}
 bool positive(double v) { return v > 0.0 && v < __builtin_inf(); }
-int tiles_of(int d) {
-    const int T = (d + TILE - 1) / TILE;
-    return T * (T + 1) / 2;
-}
 long long eig_doubles(int d, int b) { return 4ll * b * d + 3ll * b * b + 3ll * b; }
 }  // namespace
 
@@ -818,7 +772,7 @@ extern "C" int codlad_pca_deviations(const float *x, const double *Rt, const uin
 extern "C" long long codlad_pca_covariance_scratch_bytes(int N, int d) {
     CODLAD_REQUIRE(N > 0 && N <= MAX_N && d > 0 && d <= MAX_D && d % 3 == 0,
                    "bad sizes (1 <= N <= CODLAD_PCA_MAX_N, d = 3 m <= CODLAD_PCA_MAX_DIM)");
-    return 8ll * chunks_of(N).nch * tiles_of(d) * TILE * TILE;
+    return 8ll * chunks_of(N).nch * tri_tiles_of(d, TILE) * TILE * TILE;
 }
 
 extern "C" int codlad_pca_covariance(const double *D, const double *w, const uint8_t *finite, int N, int d, const double *scal,
@@ -828,7 +782,7 @@ extern "C" int codlad_pca_covariance(const double *D, const double *w, const uin
                    "bad sizes (1 <= N <= CODLAD_PCA_MAX_N, d = 3 m <= CODLAD_PCA_MAX_DIM)");
     const Chunks c = chunks_of(N);
     Cov p;
-    p.D = D, p.w = w, p.scal = scal, p.finite = finite, p.N = N, p.d = d, p.ntiles = tiles_of(d);
+    p.D = D, p.w = w, p.scal = scal, p.finite = finite, p.N = N, p.d = d, p.ntiles = tri_tiles_of(d, TILE);
     p.nch = c.nch, p.chunk = c.chunk, p.part = (double *)scratch, p.C = cov;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(pca_cov_kernel, dim3((unsigned)p.ntiles, (unsigned)p.nch), dim3(CT), 0, st, p);

@@ -291,7 +291,6 @@ __global__ __launch_bounds__(ROWS) void relax_step_kernel(int t, int n_iter, int
     }
 }
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 struct Scratch {
     size_t partials, d0, q0, xt, ga, gt, hst, gacc, gtrial, total;

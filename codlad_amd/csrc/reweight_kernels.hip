@@ -25,8 +25,9 @@
 //   ladder_max, ladder_sum, ladder_pick   Gamma(mu + t p) for t = 2^0 .. 2^-15 from a_j - t s_j; the largest t that
 //                   passes the Armijo test moves mu
 // Reductions over the structures: blocks of 256 rows whatever the grid, a wave's 64 values by the xor butterfly, the four
-// waves and then the blocks in ascending order.  No atomics.  An excluded row has U = 0 and w = 0: it adds exact zeros.
+// waves and then the blocks in ascending order (reduce_math.h).  No atomics.  An excluded row has U = 0 and w = 0: it adds exact zeros.
 #include "common.h"
+#include "reduce_math.h"
 #include "../../include/codlad_hip.h"
 
 namespace {
@@ -34,7 +35,6 @@ constexpr int RB = 256;                  // rows of a block of structures = thre
 constexpr int TILE = 64, JT = 16;        // covariance: the tile, the rows staged at a time
 constexpr int NB = 32;                   // Cholesky: the panel width
 constexpr int NT = CODLAD_REWEIGHT_LADDER;
-constexpr int MAX_CHUNKS = 32, CHUNK_ROWS = 512;
 constexpr int PAR = 8;                   // per problem: theta, c, Gamma, max a, Z, log Z
 enum { P_THETA, P_C, P_GAMMA, P_AMAX, P_Z, P_LOGZ };
 enum { S_CHI2_PRIOR, S_CHI2, S_SREL, S_PHI };
@@ -51,37 +51,7 @@ struct Rw {
     uint8_t *used;
 };
 
-__device__ inline double nan64() { return __longlong_as_double(0x7ff8000000000000ll); }
 __device__ inline double ninf64() { return __longlong_as_double(0xfff0000000000000ll); }
-__device__ inline bool fin64(double x) { return fabs(x) < __longlong_as_double(0x7ff0000000000000ll); }
-// a NaN on either side stays
-__device__ inline double max_nan(double a, double b) { return (b > a || b != b) ? b : a; }
-
-__device__ inline double wave_sum(double x) {
-#pragma unroll
-    for (int st = 32; st > 0; st >>= 1) x += __shfl_xor(x, st);
-    return x;
-}
-__device__ inline double wave_max(double x) {
-#pragma unroll
-    for (int st = 32; st > 0; st >>= 1) x = max_nan(x, __shfl_xor(x, st));
-    return x;
-}
-// the workgroup's 256 values: the waves by the butterfly, then ((w0 + w1) + w2) + w3; every thread gets the result
-__device__ inline double block_sum(double x, double *red) {
-    x = wave_sum(x);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
-__device__ inline double block_max(double x, double *red) {
-    x = wave_max(x);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-    __syncthreads();
-    return max_nan(max_nan(max_nan(red[0], red[1]), red[2]), red[3]);
-}
 
 // ------------------------------------------------------------------------------------------------------ once per call --
 __global__ __launch_bounds__(RB) void prep_kernel(Rw r) {
@@ -316,12 +286,6 @@ __global__ __launch_bounds__(RB) void grad_kernel(Rw r) {
     else if (r.n_iter[p] >= r.max_iter) r.status[p] = CODLAD_REWEIGHT_CAP;
 }
 
-__device__ inline void tile_of(int ti, int &bi, int &bj) {            // lower triangle, rows ascending: ti = bi (bi + 1) / 2 + bj
-    bi = 0;
-    while ((bi + 1) * (bi + 2) / 2 <= ti) ++bi;
-    bj = ti - bi * (bi + 1) / 2;
-}
-
 // one wave per (tile, chunk): lane (ty, tx) of 8 x 8 owns the rows ty * 4 .. + 3 and 32 + ty * 4 .. + 3 of the tile and the
 // columns tx * 4 .. + 3 and 32 + tx * 4 .. + 3: four 32-byte LDS reads feed 64 fused multiply-adds
 __global__ __launch_bounds__(64) void cov_kernel(Rw r) {
@@ -331,7 +295,7 @@ __global__ __launch_bounds__(64) void cov_kernel(Rw r) {
     __shared__ __attribute__((aligned(32))) double Bs[JT][TILE];
     const int ch = blockIdx.x / r.nt, ti = blockIdx.x % r.nt;
     int bi, bj;
-    tile_of(ti, bi, bj);
+    tri_tile_of(ti, bi, bj);
     const int t = threadIdx.x, ty = t >> 3, tx = t & 7;
     const int ka = bi * TILE + t, kb = bj * TILE + t;
     const bool ina = ka < r.M, inb = kb < r.M;
@@ -386,7 +350,7 @@ __global__ __launch_bounds__(RB) void hess_kernel(Rw r) {
     const int p = blockIdx.y;
     if (r.status[p] != -1) return;
     int bi, bj;
-    tile_of(blockIdx.x, bi, bj);
+    tri_tile_of(blockIdx.x, bi, bj);
     const double theta = r.par[(size_t)p * PAR + P_THETA], c = r.par[(size_t)p * PAR + P_C];
     const double *part = r.cov + ((size_t)p * r.nch * r.nt + blockIdx.x) * (TILE * TILE);
     double *H = r.H + (size_t)p * r.Mp * r.Mp;
@@ -651,12 +615,9 @@ Dims dims(int N, int M) {
     Dims d;
     d.Mp = (M + NB - 1) / NB * NB;
     d.nb = (int)(((long long)N + RB - 1) / RB);
-    int nch = (int)(((long long)N + CHUNK_ROWS - 1) / CHUNK_ROWS);
-    nch = nch > MAX_CHUNKS ? MAX_CHUNKS : nch;
-    d.chunk = (int)((((long long)N + nch - 1) / nch + JT - 1) / JT * JT);
-    d.nch = (int)(((long long)N + d.chunk - 1) / d.chunk);
-    const int T = (M + TILE - 1) / TILE;
-    d.nt = T * (T + 1) / 2;
+    const Chunks c = chunks_of(N);
+    d.chunk = c.chunk, d.nch = c.nch;
+    d.nt = tri_tiles_of(M, TILE);
     d.shared = (long long)N * M + 2ll * N + d.nb + 2ll * d.Mp + (long long)d.nb * d.Mp;
     d.per_problem = PAR + 3ll * d.Mp + 2ll * N + 3ll * d.nb + 2ll * d.nb * d.Mp + 2ll * d.nb * NT +
                     (long long)d.nch * d.nt * TILE * TILE + (long long)d.Mp * d.Mp;

@@ -15,6 +15,7 @@
 // codlad_saxs_hydration_fit: one workgroup per curve set, a thread per grid point (strided); +, * and / in float64 only.
 // -ffp-contract=off: one rounding per operation, in fp32 and in float64.
 #include "common.h"
+#include "reduce_math.h"
 #include "saxs_math.h"
 #include "structure_math.h"
 
@@ -25,8 +26,6 @@ constexpr int THREADS = WAVE * WAVES;
 constexpr int QC = CODLAD_SAXS_HYD_Q_CHUNK;
 constexpr int NP = CODLAD_SAXS_HYD_PARTIALS;
 static_assert(NP == 6 && NP * QC <= THREADS, "one thread writes one (partial, k) of a chunk");
-
-__device__ inline double nan64() { return __longlong_as_double(0x7ff8000000000000ll); }
 
 __global__ __launch_bounds__(THREADS) void finite_kernel(const float *xyz, const float *weight, int n, uint8_t *finite) {
     const float *x = xyz + (size_t)blockIdx.x * n * 3, *wt = weight + (size_t)blockIdx.x * n;
@@ -41,7 +40,7 @@ __global__ __launch_bounds__(THREADS) void saxs_part_kernel(const float *xyz, in
                                                             int n_types, const float *ff_t, const float *ff_d,
                                                             const float *weight, const float *q, int n_q, const uint8_t *finite,
                                                             double *partial) {
-    __shared__ double wave_sum[WAVES][NP][QC];
+    __shared__ double wave_part[WAVES][NP][QC];
     const int s = blockIdx.x / n_wg, p = blockIdx.x % n_wg;
     if (!finite[s]) return;                                       // its partials are never read
     const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
@@ -119,17 +118,15 @@ __global__ __launch_bounds__(THREADS) void saxs_part_kernel(const float *xyz, in
         for (int c = 0; c < NP; ++c) {
 #pragma unroll
             for (int kk = 0; kk < QC; ++kk) {
-                double e = E[c][kk];
-#pragma unroll
-                for (int st = WAVE / 2; st > 0; st >>= 1) e += __shfl_xor(e, st);
-                if (lane == 0) wave_sum[w][c][kk] = e;
+                const double e = wave_sum(E[c][kk]);
+                if (lane == 0) wave_part[w][c][kk] = e;
             }
         }
         __syncthreads();
         if ((int)threadIdx.x < NP * QC) {
             const int c = threadIdx.x / QC, kk = threadIdx.x % QC;
             if (kk < kc)
-                out[(size_t)c * n_q + c0 + kk] = ((wave_sum[0][c][kk] + wave_sum[1][c][kk]) + wave_sum[2][c][kk]) + wave_sum[3][c][kk];
+                out[(size_t)c * n_q + c0 + kk] = ((wave_part[0][c][kk] + wave_part[1][c][kk]) + wave_part[2][c][kk]) + wave_part[3][c][kk];
         }
         __syncthreads();
     }

@@ -3,7 +3,7 @@
 // over all pairs of every structure of a call - no neighbour list, no cut-off, no atomics, each structure on its own.
 //
 // Three launches on the caller's stream (a fourth, one thread per k, when the ensemble mean is asked for):
-//   finite_kernel     one workgroup per structure: is any coordinate NaN or +-inf (as in observables_kernels.hip)
+//   finite_kernel     structure_math.h's: one workgroup per structure, is any coordinate NaN or +-inf
 //   saxs_pair_kernel  one workgroup of four waves per (structure, pair of row blocks p and B - 1 - p: the triangle is
 //                     evenly loaded).  Lane l owns atom i of the row block; a wave walks its partner tiles, 64 atoms a tile,
 //                     one partner per lane in registers: the j loop is wave-uniform, partner j's coordinates and type come
@@ -14,6 +14,7 @@
 // parity), not the hardware instruction and not a library call: the float32 restatement of the tests performs the same
 // operations.  -ffp-contract=off: one rounding per operation, in fp32 and in float64.
 #include "common.h"
+#include "reduce_math.h"
 #include "saxs_math.h"
 #include "structure_math.h"
 
@@ -23,18 +24,10 @@ constexpr int WAVES = 4;
 constexpr int THREADS = WAVE * WAVES;
 constexpr int QC = CODLAD_SAXS_Q_CHUNK;
 
-__global__ __launch_bounds__(THREADS) void finite_kernel(const float *xyz, int n3, uint8_t *finite) {
-    const float *x = xyz + (size_t)blockIdx.x * n3;
-    int bad = 0;
-    for (int k = threadIdx.x; k < n3; k += THREADS) bad |= non_finite(x[k]);
-    bad = __syncthreads_or(bad);
-    if (threadIdx.x == 0) finite[blockIdx.x] = bad ? 0 : 1;
-}
-
 __global__ __launch_bounds__(THREADS) void saxs_pair_kernel(const float *xyz, int n, int n_blocks, int n_wg, const int32_t *type,
                                                             int n_types, const float *ff, const float *q, int n_q,
                                                             const uint8_t *finite, double *partial) {
-    __shared__ double wave_sum[WAVES][QC];
+    __shared__ double wave_part[WAVES][QC];
     const int s = blockIdx.x / n_wg, p = blockIdx.x % n_wg;
     if (!finite[s]) return;                                       // its partials are never read
     const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
@@ -96,15 +89,13 @@ __global__ __launch_bounds__(THREADS) void saxs_pair_kernel(const float *xyz, in
         }
 #pragma unroll
         for (int kk = 0; kk < QC; ++kk) {
-            double e = E[kk];
-#pragma unroll
-            for (int st = WAVE / 2; st > 0; st >>= 1) e += __shfl_xor(e, st);
-            if (lane == 0) wave_sum[w][kk] = e;
+            const double e = wave_sum(E[kk]);
+            if (lane == 0) wave_part[w][kk] = e;
         }
         __syncthreads();
         if ((int)threadIdx.x < kc) {
             const int kk = threadIdx.x;
-            out[c0 + kk] = ((wave_sum[0][kk] + wave_sum[1][kk]) + wave_sum[2][kk]) + wave_sum[3][kk];
+            out[c0 + kk] = ((wave_part[0][kk] + wave_part[1][kk]) + wave_part[2][kk]) + wave_part[3][kk];
         }
         __syncthreads();
     }
@@ -115,7 +106,7 @@ __global__ __launch_bounds__(THREADS) void saxs_sum_kernel(const double *partial
     const int64_t e = (int64_t)blockIdx.x * THREADS + threadIdx.x;
     if (e >= (int64_t)n_struct * n_q) return;
     const int s = (int)(e / n_q), k = (int)(e % n_q);
-    double sum = __longlong_as_double(0x7ff8000000000000ll);
+    double sum = nan64();
     if (finite[s]) {
         sum = 0.0;
         const double *part = partial + (size_t)s * n_wg * n_q + k;
@@ -133,7 +124,7 @@ __global__ __launch_bounds__(THREADS) void saxs_mean_kernel(const double *I, con
     int count = 0;
     for (int s = 0; s < n_struct; ++s)
         if (finite[s]) sum += I[(size_t)s * n_q + k], ++count;
-    mean[k] = count ? sum / (double)count : __longlong_as_double(0x7ff8000000000000ll);
+    mean[k] = count ? sum / (double)count : nan64();
 }
 }  // namespace
 
@@ -148,7 +139,7 @@ extern "C" int codlad_saxs_debye(const float *xyz, int n_struct, int n_atoms, co
     CODLAD_REQUIRE(n_wg * n_struct < (int64_t)1 << 31 && (int64_t)n_atoms * 3 < (int64_t)1 << 31,
                    "too many workgroups for one launch");
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(finite_kernel, dim3((unsigned)n_struct), dim3(THREADS), 0, st, xyz, n_atoms * 3, finite);
+    hipLaunchKernelGGL(finite_kernel<THREADS>, dim3((unsigned)n_struct), dim3(THREADS), 0, st, xyz, n_atoms * 3, finite);
     int rc = codlad_check_launch("codlad_saxs_debye");
     if (rc) return rc;
     hipLaunchKernelGGL(saxs_pair_kernel, dim3((unsigned)(n_wg * n_struct)), dim3(THREADS), 0, st, xyz, n_atoms, (int)blocks,

@@ -1,5 +1,8 @@
-"""What the structure-analysis entry points share: the check of a structure batch, the per-topology cache, and the
+"""What the structure-analysis entry points share: the check of a structure batch, of a pool with its atom selection and
+weights, of a positive number and a count, the flag and scratch buffers of a call, the per-topology cache, and the
 tables of a template (covalent radii, exclusion CSR, bond list) that the geometry check and the relaxation both read."""
+import math
+
 import torch
 
 from .. import _lib
@@ -29,6 +32,77 @@ def structures(xyz, what, n_atoms=None, dims=3):
     if n_atoms is not None and xyz.shape[-2] != n_atoms:
         raise ValueError(f"{what} has {xyz.shape[-2]} atoms, the topology {n_atoms}")
     return xyz.detach().to(torch.float32).contiguous()
+
+
+def selection(sel, n_atoms, dev):
+    """sel (index list / tensor, or None) -> (int32 device tensor or None, count for the C ABI)."""
+    if sel is None:
+        return None, 0
+    idx = torch.as_tensor(sel).reshape(-1).to(torch.int64)
+    if idx.numel() == 0:
+        raise ValueError("sel is empty")
+    if int(idx.min()) < 0 or int(idx.max()) >= n_atoms:
+        raise ValueError(f"sel has an index outside [0, {n_atoms})")
+    return idx.to(device=dev, dtype=torch.int32).contiguous(), idx.numel()
+
+
+def pool(x, sel, what, max_n):
+    """One pool of structures x [N, n, 3] and its atom selection -> (the checked structures, sel on the device, n_sel).  A
+    CPU tensor is refused first, then a pool of more than max_n structures, then the selection."""
+    x = structures(x, f"{what}: x")
+    if x.shape[0] > max_n:
+        raise ValueError(f"{what}: at most {max_n} structures in one pool, got {x.shape[0]}")
+    sel, n_sel = selection(sel, x.shape[1], x.device)
+    return x, sel, n_sel
+
+
+def weights(weights, N, dev, what, need_positive):
+    """Per-structure weights -> float64 [N] on dev; ValueError unless there are N of them, finite and >= 0.  With
+    need_positive, None stays None (no weights) and one weight at least must be > 0."""
+    if need_positive and weights is None:
+        return None
+    w = torch.as_tensor(weights).detach().to(torch.float64).reshape(-1)
+    if w.shape[0] != N:
+        raise ValueError(f"{what}: weights must have one value per structure ({N}), got {w.shape[0]}")
+    if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+        raise ValueError(f"{what}: weights must be finite and >= 0")
+    if need_positive and not bool((w > 0).any()):
+        raise ValueError(f"{what}: every weight is 0")
+    return w.to(dev).contiguous()
+
+
+def positive(v, name, what):
+    """v as a float; ValueError unless it is a positive finite number (a bool counts as the number it is)."""
+    try:
+        f = float(v)
+    except (TypeError, ValueError):
+        f = math.nan
+    if not (math.isfinite(f) and f > 0):
+        raise ValueError(f"{what}: {name} must be a positive finite number, got {v!r}")
+    return f
+
+
+def count(v, name, hi, what, types=(int,)):
+    """v as an int; ValueError unless it is one of `types` (never a bool) in 1 .. hi."""
+    if isinstance(v, bool) or not isinstance(v, types) or not 1 <= v <= hi:
+        raise ValueError(f"{what}: {name} must be an integer in 1 .. {hi}, got {v!r}")
+    return int(v)
+
+
+def flags(N, dev):
+    """An uninitialised uint8 [N] on dev for per-structure flags a kernel writes.  The allocation holds two elements or
+    more: tests/memcheck.py cannot tell a one-element integer buffer from its poison."""
+    return torch.empty(max(N, 2), dtype=torch.uint8, device=dev)[:N]
+
+
+def scratch(fn_name, *args, dev, dtype=torch.float64):
+    """The scratch tensor (float64 words; int64 where a kernel keeps integers there) of the size
+    codlad_..._scratch_bytes(*args) asks for, rounded up to whole words; a negative size raises what _lib.check makes of
+    the library's last error, under the function's name."""
+    nbytes = getattr(_lib.lib(), fn_name)(*args)
+    if nbytes < 0:
+        _lib.check(-1, fn_name)
+    return torch.empty((nbytes + 7) // 8, dtype=dtype, device=dev)
 
 
 def cached(top, name, key, build):

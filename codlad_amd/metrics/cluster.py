@@ -9,28 +9,10 @@ import torch
 
 from .. import _lib
 from . import _inputs
-from .ensemble import _moments, _pair_msd, _selection
+from .ensemble import _moments, _pair_msd
 
 CLUSTER_MAX_N = _lib.CLUSTER_MAX_N
 CLUSTER_BATCH = 64            # rounds enqueued between two looks at the number of structures still active
-
-
-def _pool(x, sel, what):
-    x = _inputs.structures(x, f"{what}: x")
-    if x.shape[0] > CLUSTER_MAX_N:
-        raise ValueError(f"{what}: at most {CLUSTER_MAX_N} structures in one pool, got {x.shape[0]}")
-    sel, n_sel = _selection(sel, x.shape[1], x.device)
-    return x, sel, n_sel
-
-
-def _cutoff(cutoff, what):
-    try:
-        c = float(cutoff)
-    except (TypeError, ValueError):
-        c = math.nan
-    if not (math.isfinite(c) and c > 0):
-        raise ValueError(f"{what}: cutoff must be a positive finite number, got {cutoff!r}")
-    return c
 
 
 def _matrix(x, sel, n_sel, cut2, squared, want_matrix, want_bits):
@@ -38,10 +20,7 @@ def _matrix(x, sel, n_sel, cut2, squared, want_matrix, want_bits):
     dev = x.device
     lib = _lib.lib()
     mom = _moments(x, N, n, sel, n_sel)
-    nbytes = lib.codlad_rmsd_matrix_scratch_bytes(N, n_sel or n)
-    if nbytes < 0:
-        _lib.check(-1, "codlad_rmsd_matrix_scratch_bytes")
-    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    scratch = _inputs.scratch("codlad_rmsd_matrix_scratch_bytes", N, n_sel or n, dev=dev)
     out = torch.empty(N, N, dtype=torch.float64, device=dev) if want_matrix else None
     # the bitmap and the finite bytes share one allocation of two words or more (tests/memcheck.py cannot tell a
     # one-element integer buffer from its poison)
@@ -62,7 +41,7 @@ def rmsd_matrix(x, sel=None, squared=False):
     diagonal exactly 0; the row and the column of a structure with a NaN or an infinity among its selected atoms are NaN.
     An element depends on its two structures alone, and a repeat gives the same bits - not those of superposed_rmsd_batch,
     whose sums have another order."""
-    x, sel, n_sel = _pool(x, sel, "rmsd_matrix")
+    x, sel, n_sel = _inputs.pool(x, sel, "rmsd_matrix", CLUSTER_MAX_N)
     return _matrix(x, sel, n_sel, 0.0, squared, True, False)[0]
 
 
@@ -71,22 +50,13 @@ def rmsd_neighbours(x, cutoff, sel=None, return_matrix=False):
     bit j & 63 of word j >> 6 of row i is set iff both structures are finite and msd_ij <= cutoff^2, the diagonal bit of a
     finite structure included, bits at j >= N zero), finite bool [N], n = N, and with return_matrix rmsd float64 [N, N].
     Without return_matrix no N x N table is made: 512 MB of bits for 65 536 structures."""
-    c = _cutoff(cutoff, "rmsd_neighbours")
-    x, sel, n_sel = _pool(x, sel, "rmsd_neighbours")
+    c = _inputs.positive(cutoff, "cutoff", "rmsd_neighbours")
+    x, sel, n_sel = _inputs.pool(x, sel, "rmsd_neighbours", CLUSTER_MAX_N)
     out, bits, finite = _matrix(x, sel, n_sel, c * c, False, return_matrix, True)
     res = dict(bits=bits, finite=finite.to(torch.bool), n=x.shape[0])
     if return_matrix:
         res["rmsd"] = out
     return res
-
-
-def _weights(weights, N, dev):
-    w = torch.as_tensor(weights).detach().to(torch.float64).reshape(-1)
-    if w.shape[0] != N:
-        raise ValueError(f"cluster: weights must have one value per structure ({N}), got {w.shape[0]}")
-    if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
-        raise ValueError("cluster: weights must be finite and >= 0")
-    return w.to(dev).contiguous()
 
 
 def cluster_neighbours(bits, n, finite=None, weights=None):
@@ -111,13 +81,10 @@ def cluster_neighbours(bits, n, finite=None, weights=None):
         if fin.shape[0] != n:
             raise ValueError(f"cluster_neighbours: finite must have one entry per structure ({n}), got {fin.shape[0]}")
         fin = fin.to(device=dev).to(torch.uint8).contiguous()
-    w = None if weights is None else _weights(weights, n, dev)
+    w = None if weights is None else _inputs.weights(weights, n, dev, "cluster", False)
     bits = bits.contiguous()
     lib = _lib.lib()
-    nbytes = lib.codlad_cluster_scratch_bytes(n)
-    if nbytes < 0:
-        _lib.check(-1, "codlad_cluster_scratch_bytes")
-    scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    scratch = _inputs.scratch("codlad_cluster_scratch_bytes", n, dev=dev, dtype=torch.int64)
     state = torch.zeros(_lib.CLUSTER_STATE_WORDS, dtype=torch.int32, device=dev)          # phase 0: new
     labels, centres, sizes = torch.empty(3, n, dtype=torch.int32, device=dev).unbind(0)
     p = _lib.ptr
@@ -151,11 +118,11 @@ def cluster(x, cutoff, sel=None, weights=None, return_matrix=False):
     rmsd [N, N].  centre_rmsd is read from the matrix when it was asked for; otherwise it is N pairs through
     superposed_rmsd_batch's kernel, to the bit what that gives for (structure, its centre).  weights [N] (>= 0, finite;
     for instance reweight's w) turn the populations into the weighted ones."""
-    c = _cutoff(cutoff, "cluster")
-    x, sel, n_sel = _pool(x, sel, "cluster")
+    c = _inputs.positive(cutoff, "cutoff", "cluster")
+    x, sel, n_sel = _inputs.pool(x, sel, "cluster", CLUSTER_MAX_N)
     N = x.shape[0]
     if weights is not None:
-        _weights(weights, N, x.device)                        # refused before any launch
+        _inputs.weights(weights, N, x.device, "cluster", False)                      # refused before any launch
     rmsd, bits, finite = _matrix(x, sel, n_sel, c * c, False, return_matrix, True)
     out = cluster_neighbours(bits, N, finite=finite, weights=weights)
     lab = out["labels"].to(torch.int64)

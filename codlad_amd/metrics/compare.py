@@ -12,7 +12,6 @@ import torch
 
 from .. import _lib
 from . import _inputs
-from .ensemble import _selection
 
 COMPARE_MAX_BINS, DIST_HIST_MAX_SEL, DIVERGENCE_MAX_COLS = _lib.COMPARE_MAX_BINS, _lib.DIST_HIST_MAX_SEL, _lib.DIVERGENCE_MAX_COLS
 COMPARE_MAX_ROWS = _lib.COMPARE_MAX_ROWS
@@ -34,26 +33,11 @@ def pair_table(m):
 
 
 def _n_bins(n_bins, what, name="n_bins"):
-    if isinstance(n_bins, bool) or not isinstance(n_bins, (int, np.integer)) or not 1 <= n_bins <= COMPARE_MAX_BINS:
-        raise ValueError(f"{what}: {name} must be an integer in 1 .. {COMPARE_MAX_BINS}, got {n_bins!r}")
-    return int(n_bins)
-
-
-def _positive(v, name, what):
-    try:
-        f = float(v)
-    except (TypeError, ValueError):
-        f = math.nan
-    if not (math.isfinite(f) and f > 0):
-        raise ValueError(f"{what}: {name} must be a positive finite number, got {v!r}")
-    return f
+    return _inputs.count(n_bins, name, COMPARE_MAX_BINS, what, types=(int, np.integer))      # numpy integers are taken here
 
 
 def _pool(x, sel, what):
-    x = _inputs.structures(x, f"{what}: x")
-    if x.shape[0] > COMPARE_MAX_ROWS:
-        raise ValueError(f"{what}: at most {COMPARE_MAX_ROWS} structures in one pool, got {x.shape[0]}")
-    sel, n_sel = _selection(sel, x.shape[1], x.device)
+    x, sel, n_sel = _inputs.pool(x, sel, what, COMPARE_MAX_ROWS)
     m = n_sel or x.shape[1]
     if not 2 <= m <= DIST_HIST_MAX_SEL:
         raise ValueError(f"{what}: 2 .. {DIST_HIST_MAX_SEL} selected atoms, got {m}")
@@ -72,7 +56,7 @@ def _dist_launch(x, sel, n_sel, m, inv_dr, n_bins, what):
     dev = x.device
     words = _table_bytes("codlad_dist_hist_bytes", m, n_bins, what) // 4
     H = torch.empty(words, dtype=torch.int32, device=dev).view(m * (m - 1) // 2, n_bins + 2)
-    finite = torch.empty(max(N, 2), dtype=torch.uint8, device=dev)[:N]
+    finite = _inputs.flags(N, dev)
     n_counted = torch.empty(2, dtype=torch.int32, device=dev)[:1]
     p = _lib.ptr
     rc = _lib.lib().codlad_dist_hist(p(x), N, n, p(sel), n_sel, inv_dr, n_bins, p(H), p(finite), p(n_counted), _lib.stream_ptr(dev))
@@ -85,14 +69,14 @@ def _grid(dr, r_max, n_bins, what):
     and n_bins given leave r_max = n_bins dr, dr and r_max given leave n_bins = ceil(r_max / dr)."""
     if dr is None:
         n_bins = _n_bins(n_bins, what)
-        r_max = _positive(r_max, "r_max", what)
+        r_max = _inputs.positive(r_max, "r_max", what)
         dr = r_max / n_bins
     else:
-        dr = _positive(dr, "dr", what)
+        dr = _inputs.positive(dr, "dr", what)
         if r_max is None:
             n_bins = _n_bins(n_bins, what)
         else:
-            n_bins = max(1, int(math.ceil(_positive(r_max, "r_max", what) / dr - 1e-9)))
+            n_bins = max(1, int(math.ceil(_inputs.positive(r_max, "r_max", what) / dr - 1e-9)))
             if n_bins > COMPARE_MAX_BINS:
                 raise ValueError(f"{what}: at most {COMPARE_MAX_BINS} bins, r_max = {r_max} at dr = {dr} asks for {n_bins}")
         r_max = n_bins * dr

@@ -24,16 +24,7 @@ def superposed_rmsd(a, b):
 # --- Superposition on the device (codlad_ens_*, csrc/ensemble_kernels.hip): minimal RMSD under a proper rotation plus
 # translation for many pairs per launch, fp64 after an exact conversion of the fp32 coordinates, deterministic sums.
 
-def _selection(sel, n_atoms, dev):
-    """sel (index list / tensor, or None) -> (int32 device tensor or None, count for the C ABI)."""
-    if sel is None:
-        return None, 0
-    idx = torch.as_tensor(sel).reshape(-1).to(torch.int64)
-    if idx.numel() == 0:
-        raise ValueError("sel is empty")
-    if int(idx.min()) < 0 or int(idx.max()) >= n_atoms:
-        raise ValueError(f"sel has an index outside [0, {n_atoms})")
-    return idx.to(device=dev, dtype=torch.int32).contiguous(), idx.numel()
+_selection = _inputs.selection        # the name the tests and metrics/__init__.py reach it by
 
 
 def _moments(x, n_conf, n_atoms, sel, n_sel):

@@ -8,7 +8,6 @@ import torch
 
 from .. import _lib
 from . import _inputs
-from .ensemble import _selection
 
 LDDT_MAX_THRESHOLDS, LDDT_MAX_ATOMS = _lib.LDDT_MAX_THRESHOLDS, _lib.LDDT_MAX_ATOMS
 LDDT_THRESHOLDS = (0.5, 1.0, 2.0, 4.0)
@@ -155,7 +154,7 @@ def lddt_lists(xyz, ref, res_ptr, swap_partner=None, ref_index=None, sel=None, c
     _inputs.need_cuda(xyz, "lddt: xyz")
     n_atoms = int(np.asarray(res_ptr).reshape(-1)[-1]) if np.size(res_ptr) else 0
     x, y, idx = _checked(xyz, ref, n_atoms, ref_index)
-    sel_d, n_sel = _selection(sel, n_atoms, x.device)
+    sel_d, n_sel = _inputs.selection(sel, n_atoms, x.device)
     tab = _tables(res_ptr, n_atoms, None if sel_d is None else sel_d.cpu().numpy(), swap_partner)
     return _launch(x, y, idx, n_sel, sel_d, _on(x.device, tab), params)
 
@@ -189,7 +188,7 @@ def lddt(xyz, ref, top, ref_index=None, sel=None, cutoff=15.0, thresholds=LDDT_T
     params = _params(cutoff, thresholds, seq_sep)
     x, y, idx = _checked(xyz, ref, top.n_atoms, ref_index)
     dev = x.device
-    sel_d, n_sel = _selection(sel, top.n_atoms, dev)
+    sel_d, n_sel = _inputs.selection(sel, top.n_atoms, dev)
     partner = lddt_symmetry(top) if symmetry else None
     build = lambda s: _on(dev, _tables(top.first_atom, top.n_atoms, s, partner))                 # noqa: E731
     tab = _inputs.cached(top, "_lddt_tables", (bool(symmetry), str(dev)), lambda: build(None)) if sel_d is None \

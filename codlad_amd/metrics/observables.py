@@ -7,7 +7,7 @@ import torch
 
 from .. import _lib
 from . import _inputs
-from .ensemble import _moments, _selection
+from .ensemble import _moments
 
 VDW_RADII = {"C": 1.70, "N": 1.55, "O": 1.52, "S": 1.80, "P": 1.80, "H": 1.20}       # Bondi (1964), A
 SASA_MAX_POINTS = _lib.SASA_MAX_POINTS
@@ -114,7 +114,7 @@ def radius_of_gyration(xyz, sel=None):
     of the atoms `sel` (default: all), m their number - G of codlad_ens_moments, no kernel of its own.  NaN for a structure
     with a coordinate that is not a number."""
     x = _inputs.structures(xyz, "radius_of_gyration: xyz")
-    sel, n_sel = _selection(sel, x.shape[1], x.device)
+    sel, n_sel = _inputs.selection(sel, x.shape[1], x.device)
     mom = _moments(x, x.shape[0], x.shape[1], sel, n_sel)
     return torch.sqrt(mom[:, 3] / float(n_sel or x.shape[1]))
 
@@ -127,7 +127,7 @@ def contact_map(xyz, sel=None, cutoff=8.0):
     if not float(cutoff) >= 0:
         raise ValueError(f"contact_map: cutoff must be >= 0, got {cutoff}")
     S, n = x.shape[0], x.shape[1]
-    sel, n_sel = _selection(sel, n, x.device)
+    sel, n_sel = _inputs.selection(sel, n, x.device)
     m = n_sel or n
     counts = torch.empty(m, m, dtype=torch.int32, device=x.device)
     rc = _lib.lib().codlad_contact_counts(_lib.ptr(x), S, n, _lib.ptr(sel), n_sel, C.c_float(float(cutoff) ** 2),

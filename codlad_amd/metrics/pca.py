@@ -5,59 +5,20 @@ units (covariance), its largest eigenpairs with the projections of the pool (pca
 model (pca_project).  The host enqueues the iterations of the fit and of the eigen-solve in batches and reads one word per
 batch.  weights [N] (>= 0, finite; for instance reweight's w) make every average the weighted one; uniform weights that
 are 1 or another power of two return the bits of weights=None (a weight enters every sum as one exact factor)."""
-import math
-
 import torch
 
 from .. import _lib
 from . import _inputs
-from .ensemble import _moments, _selection
+from .ensemble import _moments
 
 PCA_MAX_N, PCA_MAX_DIM, PCA_MAX_COMPONENTS = _lib.PCA_MAX_N, _lib.PCA_MAX_DIM, _lib.PCA_MAX_COMPONENTS
 PCA_FIT_BATCH = 8             # iterations of the fit enqueued between two looks at its state
 PCA_EIG_BATCH = 16            # iterations of the eigen-solve enqueued between two looks
 
 
-def _pool(x, sel, what):
-    x = _inputs.structures(x, f"{what}: x")
-    if x.shape[0] > PCA_MAX_N:
-        raise ValueError(f"{what}: at most {PCA_MAX_N} structures in one pool, got {x.shape[0]}")
-    sel, n_sel = _selection(sel, x.shape[1], x.device)
-    return x, sel, n_sel
-
-
-def _weights(weights, N, dev, what):
-    if weights is None:
-        return None
-    w = torch.as_tensor(weights).detach().to(torch.float64).reshape(-1)
-    if w.shape[0] != N:
-        raise ValueError(f"{what}: weights must have one value per structure ({N}), got {w.shape[0]}")
-    if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
-        raise ValueError(f"{what}: weights must be finite and >= 0")
-    if not bool((w > 0).any()):
-        raise ValueError(f"{what}: every weight is 0")
-    return w.to(dev).contiguous()
-
-
-def _positive(v, name, what):
-    try:
-        f = float(v)
-    except (TypeError, ValueError):
-        f = math.nan
-    if not (math.isfinite(f) and f > 0):
-        raise ValueError(f"{what}: {name} must be a positive finite number, got {v!r}")
-    return f
-
-
-def _count(v, name, hi, what):
-    if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= hi:
-        raise ValueError(f"{what}: {name} must be an integer in 1 .. {hi}, got {v!r}")
-    return v
-
-
 def _fit_args(N, weights, start, tol, max_iter, what):
-    tol = _positive(tol, "tol", what)
-    max_iter = _count(max_iter, "max_iter", _lib.PCA_MAX_ITER, what)
+    tol = _inputs.positive(tol, "tol", what)
+    max_iter = _inputs.count(max_iter, "max_iter", _lib.PCA_MAX_ITER, what)
     if start is not None:
         if isinstance(start, bool) or not isinstance(start, int) or not 0 <= start < N:
             raise ValueError(f"{what}: start must be the index of a structure (0 .. {N - 1}), got {start!r}")
@@ -81,15 +42,12 @@ def _fit(x, sel, n_sel, w, start, tol, max_iter):
     lib = _lib.lib()
     p = _lib.ptr
     mom = _moments(x, N, n, sel, n_sel)
-    nbytes = lib.codlad_pca_fit_scratch_bytes(N, m)
-    if nbytes < 0:
-        _lib.check(-1, "codlad_pca_fit_scratch_bytes")
-    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    scratch = _inputs.scratch("codlad_pca_fit_scratch_bytes", N, m, dev=dev)
     state = torch.zeros(_lib.PCA_STATE_WORDS, dtype=torch.int32, device=dev)          # phase 0: new
     scal = torch.empty(_lib.PCA_SCALARS, dtype=torch.float64, device=dev)
     target, mean = torch.empty(2, m, 3, dtype=torch.float64, device=dev).unbind(0)
     Rt = torch.empty(N, 12, dtype=torch.float64, device=dev)
-    finite = torch.empty(max(N, 2), dtype=torch.uint8, device=dev)[:N]               # (tests/memcheck.py: two elements or more)
+    finite = _inputs.flags(N, dev)
     for _batch in range(max_iter // PCA_FIT_BATCH + 2):
         rc = lib.codlad_pca_fit(p(x), p(mom), N, n, p(sel), n_sel, p(w), start, tol, max_iter, PCA_FIT_BATCH, p(state), p(scal),
                                 p(target), p(mean), p(Rt), p(finite), p(scratch), _lib.stream_ptr(dev))
@@ -128,10 +86,7 @@ def _covariance(f, D):
     N, d = D.shape
     dev = D.device
     lib = _lib.lib()
-    nbytes = lib.codlad_pca_covariance_scratch_bytes(N, d)
-    if nbytes < 0:
-        _lib.check(-1, "codlad_pca_covariance_scratch_bytes")
-    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    scratch = _inputs.scratch("codlad_pca_covariance_scratch_bytes", N, d, dev=dev)
     cov = torch.empty(d, d, dtype=torch.float64, device=dev)
     corr = torch.empty(d // 3, d // 3, dtype=torch.float64, device=dev)
     total = torch.empty(1, dtype=torch.float64, device=dev)
@@ -146,10 +101,7 @@ def _eigen(cov, k, rtol, max_iter):
     d = cov.shape[0]
     dev = cov.device
     lib = _lib.lib()
-    nbytes = lib.codlad_pca_eigen_scratch_bytes(d, k)
-    if nbytes < 0:
-        _lib.check(-1, "codlad_pca_eigen_scratch_bytes")
-    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    scratch = _inputs.scratch("codlad_pca_eigen_scratch_bytes", d, k, dev=dev)
     state = torch.zeros(_lib.PCA_STATE_WORDS, dtype=torch.int32, device=dev)
     evals, resid = torch.empty(2, k, dtype=torch.float64, device=dev).unbind(0)
     comps = torch.empty(k, d, dtype=torch.float64, device=dev)
@@ -176,10 +128,10 @@ def _project(D, comps):
 
 
 def _checked_fit(x, sel, weights, start, tol, max_iter, what, need_dim=False):
-    x, sel, n_sel = _pool(x, sel, what)
+    x, sel, n_sel = _inputs.pool(x, sel, what, PCA_MAX_N)
     if need_dim:
         _dim(n_sel, x.shape[1], what)
-    w = _weights(weights, x.shape[0], x.device, what)
+    w = _inputs.weights(weights, x.shape[0], x.device, what, True)
     tol, max_iter, start = _fit_args(x.shape[0], w, start, tol, max_iter, what)
     return _fit(x, sel, n_sel, w, start, tol, max_iter)
 
@@ -228,12 +180,12 @@ def pca(x, n_components=10, sel=None, weights=None, rtol=1e-10, max_iter=1000, r
     "limit"); with return_covariance cov and cross_correlation, with return_deviations deviations [N, 3 m].  A covariance of
     rank below k gives eigenvalues that are zero within rounding and still orthonormal components."""
     what = "pca"
-    x, sel, n_sel = _pool(x, sel, what)
+    x, sel, n_sel = _inputs.pool(x, sel, what, PCA_MAX_N)
     m = _dim(n_sel, x.shape[1], what)
-    k = _count(n_components, "n_components", min(PCA_MAX_COMPONENTS, 3 * m), what)
-    rtol = _positive(rtol, "rtol", what)
-    max_iter = _count(max_iter, "max_iter", _lib.PCA_MAX_ITER, what)
-    w = _weights(weights, x.shape[0], x.device, what)
+    k = _inputs.count(n_components, "n_components", min(PCA_MAX_COMPONENTS, 3 * m), what)
+    rtol = _inputs.positive(rtol, "rtol", what)
+    max_iter = _inputs.count(max_iter, "max_iter", _lib.PCA_MAX_ITER, what)
+    w = _inputs.weights(weights, x.shape[0], x.device, what, True)
     tol, fit_max_iter, start = _fit_args(x.shape[0], w, start, tol, fit_max_iter, what)
     f = _fit(x, sel, n_sel, w, start, tol, fit_max_iter)
     D, fluct = _deviations(f, True, True)
@@ -256,7 +208,7 @@ def pca_project(y, model):
     what = "pca_project"
     if not isinstance(model, dict) or "mean" not in model or "components" not in model:
         raise ValueError(f"{what}: model must be the dict pca returns (mean, components)")
-    y, sel, n_sel = _pool(y, model.get("sel"), what)
+    y, sel, n_sel = _inputs.pool(y, model.get("sel"), what, PCA_MAX_N)
     N, n = y.shape[:2]
     mean, comps = model["mean"], model["components"]
     m = _dim(n_sel, n, what)
@@ -269,7 +221,7 @@ def pca_project(y, model):
     mom = _moments(y, N, n, sel, n_sel)
     tmom = torch.empty(4, dtype=torch.float64, device=dev)
     Rt = torch.empty(N, 12, dtype=torch.float64, device=dev)
-    finite = torch.empty(max(N, 2), dtype=torch.uint8, device=dev)[:N]
+    finite = _inputs.flags(N, dev)
     p = _lib.ptr
     rc = _lib.lib().codlad_pca_align(p(y), p(mom), N, n, p(sel), n_sel, p(mean), p(tmom), p(Rt), p(finite), _lib.stream_ptr(dev))
     _lib.check(rc, "codlad_pca_align")

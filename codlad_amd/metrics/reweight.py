@@ -68,10 +68,7 @@ def _solve(what, Y, y, sigma, theta, w0, scale, mu0, gtol, max_iter):
     dev = Yd.device
     (N, M), T = Yd.shape, th.shape[0]
     lib = _lib.lib()
-    nbytes = lib.codlad_reweight_scratch_bytes(N, M, T)
-    if nbytes < 0:
-        _lib.check(-1, "codlad_reweight_scratch_bytes")
-    scratch = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+    scratch = _inputs.scratch("codlad_reweight_scratch_bytes", N, M, T, dev=dev)
     f64 = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=dev)     # noqa: E731
     mu, w, mean, scal = f64(T, M), f64(T, N), f64(T, M), f64(T, _lib.REWEIGHT_SCALARS)
     n_iter = torch.empty(T, dtype=torch.int32, device=dev)
@@ -79,7 +76,7 @@ def _solve(what, Y, y, sigma, theta, w0, scale, mu0, gtol, max_iter):
     used = torch.empty(N, dtype=torch.uint8, device=dev)
     p = _lib.ptr
     rc = lib.codlad_reweight_solve(p(Yd), p(yd), p(sd), p(w0d), N, M, th.ctypes.data, sc.ctypes.data, T, p(mu0d), float(gtol),
-                                   int(max_iter), p(scratch), nbytes, p(mu), p(w), p(mean), p(scal), p(n_iter), p(status), p(used),
+                                   int(max_iter), p(scratch), 8 * scratch.numel(), p(mu), p(w), p(mean), p(scal), p(n_iter), p(status), p(used),
                                    _lib.stream_ptr(dev))
     _lib.check(rc, "codlad_reweight_solve")
     out = dict(mu=mu, w=w, mean=mean, chi2_prior=scal[:, 0], chi2=scal[:, 1], s_rel=scal[:, 2], phi_eff=scal[:, 3], n_iter=n_iter,

@@ -63,7 +63,7 @@ def body(args, dev, lines):
         t_fit = events(fit, args.repeats)
         lines.append(f"N = {N}, m = {m} (d = {d}): fit {f0['status']} in {f0['n_iter']} iterations")
         lines.append(f"  fit                  HIP events {spread(t_fit)}   = {med(t_fit) / f0['n_iter'] * 1e3:.3f} ms per iteration")
-        x_, sel, n_sel = P._pool(x, None, "pca_cost")
+        x_, sel, n_sel = P._inputs.pool(x, None, "pca_cost", P.PCA_MAX_N)
         rec = P._fit(x_, sel, n_sel, None, -1, 1e-6, 100)
         D, _ = P._deviations(rec, True, True)
         cov_call = lambda: P._covariance(rec, D)          # noqa: E731
