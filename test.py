@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Inference entry point, drop-in for the sampling part of the reference's test.py
-(`--experiment latent` and `--experiment recon`), running on the HIP path.
+(`--experiment latent` and `--experiment recon`), running on the HIP path.  `--help` describes every flag.
 
 Kept from the reference (test.py:894-961): flag names and defaults, checkpoint locations
 (`./results/<exp>/protein_weights_{best,last,step_N}.pt` with `net_model` / `ema_model`, VQ-VAE
@@ -8,72 +8,21 @@ directories of utils/model_module.py), the call sequence build_model -> create_d
 p_sample_loop -> get_norm_feature -> latent_decode -> ic_to_xyz, and the output directory.
 Different by design: all ensemble members of a batch of frames are sampled in ONE launch set (the
 reference loops over them); the C2 prior call that only supplies `mask` (test.py:495) is replaced by
-the length mask; mdtraj I/O is replaced by saving coordinates as .npy (and multi-model PDB + .xtc, --save_pdb).
-Addition: `--superpose first|ref` writes the --save_pdb models superposed on model 0 of their frame's ensemble or on the true
-structure (CA fit on the device, metrics.superpose); the .npy is never altered.
-Data: `--pdb_files ens.pdb ...` (multi-model PDB ensembles -> the reference's load_dataset without mdtraj),
-`--data_process --data_files f.pkl ...` (pickled per-frame dicts, as the reference's --data_process branch reads
-them) or `--synthetic` (no PED/PDB/Atlas files ship with the reference).
-Addition: `--fix_residues SPEC` keeps the VQ-VAE encoder's latents of the chosen residues (residue pinning, a
-`PinLatents` denoised_fn) and samples the rest of each structure conditioned on them.
-Addition: `--sampler ddim [--eta E]` samples the latents with DDIM (ddim_sample_loop) instead of the ancestral DDPM loop.
-Addition: `--sampler dpmpp` samples them with DPM-Solver++(2M) (dpm_solver_sample_loop: deterministic, multistep, meant for
-10-25 steps); `--timestep_spacing logsnr` spaces the --num_sampling_steps steps uniformly in log-SNR (the spec "logsnrN";
-steps that fall on the same base step merge, the run prints how many are kept) instead of uniformly in t.
-Flow matching (`--model fm ...`): the ODE sampler runs fused on the device; `--compute_nfe` prints the model evaluations of
-every batch; addition: `--ode_stepwise` integrates with one model call per stage from the host instead (same numbers).
-Addition: `--experiment bpd` scores the checkpoint instead of sampling from it: the variational bound in bits per dimension
-(calc_bpd_loop over --num_sampling_steps respaced steps, one fused loop per batch) of the batch's own VQ-VAE latents; prints
-the mean total_bpd / prior_bpd per file and saves vb / mse / xstart_mse [N, T] as .npy.  One rank only.
-Addition: `--experiment fmloss` scores a flow-matching checkpoint (--model fm / icfm / vpfm) the way the reference's
-validation pass does (train_latent.py:338-350: the matcher's path, the model, loss_fn), at the K = --num_steps times
-(k + 0.5) / K, one fused sweep per batch: x1 = the batch's own VQ-VAE latents, x0 and the path's noise from the run's seed;
-prints the mean --loss per file and per time and saves the per-sample table [N, K] as .npy.  One rank only.
-Addition: `--cg_pdb ca.pdb ... [--cg_xtc traj.xtc]` backmaps a CA-only (coarse-grained) trajectory: the sequence and the CA
-frames are all the input there is (utils/cg_input.py), the atoms written are the residue templates'.  The chain loses its
-first and last residue, which supply only the flanking CAs (as on every route).  With no true atoms there is no Evaluation
-block; instead `--geometry_check` (implied by --cg_pdb, available on every route whose topology is known) judges every
-generated structure against its template topology on the device (metrics.geometry_check): broken / spurious bonds, clashes.
-Addition: `--stereo_check` (opt-in, wherever --geometry_check is allowed) adds what the covalent graph cannot see
-(metrics.stereo_check): inverted CA / CB centres, cis and twisted peptide bonds, and the phi / psi / omega / chi table.
-Addition: `--relax [N]` (opt-in, wherever --geometry_check is allowed) relaxes every generated structure on the device before
-it is checked and written (metrics.relax: N iterations of restrained steepest descent, CAs fixed): overlapping atoms are
-pushed apart, bonded geometry and rigid torsions stay the decoder's.  The decoder's own coordinates are kept beside them.
-Addition: `--observables [N_POINTS]` (opt-in, wherever --geometry_check is allowed; after --relax when both are given)
-describes the written ensemble on the device: per-residue solvent-accessible surface area (metrics.sasa, N_POINTS test
-points per atom), the radius of gyration of every structure and the CA contact-frequency map at 8 A.
-Addition: `--dssp` (opt-in, wherever --geometry_check is allowed; after --relax when both are given) assigns the secondary
-structure of every written structure on the device (metrics.dssp: Kabsch-Sander hydrogen bonds, DSSP states) and the
-propensity of each state per residue over the file's structures.
-Addition: `--saxs [N_Q]` (opt-in, wherever --observables is allowed; after --relax when both are given) computes the
-small-angle X-ray scattering profile of every written structure on the device (metrics.saxs_profile: the Debye sum over
-all atom pairs, united-atom form factors in a displaced solvent) on N_Q points of [0, 0.5] 1/A, or on the q grid of
-`--saxs_data FILE` (q, I, sigma columns), against which the ensemble mean is then scaled and its reduced chi^2 printed.
-`--saxs_hydration [C1 C2]` (only with --saxs) adds the hydration shell and the excluded-volume scale, given or fitted to
---saxs_data (metrics.saxs_partials, saxs_hydration_fit).
-`--saxs_reweight THETA [THETA ...]` (with --saxs and --saxs_data) reweights the written structures against the curve by
-maximum entropy at every THETA (metrics.saxs_reweight, the scale fitted along) and prints the L-curve.
-`--cluster CUTOFF` clusters the written structures of every data file (Daura / GROMOS, metrics.cluster) at the RMSD
-CUTOFF in A over the CA atoms (`--cluster_atoms all`: every atom).
-`--pca [K]` (default 10) describes how the written structures of every data file move (metrics.pca): the mean structure
-after mutual superposition, the RMSF and the K largest principal components of the covariance, over the CA atoms
-(`--pca_atoms all`: every written atom, while 3 x atoms <= 4096).
-`--compare [N_BINS]` (default 50) compares the written structures of every data file, as one ensemble, with the file's
-true frames (metrics.ensemble_compare): Jensen-Shannon divergences of every CA-CA distance distribution, of Rg and, when
-the topology is known and no atom is masked, of the backbone and side-chain torsions; `--compare_cluster CUTOFF` adds
-the cluster-population similarity (ENCORE's CES).
-`--lddt` (wherever --compare applies) scores every written structure against the true frame its CA trace came from
-(metrics.lddt): the local distance difference test per structure and per residue, superposition-free, with symmetric side
-chains in the better naming; masked atoms take no part.
-Addition: `--pr [DR]` (opt-in, wherever --observables is allowed; after --relax when both are given) computes the pair
-distribution P(r) of every written structure on the device (metrics.pair_distribution: the typed pair-distance histogram
-in bins of DR A, default 0.5, weighted with the forward amplitudes) and prints D_max, the real-space Rg and the number of
-structures with pairs beyond the contour-length bound.
+the length mask; mdtraj I/O is replaced by saving coordinates as .npy (and multi-model PDB + .xtc, --save_pdb);
+torchdiffeq.odeint by the fused ODE loop; every batch draws its noise from its own generator, so a structure does
+not depend on the number of GPUs.
+Data: `--pdb_files`, `--data_process --data_files`, `--cg_pdb` (CA-only, no true atoms: no Evaluation block) or
+`--synthetic` (no PED/PDB/Atlas files ship with the reference).
+Additions with no counterpart in the reference: the samplers (--sampler, --timestep_spacing, --fix_residues), the
+scores of a checkpoint (--experiment bpd / fmloss), --relax, and the analyses of the written structures: the rows of
+ANALYSES below, each of which says in one place where it applies, what it launches, writes and prints.  Everything
+a batch launches is enqueued before its one torch.cuda.synchronize() and read back after it.
 """
 import argparse
 import os
 import pickle
 import time
+import types
 
 import numpy as np
 import torch
@@ -185,99 +134,37 @@ def check_cg_input(args):
             raise SystemExit("--cg_pdb cannot be combined with --superpose ref: there is no true structure to superpose on "
                              "(use --superpose first)")
     elif want:
-        if args.experiment in ("bpd", "fmloss"):
-            raise SystemExit(f"--geometry_check judges generated structures: --experiment {args.experiment} generates none")
-        if args.data_process and not args.synthetic:
-            raise SystemExit("--geometry_check needs the topology of the structures: --data_process pickles carry none "
-                             "(use --pdb_files, --cg_pdb or --synthetic)")
+        refuse_out_of_scope(args, GEOMETRY)
     args.geometry_check = want
     return want
 
 
-def check_stereo(args):
-    """Where --stereo_check applies: exactly where --geometry_check does - structures are generated and their topology is
-    known.  (The refusals of --cg_pdb itself are check_cg_input's.)  Returns whether it is on."""
-    want = bool(getattr(args, "stereo_check", False))
-    if want and not getattr(args, "cg_pdb", None):
-        if args.experiment in ("bpd", "fmloss"):
-            raise SystemExit(f"--stereo_check judges generated structures: --experiment {args.experiment} generates none")
-        if args.data_process and not args.synthetic:
-            raise SystemExit("--stereo_check needs the topology of the structures: --data_process pickles carry none "
-                             "(use --pdb_files, --cg_pdb or --synthetic)")
-    args.stereo_check = want
-    return want
+REQUIRED, USED = "required", "used"        # what an analysis needs of the input route's topology; None: nothing
 
 
-def check_relax(args):
-    """Where --relax applies: exactly where --geometry_check does (structures are generated and their topology is known; the
-    refusals of --cg_pdb itself are check_cg_input's).  Returns the number of iterations, 0 = off."""
-    n = getattr(args, "relax", None)
-    if n is None:
-        args.relax = 0
-        return 0
-    if n < 0:
-        raise SystemExit(f"--relax takes a number of iterations >= 0, got {n}")
-    if not getattr(args, "cg_pdb", None):
-        if args.experiment in ("bpd", "fmloss"):
-            raise SystemExit(f"--relax relaxes generated structures: --experiment {args.experiment} generates none")
-        if args.data_process and not args.synthetic:
-            raise SystemExit("--relax needs the topology of the structures: --data_process pickles carry none "
-                             "(use --pdb_files, --cg_pdb or --synthetic)")
-    return n
+def refuse_out_of_scope(args, row):
+    """The scope refusals every analysis (and --relax) shares, each with its own verb: structures are generated (not with
+    --experiment bpd / fmloss) and, for a row that requires the topology, the input route knows it (--data_process pickles
+    carry none).  The refusals of --cg_pdb itself are check_cg_input's; a row that requires the topology leaves them to it."""
+    early = row.topology == REQUIRED and not row.late
+    if early and getattr(args, "cg_pdb", None):
+        return
+    experiment = getattr(args, "experiment", "latent")
+    if experiment in ("bpd", "fmloss"):
+        raise SystemExit(f"{row.flag} {row.does}: --experiment {experiment} generates none")
+    if early and args.data_process and not args.synthetic:
+        raise SystemExit(f"{row.flag} needs the topology of the structures: --data_process pickles carry none "
+                         "(use --pdb_files, --cg_pdb or --synthetic)")
 
 
-def check_observables(args):
-    """Where --observables applies: exactly where --geometry_check does (structures are generated and their topology is
-    known; the refusals of --cg_pdb itself are check_cg_input's).  Returns the number of test points per atom, 0 = off."""
-    n = getattr(args, "observables", None)
-    if n is None:
-        args.observables = 0
-        return 0
-    if not 1 <= n <= metrics.SASA_MAX_POINTS:
-        raise SystemExit(f"--observables takes a number of test points per atom in 1 .. {metrics.SASA_MAX_POINTS}, got {n}")
-    if not getattr(args, "cg_pdb", None):
-        if args.experiment in ("bpd", "fmloss"):
-            raise SystemExit(f"--observables describes generated structures: --experiment {args.experiment} generates none")
-        if args.data_process and not args.synthetic:
-            raise SystemExit("--observables needs the topology of the structures: --data_process pickles carry none "
-                             "(use --pdb_files, --cg_pdb or --synthetic)")
-    return n
-
-
-def check_saxs(args):
-    """Where --saxs applies: exactly where --observables does.  Returns the number of q values, 0 = off."""
-    n = getattr(args, "saxs", None)
-    if n is None:
-        if getattr(args, "saxs_data", None):
-            raise SystemExit("--saxs_data needs --saxs: the curve is compared with the profile --saxs computes")
-        args.saxs = 0
-        return 0
-    if not 1 <= n <= metrics.SAXS_MAX_Q:
-        raise SystemExit(f"--saxs takes a number of q values in 1 .. {metrics.SAXS_MAX_Q}, got {n}")
-    if not getattr(args, "cg_pdb", None):
-        if args.experiment in ("bpd", "fmloss"):
-            raise SystemExit(f"--saxs describes generated structures: --experiment {args.experiment} generates none")
-        if args.data_process and not args.synthetic:
-            raise SystemExit("--saxs needs the topology of the structures: --data_process pickles carry none "
-                             "(use --pdb_files, --cg_pdb or --synthetic)")
-    return n
-
-
-def check_pr(args):
-    """Where --pr applies: exactly where --observables does.  Returns the bin width in A, 0 = off."""
-    dr = getattr(args, "pr", None)
-    if dr is None:
-        args.pr = 0.0
-        return 0.0
-    if not (np.isfinite(dr) and dr > 0):
-        raise SystemExit(f"--pr takes a bin width in A, a positive number, got {dr}")
-    if not getattr(args, "cg_pdb", None):
-        if args.experiment in ("bpd", "fmloss"):
-            raise SystemExit(f"--pr describes generated structures: --experiment {args.experiment} generates none")
-        if args.data_process and not args.synthetic:
-            raise SystemExit("--pr needs the topology of the structures: --data_process pickles carry none "
-                             "(use --pdb_files, --cg_pdb or --synthetic)")
-    return dr
+def topology_of(name, row):
+    """The Topology of the written residues of one output file, as `row` needs it: a row that requires one is refused on an
+    input route that knows none, one that merely uses it gets None there, and so does a row that needs none."""
+    if row.topology and name in _GEOMETRY_TOP:
+        return _GEOMETRY_TOP[name]
+    if row.topology == REQUIRED:
+        raise SystemExit(f"{row.flag}: the topology of {name} is not known on this input route")
+    return None
 
 
 def check_saxs_hydration(args):
@@ -318,51 +205,6 @@ def check_saxs_reweight(args):
     return args.saxs_reweight
 
 
-def check_cluster(args):
-    """--cluster CUTOFF: a positive finite RMSD in A; it describes generated structures.  Returns the cut-off, 0 = off."""
-    c = getattr(args, "cluster", None)
-    if c is None:
-        args.cluster = 0.0
-        return 0.0
-    if not (np.isfinite(c) and c > 0):
-        raise SystemExit(f"--cluster takes an RMSD cut-off in A, a positive number, got {c}")
-    if getattr(args, "experiment", "latent") in ("bpd", "fmloss"):
-        raise SystemExit(f"--cluster describes generated structures: --experiment {args.experiment} generates none")
-    return c
-
-
-def check_pca(args):
-    """--pca [K]: the number of principal components, 1 .. 64; it describes generated structures.  Returns K, 0 = off."""
-    k = getattr(args, "pca", None)
-    if k is None:
-        args.pca = 0
-        return 0
-    if not 1 <= k <= 64:
-        raise SystemExit(f"--pca takes the number of components, 1 .. 64, got {k}")
-    if getattr(args, "experiment", "latent") in ("bpd", "fmloss"):
-        raise SystemExit(f"--pca describes generated structures: --experiment {args.experiment} generates none")
-    return k
-
-
-def check_compare(args):
-    """--compare [N_BINS]: the number of distance bins, 1 .. 256; it compares generated structures with the true frames.
-    --compare_cluster CUTOFF (only with --compare): a positive finite RMSD in A.  Returns N_BINS, 0 = off."""
-    k = getattr(args, "compare", None)
-    c = getattr(args, "compare_cluster", None)
-    if c is not None and not (np.isfinite(c) and c > 0):
-        raise SystemExit(f"--compare_cluster takes an RMSD cut-off in A, a positive number, got {c}")
-    if k is None:
-        if c is not None:
-            raise SystemExit("--compare_cluster needs --compare")
-        args.compare = 0
-        return 0
-    if not 1 <= k <= metrics.COMPARE_MAX_BINS:
-        raise SystemExit(f"--compare takes the number of distance bins, 1 .. {metrics.COMPARE_MAX_BINS}, got {k}")
-    if getattr(args, "experiment", "latent") in ("bpd", "fmloss"):
-        raise SystemExit(f"--compare compares generated structures with the true ones: --experiment {args.experiment} generates none")
-    return k
-
-
 def compare_truth(name, batch, flag="--compare"):
     """The true coordinates --compare and --lddt measure against: batch["nxyz"][:, 1:], [frames * n_atoms, 3]; SystemExit when
     the input route has none (--cg_pdb)."""
@@ -381,12 +223,6 @@ def compare_no_atom_masked(batch):
     return not bool(m.any()) if m.dtype == torch.bool else m.numel() == 0
 
 
-def check_lddt(args):
-    """--lddt scores generated structures against the true frames."""
-    if getattr(args, "lddt", False) and getattr(args, "experiment", "latent") in ("bpd", "fmloss"):
-        raise SystemExit(f"--lddt scores generated structures against the true ones: --experiment {args.experiment} generates none")
-
-
 def lddt_selection(batch, n_frames, n_atoms):
     """The atoms --lddt scores: those mask_xyz_list (a boolean mask or an index list over frames * n_atoms) masks in no frame,
     as an index list; None when nothing is masked."""
@@ -398,47 +234,6 @@ def lddt_selection(batch, n_frames, n_atoms):
     masked[m.reshape(-1) if m.dtype == torch.bool else m.reshape(-1).long()] = True
     masked = masked.reshape(n_frames, n_atoms).any(0)
     return None if not bool(masked.any()) else torch.nonzero(~masked).reshape(-1).tolist()
-
-
-def lddt_report(name, ld):
-    """The printed summary of --lddt for one output file (ld: metrics.lddt's dict) -> the stats."""
-    g, res = ld["global"].cpu().numpy(), ld["residue"].cpu().numpy()
-    scored = res[~np.isnan(res)]
-    stats = {"data_name": name, "lddt_mean": float(np.nanmean(g)), "lddt_median": float(np.nanmedian(g)), "lddt_min": float(np.nanmin(g)),
-             "lddt_residues_below_0.7": float((scored < 0.7).mean()) if scored.size else float("nan"),
-             "lddt_swapped_residues": int(ld["swapped"].sum()), "lddt_not_finite": int((~ld["finite"]).sum())}
-    print("############## vvvvvvvvv lDDT of the generated structures against their true frames (1 = every local distance kept):")
-    print(f"lddt {name}: global mean {stats['lddt_mean']:.4f} median {stats['lddt_median']:.4f} min {stats['lddt_min']:.4f}   "
-          f"residues below 0.7: {100.0 * stats['lddt_residues_below_0.7']:.1f} %   swapped symmetric residues: "
-          f"{stats['lddt_swapped_residues']}")
-    for k, v in stats.items():
-        print(k, v)
-    print("############## ^^^^^^^^^ lDDT")
-    return stats
-
-
-def compare_report(name, cmp):
-    """The printed summary of --compare for one output file (cmp: metrics.ensemble_compare's dict) -> the stats."""
-    stats = {"data_name": name, "compare_generated": cmp["n_a"], "compare_true": cmp["n_b"], "compare_r_max": cmp["r_max"],
-             "compare_js_dist_mean": float(cmp["js_dist_mean"]), "compare_js_dist_median": float(cmp["js_dist_median"]),
-             "compare_js_rg": float(cmp["js_rg"]), "compare_w1_rg": float(cmp["w1_rg"])}
-    line = (f"compare {name}: distance JS mean {stats['compare_js_dist_mean']:.4f} median {stats['compare_js_dist_median']:.4f}   "
-            f"Rg JS {stats['compare_js_rg']:.4f} W1 {stats['compare_w1_rg']:.3f} A")
-    if "js_torsion_mean" in cmp:
-        per = [float(v) for v in cmp["js_torsion_mean"].cpu()]
-        stats.update({f"compare_js_{n}": v for n, v in zip(metrics.TORSION_NAMES, per)})
-        line += "   torsion JS " + " ".join(f"{n} {v:.4f}" for n, v in zip(metrics.TORSION_NAMES, per))
-    else:
-        line += "   torsions skipped (the topology is not known, or the batch masks atoms)"
-    if "js_cluster" in cmp:
-        stats.update(compare_js_cluster=float(cmp["js_cluster"]), compare_clusters=cmp["n_clusters"])
-        line += f"   cluster JS {stats['compare_js_cluster']:.4f} ({cmp['n_clusters']} clusters)"
-    print("############## vvvvvvvvv generated against true ensemble (Jensen-Shannon divergences in bits, 0 = same distribution):")
-    print(line)
-    for k, v in stats.items():
-        print(k, v)
-    print("############## ^^^^^^^^^ generated against true ensemble")
-    return stats
 
 
 def pca_selection(name, n_atoms, atoms, ca):
@@ -455,60 +250,6 @@ def pca_selection(name, n_atoms, atoms, ca):
         raise SystemExit(f"--pca: {name} has 3 x {m} = {3 * m} coordinates over the chosen atoms, at most {metrics.PCA_MAX_DIM} "
                          f"(--pca_atoms ca runs over the CA atoms)")
     return sel
-
-
-def pca_report(name, pc):
-    """The printed summary of --pca for one output file (pc: metrics.pca's dict) -> the stats."""
-    ex = pc["explained"].cpu().numpy()
-    fl = pc["rmsf"].cpu().numpy()
-    stats = {"data_name": name, "structures": int(pc["finite"].shape[0]), "pca_non_finite": int((~pc["finite"]).sum()),
-             "pca_fit_iterations": int(pc["n_iter"]), "pca_fit_status": pc["status"], "pca_eig_iterations": int(pc["eig_iter"]),
-             "pca_eig_status": pc["eig_status"], "pca_total_variance": float(pc["total_variance"]),
-             "pca_explained_first3": [float(v) for v in ex[:3]], "rmsf_mean": float(fl.mean()), "rmsf_max": float(fl.max())}
-    print("############## vvvvvvvvv essential dynamics (mean structure, RMSF, PCA; A and A^2):")
-    print(f"fit in {stats['pca_fit_iterations']} iterations ({stats['pca_fit_status']})   total variance "
-          f"{stats['pca_total_variance']:.3f}   explained by the first three " +
-          " ".join(f"{v:.3f}" for v in stats["pca_explained_first3"]) +
-          f"   RMSF mean {stats['rmsf_mean']:.3f} max {stats['rmsf_max']:.3f}")
-    for k, v in stats.items():
-        print(k, v)
-    print("############## ^^^^^^^^^ essential dynamics")
-    return stats
-
-
-def cluster_report(name, cl):
-    """The printed summary of --cluster for one output file (cl: metrics.cluster's dict) -> the stats."""
-    pop = cl["populations"].cpu().numpy()
-    cr = cl["centre_rmsd"][cl["labels"] >= 0]
-    stats = {"data_name": name, "structures": int(cl["labels"].shape[0]), "cluster_non_finite": int((cl["labels"] < 0).sum()),
-             "clusters": int(cl["n_clusters"]), "cluster_top5_share": float(pop[:5].sum()) if pop.size else float("nan"),
-             "cluster_centre_rmsd_mean": float(cr.mean()) if cr.numel() else float("nan")}
-    print("############## vvvvvvvvv clustering (Daura / GROMOS; RMSD in A):")
-    print(f"{stats['clusters']} clusters of {stats['structures']} structures   share of the largest five "
-          f"{stats['cluster_top5_share']:.3f}   mean RMSD to the centre {stats['cluster_centre_rmsd_mean']:.3f}")
-    for k, v in stats.items():
-        print(k, v)
-    print("############## ^^^^^^^^^ clustering")
-    return stats
-
-
-def saxs_reweight_report(name, sx, data, thetas):
-    """--saxs_reweight for one output file: metrics.saxs_reweight of the profiles sx["I"] (hydrated under --saxs_hydration)
-    against `data` at every theta; prints the L-curve (chi^2 before and after, phi_eff, scale, status per theta) ->
-    (weights float64 numpy [n_theta, S], reweighted mean profiles [n_theta, N_Q], the stats)."""
-    rw = metrics.saxs_reweight(sx["I"], data[0], data[1], data[2], list(thetas), finite=sx["finite"])
-    col = {k: rw[k].cpu().numpy() for k in ("chi2_prior", "chi2", "phi_eff", "scale", "status", "n_iter", "rounds", "scale_converged")}
-    stats = {"data_name": name}
-    print("############## vvvvvvvvv SAXS reweighting (maximum entropy; chi^2 at the fitted scale, before -> after):")
-    for t, theta in enumerate(thetas):
-        status = metrics.REWEIGHT_STATUS[int(col["status"][t])] + ("" if col["scale_converged"][t] else ", scale not converged")
-        print(f"theta {theta:g}   chi2 {col['chi2_prior'][t]:.6g} -> {col['chi2'][t]:.6g}   phi_eff {col['phi_eff'][t]:.4f}   "
-              f"scale {col['scale'][t]:.6g}   {status} ({int(col['n_iter'][t])} Newton steps, {int(col['rounds'][t])} rounds)")
-        for k in ("chi2_prior", "chi2", "phi_eff", "scale"):
-            stats[f"saxs_reweight_{k}_theta{theta:g}"] = float(col[k][t])
-        stats[f"saxs_reweight_status_theta{theta:g}"] = int(col["status"][t])
-    print("############## ^^^^^^^^^ SAXS reweighting")
-    return rw["w"].cpu().numpy(), rw["mean"].cpu().numpy(), stats
 
 
 def read_saxs_data(path):
@@ -529,20 +270,6 @@ def read_saxs_data(path):
         raise SystemExit(f"--saxs_data {path}: two rows or more are needed")
     q, I, sigma = np.array(rows, dtype=np.float64).T
     return q, I, sigma
-
-
-def check_dssp(args):
-    """Where --dssp applies: exactly where --geometry_check does (structures are generated and their topology is known; the
-    refusals of --cg_pdb itself are check_cg_input's).  Returns whether it is on."""
-    on = bool(getattr(args, "dssp", False))
-    args.dssp = on
-    if on and not getattr(args, "cg_pdb", None):
-        if args.experiment in ("bpd", "fmloss"):
-            raise SystemExit(f"--dssp describes generated structures: --experiment {args.experiment} generates none")
-        if args.data_process and not args.synthetic:
-            raise SystemExit("--dssp needs the topology of the structures: --data_process pickles carry none "
-                             "(use --pdb_files, --cg_pdb or --synthetic)")
-    return on
 
 
 def check_sampler(args):
@@ -629,7 +356,7 @@ def fmloss_steps(args):
 def load_vae(args, device, load=True):
     """The VQ-VAE; with its e3nn encoder when the run needs it (`--experiment recon` encodes the batch's atoms, so does
     --fix_residues for the latents it pins and `--experiment bpd` for the latents it scores)."""
-    enc = args.experiment in ("recon", "bpd", "fmloss") or getattr(args, "fix_residues", None) is not None
+    enc = args.experiment in ("recon", "bpd", "fmloss") or args.fix_residues is not None
     if not load:
         return build_vae(args.vae_type, with_encoder=enc).to(device).eval()
     if args.synthetic_weights:
@@ -689,9 +416,7 @@ def iter_batches(args):
             plan = chunk_plan(args.synthetic_frames)
             names = [synth.IDX2THR[int(z)] for z in prot["z_full"]]
             geom_top = None
-            if getattr(args, "geometry_check", False) or getattr(args, "stereo_check", False) or getattr(args, "relax", 0) \
-                    or getattr(args, "observables", 0) or getattr(args, "dssp", False) or getattr(args, "saxs", 0) \
-                    or getattr(args, "pr", 0) or getattr(args, "compare", 0) or getattr(args, "lddt", False):
+            if any(row.topology and row.on(args) for row in (RELAX,) + ANALYSES):
                 from codlad_amd.utils.cg_input import template_topology
                 geom_top = template_topology(names[1:-1])             # one Topology (and one set of device tables) per protein
             for c, (a, b) in enumerate(plan):
@@ -703,7 +428,7 @@ def iter_batches(args):
                 # the encoder reads the all-atom side of the batch (recon; the known latents of --fix_residues); --compare and
                 # --lddt its true coordinates
                 if getattr(args, "experiment", "latent") in ("recon", "bpd", "fmloss") or getattr(args, "fix_residues", None) is not None \
-                        or getattr(args, "compare", 0) or getattr(args, "lddt", False):
+                        or any(row.truth and row.on(args) for row in ANALYSES):
                     batch.update(synth.make_atoms(prot, range(a, b), seed=1000 + i))
                 yield out, batch, prot["info"]
         return
@@ -791,46 +516,8 @@ class Evaluation:
                  "test_inter": mean("loss_inter"), "test_pi_pi": mean("loss_pi_pi"),
                  "test_all_valid_ratio": float(np.mean(self.valid)), "test_all_ged": float(np.mean(self.ged)),
                  "diversity": metrics.compute_div(self.recon, self.true) if len(self.recon) > 1 else 0}
-        print("############## vvvvvvvvv result test_stats:")
-        for k, v in stats.items():
-            print(k, v)
-        print("############## ^^^^^^^^^ result test_stats:")
+        print_frame("result test_stats:", (), stats, "result test_stats:")
         return stats
-
-
-def geometry_report(name, geo, n_atoms):
-    """The printed summary of --geometry_check for one output file (geo: metrics.geometry_check's dict) -> the stats."""
-    c = geo["counts"].to(torch.float64)
-    near = c[:, 3]
-    ratio = torch.where(near > 0, c[:, 4] / near.clamp(min=1), torch.zeros_like(near))
-    stats = {"data_name": name, "structures": int(c.shape[0]), "atoms": int(n_atoms),
-             "geometry_valid_ratio": float(geo["valid"].to(torch.float64).mean()),          # non-finite ones are not valid
-             "geometry_non_finite": int(torch.isnan(geo["min_dist"]).sum()),
-             "geometry_broken_bonds": float(c[:, 0].mean()), "geometry_spurious_bonds": float(c[:, 1].mean()),
-             "geometry_clashes": float(c[:, 4].mean()), "geometry_clash_over_near": float(ratio.mean()),
-             "geometry_min_dist": float(geo["min_dist"].min())}
-    print("############## vvvvvvvvv geometry check (template topology, no true structure):")
-    for k, v in stats.items():
-        print(k, v)
-    print("############## ^^^^^^^^^ geometry check")
-    return stats
-
-
-def stereo_report(name, ste):
-    """The printed summary of --stereo_check for one output file (ste: metrics.stereo_check's dict) -> the stats."""
-    c = ste["counts"].to(torch.int64)
-    bad = c.sum(1) - c[:, metrics.STEREO_COUNTS.index("cis_pro")]                # what fails stereo_ok, per structure
-    worst = int(bad.argmax())
-    stats = {"data_name": name, "structures": int(c.shape[0]), "residues": int(ste["flags"].shape[1]),
-             "stereo_ok_ratio": float(ste["stereo_ok"].to(torch.float64).mean())}
-    stats.update({f"stereo_total_{k}": int(c[:, i].sum()) for i, k in enumerate(metrics.STEREO_COUNTS)})
-    stats["stereo_worst_structure"] = worst
-    stats["stereo_worst_counts"] = " ".join(f"{k}={int(c[worst, i])}" for i, k in enumerate(metrics.STEREO_COUNTS))
-    print("############## vvvvvvvvv stereo check (chirality, peptide bonds; geometry, not accuracy):")
-    for k, v in stats.items():
-        print(k, v)
-    print("############## ^^^^^^^^^ stereo check")
-    return stats
 
 
 CA_CONTACT_CUTOFF = 8.0            # A: the usual CA contact definition of --observables
@@ -844,27 +531,6 @@ def observables(xyz, top, n_points):
         raise SystemExit("--observables: the topology has no CA atoms")
     return dict(sasa=metrics.sasa(xyz, top, n_points=n_points), rg=metrics.radius_of_gyration(xyz),
                 contacts=metrics.contact_map(xyz, sel=ca, cutoff=CA_CONTACT_CUTOFF))
-
-
-def observables_report(name, obs):
-    """The printed summary of --observables for one output file -> the stats."""
-    def mean_sd(t):
-        t = t.to(torch.float64)
-        return float(t.mean()), float(t.std(unbiased=False))
-
-    fin = obs["sasa"]["finite"]
-    stats = {"data_name": name, "structures": int(fin.shape[0]), "observables_non_finite": int((~fin).sum())}
-    for key, t in (("rg", obs["rg"]), ("sasa_total", obs["sasa"]["total"])):
-        t = t[fin]
-        stats[f"{key}_mean"], stats[f"{key}_sd"] = mean_sd(t) if t.numel() else (float("nan"), float("nan"))
-    freq = obs["contacts"]["frequency"]
-    stats["ca_contacts_per_residue"] = float(freq.sum() / freq.shape[0])
-    print("############## vvvvvvvvv ensemble observables (SASA in A^2, Rg in A, CA contacts at 8 A):")
-    print(f"Rg {stats['rg_mean']:.3f} +- {stats['rg_sd']:.3f}   SASA {stats['sasa_total_mean']:.1f} +- {stats['sasa_total_sd']:.1f}")
-    for k, v in stats.items():
-        print(k, v)
-    print("############## ^^^^^^^^^ ensemble observables")
-    return stats
 
 
 def saxs_hydrated(xyz, top, q, hydration, data=None):
@@ -886,63 +552,6 @@ def saxs_hydrated(xyz, top, q, hydration, data=None):
     combine = lambda P: metrics.saxs_combine(P, hp["q"], hp["water"], c1, c2)                    # noqa: E731
     return dict(q=hp["q"], I=combine(hp["P"]), mean=combine(hp["mean"]), finite=hp["finite"], n_finite=hp["n_finite"],
                 partials=hp["P"], hydration=info)
-
-
-def saxs_report(name, sx, data=None):
-    """The printed summary of --saxs for one output file (sx: metrics.saxs_profile's dict, or saxs_hydrated's; data:
-    read_saxs_data's curve on the same q grid, or None) -> the stats."""
-    q, mean = sx["q"].cpu().numpy(), sx["mean"].cpu().numpy()
-    fin = sx["finite"]
-    stats = {"data_name": name, "structures": int(fin.shape[0]), "saxs_non_finite": int((~fin).sum()), "saxs_I0": float(mean[0])}
-    picks = sorted({len(q) // 4, len(q) // 2, len(q) - 1})
-    for k in picks:
-        stats[f"saxs_mean_q{float(q[k]):.4f}"] = float(mean[k])
-    if data is not None and "saxs_scale" not in sx.get("hydration", {}):
-        fit = metrics.saxs_fit(sx["mean"], data[0], data[1], data[2])
-        stats["saxs_scale"], stats["saxs_chi2"] = float(fit["scale"]), float(fit["chi2"])
-    stats.update(sx.get("hydration", {}))
-    print("############## vvvvvvvvv SAXS profile (Debye sum, ensemble mean; q in 1/A):")
-    print(f"I({float(q[0]):.4f}) {stats['saxs_I0']:.6g}   " + "   ".join(f"I({float(q[k]):.4f}) {float(mean[k]):.6g}" for k in picks))
-    for k, v in stats.items():
-        print(k, v)
-    print("############## ^^^^^^^^^ SAXS profile")
-    return stats
-
-
-def pr_report(name, pr):
-    """The printed summary of --pr for one output file (pr: metrics.pair_distribution's dict) -> the stats."""
-    fin = pr["finite"]
-    d_max, rg = pr["d_max"][fin].cpu().numpy(), pr["rg"][fin].cpu().numpy()
-    msd = lambda v: (float(v.mean()), float(v.std())) if v.size else (float("nan"), float("nan"))    # noqa: E731
-    stats = {"data_name": name, "structures": int(fin.shape[0]), "pr_non_finite": int((~fin).sum()),
-             "pr_overflow": int(pr["overflow"].sum()), "pr_bins": int(pr["r"].shape[0]),
-             "pr_d_max_mean": msd(d_max)[0], "pr_d_max_sd": msd(d_max)[1], "pr_rg_mean": msd(rg)[0], "pr_rg_sd": msd(rg)[1]}
-    print("############## vvvvvvvvv pair distribution P(r) (typed pair-distance histogram; A):")
-    print(f"D_max {stats['pr_d_max_mean']:.2f} +- {stats['pr_d_max_sd']:.2f}   Rg {stats['pr_rg_mean']:.3f} +- "
-          f"{stats['pr_rg_sd']:.3f}   structures with overflow {stats['pr_overflow']}")
-    for k, v in stats.items():
-        print(k, v)
-    print("############## ^^^^^^^^^ pair distribution P(r)")
-    return stats
-
-
-def dssp_report(name, sec, propensity):
-    """The printed summary of --dssp for one output file (sec: metrics.dssp's dict, propensity: metrics.ss_propensity of its
-    labels) -> the stats: the mean share of helix (H + G + I), strand (E + B) and coil (the rest) over residues and finite
-    structures."""
-    fin = sec["finite"]
-    stats = {"data_name": name, "structures": int(fin.shape[0]), "dssp_non_finite": int((~fin).sum())}
-    share = propensity.mean(dim=0)                                                  # [8]: NaN when no structure is finite
-    codes = {c: i for i, c in enumerate(metrics.DSSP_CODES)}
-    stats["helix"] = float(share[codes["H"]] + share[codes["G"]] + share[codes["I"]])
-    stats["strand"] = float(share[codes["E"]] + share[codes["B"]])
-    stats["coil"] = float(share[codes[" "]] + share[codes["T"]] + share[codes["S"]])
-    print("############## vvvvvvvvv secondary structure (DSSP, mean share of residues):")
-    print(f"helix {stats['helix']:.3f}   strand {stats['strand']:.3f}   coil {stats['coil']:.3f}")
-    for k, v in stats.items():
-        print(k, v)
-    print("############## ^^^^^^^^^ secondary structure")
-    return stats
 
 
 def ca_indices(topology):
@@ -977,6 +586,453 @@ def superpose_models(xyz, mode, ref=None, sel=None):
     return metrics.superpose(xyz.reshape(-1, n, 3), ref.repeat(E, 1, 1), sel=sel).reshape(E, B, n, 3).to(xyz.dtype)
 
 
+def print_frame(opening, headline, stats, closing):
+    """One printed report: the opening title, the headline lines, every statistic on a line of its own, the closing title."""
+    print(f"############## vvvvvvvvv {opening}")
+    for line in headline:
+        print(line)
+    for k, v in stats.items():
+        print(k, v)
+    print(f"############## ^^^^^^^^^ {closing}")
+
+
+def save_arrays(save_dir, name, files):
+    """<save_dir>/<name>_<suffix>.npy for every (suffix, device tensor or array) of `files`; None is not written."""
+    for suffix, a in files:
+        if a is not None:
+            np.save(os.path.join(save_dir, f"{name}_{suffix}.npy"), a.cpu().numpy() if torch.is_tensor(a) else a)
+
+
+def positive(v):
+    return bool(np.isfinite(v) and v > 0)
+
+
+class Written:
+    """The coordinates one batch writes, as the rows of ANALYSES read them."""
+
+    def __init__(self, args, name, batch, xyz, saxs_data):
+        self.args, self.name, self.batch, self.saxs_data = args, name, batch, saxs_data
+        self.xyz = xyz                                           # [E, B, n_atoms, 3]
+        self.n_atoms = xyz.shape[2]
+        self.pool = xyz.reshape(-1, self.n_atoms, 3)             # [E * B, n_atoms, 3]: members x frames, one pool
+
+    def ca(self):
+        """The CA atoms among the written ones, None where the input route does not name the atoms."""
+        return ca_indices(_TOPOLOGY[self.name]) if self.name in _TOPOLOGY else None
+
+    def truth(self, flag):
+        return compare_truth(self.name, self.batch, flag).reshape(-1, self.n_atoms, 3)
+
+
+class Analysis:
+    """One analysis of the written coordinates: everything the script knows about it.  The class attributes say which flag
+    it belongs to and what it needs of the input route; from them follow its scope refusals (refuse_out_of_scope), whether
+    the synthetic route builds a Topology and the true atoms (iter_batches) and the per-file refusal where the topology is
+    not known (topology_of)."""
+    flag = None              # "--geometry_check": args.geometry_check holds its value
+    does = None              # the verb of its scope refusals
+    topology = None          # REQUIRED, USED (when the input route knows one) or None
+    late = False             # True: the check lets the pickle route pass, topology_of refuses it file by file
+    truth = False            # True: it reads the true frames of the batch
+    takes = None             # (what a value must be, in the refusal's words; value -> bool)
+    off = False              # what the check leaves in args, and returns, when the flag was not given
+    writes = ()              # (file suffix, result -> device tensor, array or None = not this time): <name>_<suffix>.npy
+
+    def value(self, args):
+        """What the command line gave: the one place that puts up with a namespace that lacks the attribute."""
+        return getattr(args, self.flag[2:], None)
+
+    def on(self, args):
+        return bool(self.value(args))
+
+    def check(self, args):
+        """Refuses a value out of range and a run it does not apply to; normalises args.<flag> and returns it."""
+        v = self.value(args)
+        if v is None or v is False:
+            setattr(args, self.flag[2:], self.off)
+            return self.off
+        if self.takes and not self.takes[1](v):
+            raise SystemExit(f"{self.flag} takes {self.takes[0]}, got {v}")
+        refuse_out_of_scope(args, self)
+        return v
+
+    def run(self, w, top):
+        """Launches the analysis on w.pool (top: topology_of's answer) -> its result dict, still on the device."""
+        raise NotImplementedError
+
+    def report(self, w, res):
+        """-> print_frame's arguments: opening title, headline lines, statistics, closing title."""
+        raise NotImplementedError
+
+    def extras(self, w, res, save_dir):
+        """What follows the report, outside the timed span."""
+
+
+class Relax(Analysis):
+    """--relax N is no row of ANALYSES: it changes the coordinates the rows read (relax_structures).  It is allowed exactly
+    where a row that requires the topology is, so its check is a row's; 0 = off."""
+    flag, does, topology, off = "--relax", "relaxes generated structures", REQUIRED, 0
+    takes = "a number of iterations >= 0", lambda n: n >= 0
+
+
+class Geometry(Analysis):
+    """--geometry_check: every member of every frame against the template bond graph, one launch."""
+    flag, does, topology = "--geometry_check", "judges generated structures", REQUIRED
+    check = staticmethod(check_cg_input)                         # implied by --cg_pdb: the input route's check holds it
+    writes = (("geometry", lambda geo: geo["counts"]),           # [E * B, 5]
+              ("geometry_min", lambda geo: geo["min_dist"]))
+
+    def run(self, w, top):
+        return metrics.geometry_check(w.pool, top, order=w.args.edgeorder, near_dist=w.args.atom_cutoff)
+
+    def report(self, w, geo):
+        c = geo["counts"].to(torch.float64)
+        near = c[:, 3]
+        ratio = torch.where(near > 0, c[:, 4] / near.clamp(min=1), torch.zeros_like(near))
+        stats = {"data_name": w.name, "structures": int(c.shape[0]), "atoms": int(w.n_atoms),
+                 "geometry_valid_ratio": float(geo["valid"].to(torch.float64).mean()),          # non-finite ones are not valid
+                 "geometry_non_finite": int(torch.isnan(geo["min_dist"]).sum()),
+                 "geometry_broken_bonds": float(c[:, 0].mean()), "geometry_spurious_bonds": float(c[:, 1].mean()),
+                 "geometry_clashes": float(c[:, 4].mean()), "geometry_clash_over_near": float(ratio.mean()),
+                 "geometry_min_dist": float(geo["min_dist"].min())}
+        return "geometry check (template topology, no true structure):", (), stats, "geometry check"
+
+
+class Stereo(Analysis):
+    """--stereo_check: what the covalent graph cannot see, one launch."""
+    flag, does, topology = "--stereo_check", "judges generated structures", REQUIRED
+    writes = (("stereo", lambda ste: ste["counts"]),             # [E * B, 6]
+              ("stereo_flags", lambda ste: ste["flags"]),        # [E * B, R]
+              ("torsions", lambda ste: ste["values"]))           # [E * B, R, 9]
+
+    def run(self, w, top):
+        return metrics.stereo_check(w.pool, top)
+
+    def report(self, w, ste):
+        c = ste["counts"].to(torch.int64)
+        bad = c.sum(1) - c[:, metrics.STEREO_COUNTS.index("cis_pro")]                # what fails stereo_ok, per structure
+        worst = int(bad.argmax())
+        stats = {"data_name": w.name, "structures": int(c.shape[0]), "residues": int(ste["flags"].shape[1]),
+                 "stereo_ok_ratio": float(ste["stereo_ok"].to(torch.float64).mean())}
+        stats.update({f"stereo_total_{k}": int(c[:, i].sum()) for i, k in enumerate(metrics.STEREO_COUNTS)})
+        stats["stereo_worst_structure"] = worst
+        stats["stereo_worst_counts"] = " ".join(f"{k}={int(c[worst, i])}" for i, k in enumerate(metrics.STEREO_COUNTS))
+        return "stereo check (chirality, peptide bonds; geometry, not accuracy):", (), stats, "stereo check"
+
+
+class Observables(Analysis):
+    """--observables N_POINTS: SASA with N_POINTS test points per atom, Rg, CA contacts; 0 = off."""
+    flag, does, topology, off = "--observables", "describes generated structures", REQUIRED, 0
+    takes = f"a number of test points per atom in 1 .. {metrics.SASA_MAX_POINTS}", lambda n: 1 <= n <= metrics.SASA_MAX_POINTS
+    writes = (("sasa_residue", lambda obs: obs["sasa"]["residue"]),          # [E * B, R]
+              ("rg", lambda obs: obs["rg"]),                                 # [E * B]
+              ("ca_contacts", lambda obs: obs["contacts"]["frequency"]))     # [R, R]
+
+    def run(self, w, top):
+        return observables(w.pool, top, w.args.observables)
+
+    def report(self, w, obs):
+        def mean_sd(t):
+            t = t.to(torch.float64)
+            return float(t.mean()), float(t.std(unbiased=False))
+
+        fin = obs["sasa"]["finite"]
+        stats = {"data_name": w.name, "structures": int(fin.shape[0]), "observables_non_finite": int((~fin).sum())}
+        for key, t in (("rg", obs["rg"]), ("sasa_total", obs["sasa"]["total"])):
+            t = t[fin]
+            stats[f"{key}_mean"], stats[f"{key}_sd"] = mean_sd(t) if t.numel() else (float("nan"), float("nan"))
+        freq = obs["contacts"]["frequency"]
+        stats["ca_contacts_per_residue"] = float(freq.sum() / freq.shape[0])
+        line = f"Rg {stats['rg_mean']:.3f} +- {stats['rg_sd']:.3f}   SASA {stats['sasa_total_mean']:.1f} +- {stats['sasa_total_sd']:.1f}"
+        return "ensemble observables (SASA in A^2, Rg in A, CA contacts at 8 A):", (line,), stats, "ensemble observables"
+
+
+class Saxs(Analysis):
+    """--saxs N_Q: the Debye profile of every structure on N_Q points, or on the q grid of --saxs_data; 0 = off.  With
+    --saxs_hydration the hydrated profiles; --saxs_reweight follows the report, outside the timed span."""
+    flag, does, topology, off = "--saxs", "describes generated structures", REQUIRED, 0
+    takes = f"a number of q values in 1 .. {metrics.SAXS_MAX_Q}", lambda n: 1 <= n <= metrics.SAXS_MAX_Q
+    writes = (("saxs", lambda sx: sx["I"]),                              # float64 [E * B, N_Q]
+              ("saxs_q", lambda sx: sx["q"]),                            # float32 [N_Q]
+              ("saxs_partials", lambda sx: sx.get("partials")),          # float64 [E * B, 6, N_Q]
+              ("saxs_weights", lambda sx: sx.get("weights")),            # float64 [n_theta, E * B]
+              ("saxs_reweighted", lambda sx: sx.get("reweighted")))      # float64 [n_theta, N_Q]
+
+    def check(self, args):
+        if self.value(args) is None and getattr(args, "saxs_data", None):
+            raise SystemExit("--saxs_data needs --saxs: the curve is compared with the profile --saxs computes")
+        return super().check(args)
+
+    def run(self, w, top):
+        q = w.saxs_data[0] if w.saxs_data is not None else np.linspace(0.0, 0.5, w.args.saxs)
+        if w.args.saxs_hydration is not None:
+            return saxs_hydrated(w.pool, top, q, w.args.saxs_hydration, w.saxs_data)
+        return metrics.saxs_profile(w.pool, top, q=q)
+
+    def report(self, w, sx):
+        q, mean = sx["q"].cpu().numpy(), sx["mean"].cpu().numpy()
+        fin, data = sx["finite"], w.saxs_data
+        stats = {"data_name": w.name, "structures": int(fin.shape[0]), "saxs_non_finite": int((~fin).sum()), "saxs_I0": float(mean[0])}
+        picks = sorted({len(q) // 4, len(q) // 2, len(q) - 1})
+        for k in picks:
+            stats[f"saxs_mean_q{float(q[k]):.4f}"] = float(mean[k])
+        if data is not None and "saxs_scale" not in sx.get("hydration", {}):
+            fit = metrics.saxs_fit(sx["mean"], data[0], data[1], data[2])
+            stats["saxs_scale"], stats["saxs_chi2"] = float(fit["scale"]), float(fit["chi2"])
+        stats.update(sx.get("hydration", {}))
+        line = f"I({float(q[0]):.4f}) {stats['saxs_I0']:.6g}   " + "   ".join(f"I({float(q[k]):.4f}) {float(mean[k]):.6g}" for k in picks)
+        return "SAXS profile (Debye sum, ensemble mean; q in 1/A):", (line,), stats, "SAXS profile"
+
+    def extras(self, w, sx, save_dir):
+        """--saxs_reweight: metrics.saxs_reweight of the profiles sx["I"] (hydrated under --saxs_hydration) against the curve
+        at every theta; prints the L-curve (chi^2 before and after, phi_eff, scale, status per theta) and leaves the weights
+        [n_theta, S] and the reweighted mean profiles [n_theta, N_Q] in sx."""
+        thetas, data = w.args.saxs_reweight, w.saxs_data
+        if not thetas:
+            return
+        rw = metrics.saxs_reweight(sx["I"], data[0], data[1], data[2], list(thetas), finite=sx["finite"])
+        col = {k: rw[k].cpu().numpy() for k in ("chi2_prior", "chi2", "phi_eff", "scale", "status", "n_iter", "rounds", "scale_converged")}
+        lines = []
+        for t, theta in enumerate(thetas):
+            status = metrics.REWEIGHT_STATUS[int(col["status"][t])] + ("" if col["scale_converged"][t] else ", scale not converged")
+            lines.append(f"theta {theta:g}   chi2 {col['chi2_prior'][t]:.6g} -> {col['chi2'][t]:.6g}   phi_eff {col['phi_eff'][t]:.4f}   "
+                         f"scale {col['scale'][t]:.6g}   {status} ({int(col['n_iter'][t])} Newton steps, {int(col['rounds'][t])} rounds)")
+        print_frame("SAXS reweighting (maximum entropy; chi^2 at the fitted scale, before -> after):", lines, {}, "SAXS reweighting")
+        sx["weights"], sx["reweighted"] = rw["w"].cpu().numpy(), rw["mean"].cpu().numpy()
+
+
+class PairDistribution(Analysis):
+    """--pr DR: the typed pair-distance histogram in bins of DR A; 0 = off."""
+    flag, does, topology, off = "--pr", "describes generated structures", REQUIRED, 0.0
+    takes = "a bin width in A, a positive number", positive
+    writes = (("pr", lambda pr: pr["P"]),                                # float64 [E * B, BINS]
+              ("pr_r", lambda pr: pr["r"]))                              # float64 [BINS]
+
+    def run(self, w, top):
+        try:
+            return metrics.pair_distribution(w.pool, top, dr=w.args.pr)
+        except ValueError as e:                               # more bins than the kernel holds: a wider bin is the way out
+            raise SystemExit(f"--pr {w.args.pr}: {e}") from None
+
+    def report(self, w, pr):
+        fin = pr["finite"]
+        d_max, rg = pr["d_max"][fin].cpu().numpy(), pr["rg"][fin].cpu().numpy()
+        msd = lambda v: (float(v.mean()), float(v.std())) if v.size else (float("nan"), float("nan"))    # noqa: E731
+        stats = {"data_name": w.name, "structures": int(fin.shape[0]), "pr_non_finite": int((~fin).sum()),
+                 "pr_overflow": int(pr["overflow"].sum()), "pr_bins": int(pr["r"].shape[0]),
+                 "pr_d_max_mean": msd(d_max)[0], "pr_d_max_sd": msd(d_max)[1], "pr_rg_mean": msd(rg)[0], "pr_rg_sd": msd(rg)[1]}
+        line = (f"D_max {stats['pr_d_max_mean']:.2f} +- {stats['pr_d_max_sd']:.2f}   Rg {stats['pr_rg_mean']:.3f} +- "
+                f"{stats['pr_rg_sd']:.3f}   structures with overflow {stats['pr_overflow']}")
+        return "pair distribution P(r) (typed pair-distance histogram; A):", (line,), stats, "pair distribution P(r)"
+
+
+class Cluster(Analysis):
+    """--cluster CUTOFF: Daura / GROMOS clusters at the RMSD CUTOFF in A over --cluster_atoms; 0 = off."""
+    flag, does, off = "--cluster", "describes generated structures", 0.0
+    takes = "an RMSD cut-off in A, a positive number", positive
+    writes = (("cluster_labels", lambda cl: cl["labels"]),               # int32 [E * B], -1 = not finite
+              ("cluster_centres", lambda cl: cl["centres"]),             # int32 [K]: indices into the pool
+              ("cluster_sizes", lambda cl: cl["sizes"]))                 # int32 [K]
+
+    def run(self, w, top):
+        sel = None
+        if w.args.cluster_atoms == "ca":
+            sel = w.ca()
+            if not sel:
+                raise SystemExit(f"--cluster: the CA atoms of {w.name} are not known on this input route (use --cluster_atoms all)")
+        return metrics.cluster(w.pool, w.args.cluster, sel=sel)
+
+    def report(self, w, cl):
+        pop = cl["populations"].cpu().numpy()
+        cr = cl["centre_rmsd"][cl["labels"] >= 0]
+        stats = {"data_name": w.name, "structures": int(cl["labels"].shape[0]), "cluster_non_finite": int((cl["labels"] < 0).sum()),
+                 "clusters": int(cl["n_clusters"]), "cluster_top5_share": float(pop[:5].sum()) if pop.size else float("nan"),
+                 "cluster_centre_rmsd_mean": float(cr.mean()) if cr.numel() else float("nan")}
+        line = (f"{stats['clusters']} clusters of {stats['structures']} structures   share of the largest five "
+                f"{stats['cluster_top5_share']:.3f}   mean RMSD to the centre {stats['cluster_centre_rmsd_mean']:.3f}")
+        return "clustering (Daura / GROMOS; RMSD in A):", (line,), stats, "clustering"
+
+    def extras(self, w, cl, save_dir):
+        if w.args.save_pdb and w.name in _TOPOLOGY and cl["n_clusters"]:
+            from codlad_amd.utils.protein_module import write_pdb
+            centres = w.pool[cl["centres"].to(torch.int64)].cpu().numpy()
+            write_pdb(os.path.join(save_dir, f"cluster_centres_{w.name}.pdb"), centres, *_TOPOLOGY[w.name])
+
+
+class Pca(Analysis):
+    """--pca K: mean structure, RMSF and the K largest principal components over --pca_atoms; 0 = off."""
+    flag, does, off = "--pca", "describes generated structures", 0
+    takes = "the number of components, 1 .. 64", lambda k: 1 <= k <= 64
+    writes = (("pca_mean", lambda pc: pc["mean"]),                       # float64 [m, 3]
+              ("pca_eigenvalues", lambda pc: pc["eigenvalues"]),         # float64 [K], descending
+              ("pca_components", lambda pc: pc["components"]),           # float64 [K, m, 3]
+              ("pca_projections", lambda pc: pc["projections"]),         # float64 [E * B, K]
+              ("rmsf", lambda pc: pc["rmsf"]))                           # float64 [m]
+
+    def run(self, w, top):
+        sel = pca_selection(w.name, w.n_atoms, w.args.pca_atoms, w.ca())
+        pc = metrics.pca(w.pool, n_components=min(w.args.pca, 3 * (len(sel) if sel else w.n_atoms)), sel=sel)
+        return dict(pc, sel=sel)
+
+    def report(self, w, pc):
+        ex = pc["explained"].cpu().numpy()
+        fl = pc["rmsf"].cpu().numpy()
+        stats = {"data_name": w.name, "structures": int(pc["finite"].shape[0]), "pca_non_finite": int((~pc["finite"]).sum()),
+                 "pca_fit_iterations": int(pc["n_iter"]), "pca_fit_status": pc["status"], "pca_eig_iterations": int(pc["eig_iter"]),
+                 "pca_eig_status": pc["eig_status"], "pca_total_variance": float(pc["total_variance"]),
+                 "pca_explained_first3": [float(v) for v in ex[:3]], "rmsf_mean": float(fl.mean()), "rmsf_max": float(fl.max())}
+        line = (f"fit in {stats['pca_fit_iterations']} iterations ({stats['pca_fit_status']})   total variance "
+                f"{stats['pca_total_variance']:.3f}   explained by the first three " +
+                " ".join(f"{v:.3f}" for v in stats["pca_explained_first3"]) +
+                f"   RMSF mean {stats['rmsf_mean']:.3f} max {stats['rmsf_max']:.3f}")
+        return "essential dynamics (mean structure, RMSF, PCA; A and A^2):", (line,), stats, "essential dynamics"
+
+    def extras(self, w, pc, save_dir):
+        if w.args.save_pdb and w.name in _TOPOLOGY and pc["sel"] is None:
+            from codlad_amd.utils.protein_module import write_pdb
+            write_pdb(os.path.join(save_dir, f"pca_mean_{w.name}.pdb"), pc["mean"].cpu().numpy()[None].astype(np.float32),
+                      *_TOPOLOGY[w.name])
+
+
+class Compare(Analysis):
+    """--compare N_BINS: the written structures as one ensemble against the file's true frames; the torsions only where
+    the topology is known and the batch masks no atom; --compare_cluster CUTOFF adds the cluster populations; 0 = off."""
+    flag, does, topology, truth, off = "--compare", "compares generated structures with the true ones", USED, True, 0
+    takes = f"the number of distance bins, 1 .. {metrics.COMPARE_MAX_BINS}", lambda k: 1 <= k <= metrics.COMPARE_MAX_BINS
+    writes = (("compare_js_dist", lambda cmp: cmp["js_dist"]),               # float64 [R, R]
+              ("compare_js_torsion", lambda cmp: cmp.get("js_torsion")))     # float64 [R, 7]
+
+    def check(self, args):
+        c = getattr(args, "compare_cluster", None)
+        if c is not None and not positive(c):
+            raise SystemExit(f"--compare_cluster takes an RMSD cut-off in A, a positive number, got {c}")
+        if c is not None and self.value(args) is None:
+            raise SystemExit("--compare_cluster needs --compare")
+        return super().check(args)
+
+    def run(self, w, top):
+        truth = w.truth("--compare")
+        sel = w.ca()
+        if not sel or len(sel) < 2:
+            raise SystemExit(f"--compare: the CA atoms of {w.name} are not known on this input route")
+        top = top if top is not None and compare_no_atom_masked(w.batch) else None
+        return metrics.ensemble_compare(w.pool, truth, top=top, sel=sel, n_bins=w.args.compare, cluster_cutoff=w.args.compare_cluster)
+
+    def report(self, w, cmp):
+        stats = {"data_name": w.name, "compare_generated": cmp["n_a"], "compare_true": cmp["n_b"], "compare_r_max": cmp["r_max"],
+                 "compare_js_dist_mean": float(cmp["js_dist_mean"]), "compare_js_dist_median": float(cmp["js_dist_median"]),
+                 "compare_js_rg": float(cmp["js_rg"]), "compare_w1_rg": float(cmp["w1_rg"])}
+        line = (f"compare {w.name}: distance JS mean {stats['compare_js_dist_mean']:.4f} median {stats['compare_js_dist_median']:.4f}   "
+                f"Rg JS {stats['compare_js_rg']:.4f} W1 {stats['compare_w1_rg']:.3f} A")
+        if "js_torsion_mean" in cmp:
+            per = [float(v) for v in cmp["js_torsion_mean"].cpu()]
+            stats.update({f"compare_js_{n}": v for n, v in zip(metrics.TORSION_NAMES, per)})
+            line += "   torsion JS " + " ".join(f"{n} {v:.4f}" for n, v in zip(metrics.TORSION_NAMES, per))
+        else:
+            line += "   torsions skipped (the topology is not known, or the batch masks atoms)"
+        if "js_cluster" in cmp:
+            stats.update(compare_js_cluster=float(cmp["js_cluster"]), compare_clusters=cmp["n_clusters"])
+            line += f"   cluster JS {stats['compare_js_cluster']:.4f} ({cmp['n_clusters']} clusters)"
+        return ("generated against true ensemble (Jensen-Shannon divergences in bits, 0 = same distribution):", (line,), stats,
+                "generated against true ensemble")
+
+
+class Lddt(Analysis):
+    """--lddt: member k of frame f against true frame f; atoms the batch masks in a frame take no part."""
+    flag, does, topology, truth = "--lddt", "scores generated structures against the true ones", REQUIRED, True
+    late = True                                                          # as ever
+    writes = (("lddt", lambda ld: ld["global"]),                         # float64 [E * B]
+              ("lddt_residue", lambda ld: ld["residue"]))                # float64 [E * B, R]
+
+    def run(self, w, top):
+        truth = w.truth("--lddt")
+        return metrics.lddt(w.pool, truth, top, ref_index=torch.arange(truth.shape[0]).repeat(w.xyz.shape[0]),
+                            sel=lddt_selection(w.batch, truth.shape[0], w.n_atoms))
+
+    def report(self, w, ld):
+        g, res = ld["global"].cpu().numpy(), ld["residue"].cpu().numpy()
+        scored = res[~np.isnan(res)]
+        stats = {"data_name": w.name, "lddt_mean": float(np.nanmean(g)), "lddt_median": float(np.nanmedian(g)), "lddt_min": float(np.nanmin(g)),
+                 "lddt_residues_below_0.7": float((scored < 0.7).mean()) if scored.size else float("nan"),
+                 "lddt_swapped_residues": int(ld["swapped"].sum()), "lddt_not_finite": int((~ld["finite"]).sum())}
+        line = (f"lddt {w.name}: global mean {stats['lddt_mean']:.4f} median {stats['lddt_median']:.4f} min {stats['lddt_min']:.4f}   "
+                f"residues below 0.7: {100.0 * stats['lddt_residues_below_0.7']:.1f} %   swapped symmetric residues: "
+                f"{stats['lddt_swapped_residues']}")
+        return "lDDT of the generated structures against their true frames (1 = every local distance kept):", (line,), stats, "lDDT"
+
+
+class Dssp(Analysis):
+    """--dssp: the DSSP state of every residue of every structure, and the share of each state per residue."""
+    flag, does, topology = "--dssp", "describes generated structures", REQUIRED
+    writes = (("dssp", lambda sec: sec["ss"]),                           # uint8 [E * B, R]
+              ("dssp_propensity", lambda sec: sec["propensity"]))        # float64 [R, 8]
+
+    def run(self, w, top):
+        sec = metrics.dssp(w.pool, top)
+        return dict(sec, propensity=metrics.ss_propensity(sec["ss"]))
+
+    def report(self, w, sec):
+        """The mean share of helix (H + G + I), strand (E + B) and coil (the rest) over residues and finite structures."""
+        fin = sec["finite"]
+        stats = {"data_name": w.name, "structures": int(fin.shape[0]), "dssp_non_finite": int((~fin).sum())}
+        share = sec["propensity"].mean(dim=0)                                       # [8]: NaN when no structure is finite
+        codes = {c: i for i, c in enumerate(metrics.DSSP_CODES)}
+        stats["helix"] = float(share[codes["H"]] + share[codes["G"]] + share[codes["I"]])
+        stats["strand"] = float(share[codes["E"]] + share[codes["B"]])
+        stats["coil"] = float(share[codes[" "]] + share[codes["T"]] + share[codes["S"]])
+        line = f"helix {stats['helix']:.3f}   strand {stats['strand']:.3f}   coil {stats['coil']:.3f}"
+        return "secondary structure (DSSP, mean share of residues):", (line,), stats, "secondary structure"
+
+
+RELAX = Relax()
+GEOMETRY, STEREO, OBSERVABLES, SAXS, PR = Geometry(), Stereo(), Observables(), Saxs(), PairDistribution()
+CLUSTER, PCA, COMPARE, LDDT, DSSP = Cluster(), Pca(), Compare(), Lddt(), Dssp()
+# the order of the launches before a batch's synchronisation, and of what is written and printed after it
+ANALYSES = (GEOMETRY, STEREO, OBSERVABLES, SAXS, PR, CLUSTER, PCA, COMPARE, LDDT, DSSP)
+
+# the checks by the names they have always had (check_cg_input is --geometry_check's)
+check_stereo, check_relax, check_observables, check_saxs, check_pr = STEREO.check, RELAX.check, OBSERVABLES.check, SAXS.check, PR.check
+check_cluster, check_pca, check_compare, check_dssp = CLUSTER.check, PCA.check, COMPARE.check, DSSP.check
+
+
+def check_lddt(args):
+    """--lddt's check; nothing to return, the flag has no value."""
+    LDDT.check(args)
+
+
+def check_args(args):
+    """Every refusal that needs no GPU, before anything is loaded.  The order decides which refusal a command line with two
+    faults gets; it is the run order but for --relax, which stands third."""
+    check_cg_input(args)
+    for check in (check_stereo, check_relax, check_observables, check_saxs, check_saxs_hydration, check_saxs_reweight, check_pr,
+                  check_cluster, check_pca, check_compare, check_lddt, check_dssp, check_sampler):
+        check(args)
+
+
+def relax_structures(args, name, xyz):
+    """--relax: every member of every frame xyz [E, B, n_atoms, 3], each on its own, CAs fixed -> (the relaxed coordinates,
+    which everything after sees; metrics.relax's dict with the decoder's coordinates and their geometry check)."""
+    top = topology_of(name, RELAX)
+    flat = xyz.reshape(-1, xyz.shape[2], 3)
+    geo0 = metrics.geometry_check(flat, top, order=args.edgeorder, near_dist=args.atom_cutoff)
+    rel = metrics.relax(flat, top, n_iter=args.relax, order=args.edgeorder)
+    return rel["xyz"].reshape(xyz.shape), dict(rel, unrelaxed=xyz, geo0=geo0)
+
+
+def report_relax(w, rel, geo, save_dir):
+    """What --relax writes and prints of one output file; geo: --geometry_check's result of the relaxed coordinates when
+    that is on, else it is computed here."""
+    args, geo0 = w.args, rel["geo0"]
+    save_arrays(save_dir, w.name, (("xyz_unrelaxed", rel["unrelaxed"]),
+                                   # [E * B, 3] float64: total energy before, after, accepted steps
+                                   ("relax", torch.stack((rel["energy0"], rel["energy"], rel["n_accepted"].to(torch.float64)), 1))))
+    geo1 = geo if geo is not None else GEOMETRY.run(w, topology_of(w.name, RELAX))
+    print(f"relax {w.name}: {args.relax} iterations, {float(rel['n_accepted'].to(torch.float64).mean()):.1f} accepted, "
+          f"energy {float(rel['energy0'].mean()):.3f} -> {float(rel['energy'].mean()):.3f}, clashes "
+          f"{int(geo0['clash'].sum())} -> {int(geo1['clash'].sum())}, min_dist {float(geo0['min_dist'].min()):.3f} -> "
+          f"{float(geo1['min_dist'].min()):.3f}", flush=True)
+
+
 def unit_generator(args, batch_id, device):
     """The noise source of one batch (a data file's <= 96 frames x num_ensemble members): seeded by the run's seed
     and the batch's position in the data set alone, so a structure is sampled from the same numbers on 1 or 8 GPUs."""
@@ -994,38 +1050,18 @@ def run_sampling(model, args, x, mask=None, batch=None):
     from codlad_amd.diffusion_and_flow.ode import ModelVelocity, odeint
     t_span = torch.linspace(0, 1, args.steps).to(x.device)
     func = ModelVelocity(model, mask=mask, batch=batch)
-    if getattr(args, "ode_stepwise", False):            # any callable that is not a ModelVelocity steps through odeint
+    if args.ode_stepwise:           # any callable that is not a ModelVelocity steps through odeint
         func = lambda t, x_in, f=func: f(t, x_in)       # noqa: E731
     traj, stats = odeint(func, x, t_span, rtol=args.rtol, atol=args.atol, method=args.method, return_stats=True)
-    if getattr(args, "compute_nfe", False):
+    if args.compute_nfe:
         print(f"NFE: {stats['n_eval']} model evaluations ({args.method}: {stats['n_accept']} steps accepted, "
               f"{stats['n_reject']} rejected)", flush=True)
     return traj[-1]
 
 
-def main(args):
-    check_cg_input(args)
-    check_stereo(args)
-    check_relax(args)
-    check_observables(args)
-    check_saxs(args)
-    check_saxs_hydration(args)
-    check_saxs_reweight(args)
-    check_pr(args)
-    check_cluster(args)
-    check_pca(args)
-    check_compare(args)
-    check_lddt(args)
-    check_dssp(args)
-    check_sampler(args)
-    saxs_data = read_saxs_data(args.saxs_data) if getattr(args, "saxs_data", None) else None
-    if not torch.cuda.is_available():
-        raise SystemExit("test.py (codlad_amd) needs an MI355X: there is no CPU path")
-    # one process per GPU under torch.distributed.run: batches (independent units) are dealt to the
-    # ranks longest-first, every rank samples and decodes its own, rank 0 reports the totals
-    rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
-    check_bpd(args, world)
-    check_fmloss(args, world)
+def init_distributed(rank, world):
+    """One process per GPU under torch.distributed.run: this rank's device, and the process group when there are several
+    -> (device, backend)."""
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     backend = os.environ.get("CODLAD_DIST_BACKEND", "nccl")   # "gloo": rehearsal of N > 1 on a one-GPU box
     dev_index = local_rank if backend == "nccl" else local_rank % torch.cuda.device_count()
@@ -1038,6 +1074,176 @@ def main(args):
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device(device))
         else:
             dist.init_process_group(backend, rank=rank, world_size=world)
+    return device, backend
+
+
+def load_models(args, device, rank, world):
+    """The networks the experiment runs -> namespace of vae, model, cvae, diffusion (None where it has none).  Only rank 0
+    reads checkpoints; the other ranks receive its weights (reference: one process, test.py:264-286)."""
+    nets = types.SimpleNamespace(vae=load_vae(args, device, load=rank == 0), model=None, cvae=None, diffusion=None)
+    if args.experiment == "genzprot":
+        nets.cvae = load_cvae(args, device, load=rank == 0)
+    if args.experiment in ("latent", "bpd", "fmloss"):
+        nets.model = load_denoiser(args, device, load=rank == 0)
+        if args.model == "diffusion":
+            nets.diffusion = create_diffusion(respacing_spec(args), noise_schedule=args.noise_schedule,
+                                              predict_xstart=args.predict_xstart,
+                                              rescale_learned_sigmas=args.rescale_learned_sigmas,
+                                              # reference test.py:297-303
+                                              self_condition=hasattr(nets.model, "self_condition") and args.self_condition)
+            if args.timestep_spacing == "logsnr" and rank == 0:
+                print(f"--timestep_spacing logsnr: {nets.diffusion.num_timesteps} of {args.num_sampling_steps} requested steps kept "
+                      "(steps on the same base step merge)", flush=True)
+    elif args.experiment not in ("recon", "genzprot"):
+        raise NotImplementedError(f"experiment {args.experiment!r}: latent, recon, genzprot, bpd and fmloss are built")
+    if world > 1:
+        from codlad_amd import parallel
+        mods = [m for m in (nets.model, nets.vae, nets.cvae) if m is not None]
+        parallel.broadcast_module_state(*mods, src=0)
+        # every rank packs the same parameters into its device blobs; prove it (and leave a record of the rank
+        # count and backend the collective ran on)
+        sums = [m.engine().weights.checksum() for m in mods]
+        parallel.verify_checksums(sums, what="weights broadcast from rank 0")
+    return nets
+
+
+def deal_units(args, rank, world, fixed):
+    """This rank's batches as (id, output name, batch, info); the id is the batch's position in the data set, the same on
+    every world size.  Batches (independent units) are dealt to the ranks longest-first."""
+    units = [(g,) + u for g, u in enumerate(iter_batches(args))]
+    if world > 1:
+        from codlad_amd.parallel import shard_units, unit_cost
+        costs = [int(b["num_CGs"].shape[0]) * unit_cost(int(b["num_CGs"][0])) for _g, _n, b, _i in units]
+        units = [units[u] for u in shard_units(costs, world)[rank]]
+    if fixed is not None:
+        short = min(int(b["num_CGs"][0]) for _g, _n, b, _i in units) if units else None
+        if short is not None and fixed[-1] > short:
+            raise SystemExit(f"--fix_residues: position {fixed[-1]} is out of range (the shortest structure has {short} residues)")
+    return units
+
+
+def encode_latents(args, vae, batch):
+    """The frames' own latents: the VQ-VAE encoder on the batch's atoms, un-quantized, normalised as the samples are
+    de-normalised before they are decoded."""
+    return get_norm_feature(vae.get_latent_wovq(batch)[0], args.vae_type, norm_channel=args.norm,
+                            norm_single=args.norm_single, norm_in=True, dataname=args.data_type)
+
+
+def score_bpd(args, nets, name, batch, mask, gen, save_dir, st):
+    """--experiment bpd: the frames' own latents scored by the variational bound over the respaced steps, one fused loop."""
+    B, L, diffusion = mask.shape[0], mask.shape[1], nets.diffusion
+    x0 = encode_latents(args, nets.vae, batch).contiguous()
+    r = diffusion.calc_bpd_loop(nets.model.forward, x0, clip_denoised=False, model_kwargs=dict(y=None, mask=mask, batch=dict(batch)),
+                                step_noise=diffusion._draw_noise(x0, generator=gen))
+    torch.cuda.synchronize()
+    dt = time.time() - st
+    save_arrays(save_dir, name, [(f"bpd_{key}", r[key]) for key in ("vb", "mse", "xstart_mse")])   # [N, T], column k = step T-1-k (the IDDPM layout)
+    print(f"{name}: {B} frames, L={L}, T={diffusion.num_timesteps}: total_bpd {float(r['total_bpd'].mean()):.6f} "
+          f"prior_bpd {float(r['prior_bpd'].mean()):.6e}: {dt:.2f}s ({B / dt:.1f} structures/s)", flush=True)
+
+
+def score_fmloss(args, nets, name, batch, mask, gen, save_dir, st):
+    """--experiment fmloss: the frames' own latents are the data end x1 of the path; the source end x0 and the path's noise
+    per time come from the batch's generator; times are the midpoints (k + 0.5) / K, never 0 or 1, where the target
+    matcher's flow divides by 1 - t.  One fused sweep."""
+    from codlad_amd.diffusion_and_flow.flow import create_flow_matcher
+    B, L, K = mask.shape[0], mask.shape[1], fmloss_steps(args)
+    ts = [(k + 0.5) / K for k in range(K)]
+    x1 = encode_latents(args, nets.vae, batch).contiguous()
+    x0 = torch.randn(x1.shape, device=x1.device, dtype=x1.dtype, generator=gen)
+    eps = torch.stack([torch.randn(x1.shape, device=x1.device, dtype=x1.dtype, generator=gen) for _ in range(K)])
+    r = create_flow_matcher(args.model, args.fm_sigma).loss_sweep(
+        nets.model.forward, x0, x1, ts, step_noise=eps, loss_type=args.loss, model_kwargs=dict(y=None, mask=mask, batch=dict(batch)))
+    torch.cuda.synchronize()
+    dt = time.time() - st
+    save_arrays(save_dir, name, [(f"fmloss_{args.loss}", r["per_sample"])])                        # [N, K]
+    print(f"{name}: {B} frames, L={L}, K={K}, {args.model} sigma={args.fm_sigma}: mean {args.loss} "
+          f"{float(r['loss'].mean()):.6f}: {dt:.2f}s ({B / dt:.1f} structures/s)", flush=True)
+    for tv, v in zip(ts, r["loss"].tolist()):
+        print(f"  t={tv:.4f} {args.loss} {v:.6f}", flush=True)
+
+
+def sample_latents(args, nets, batch, mask, gen, fixed):
+    """The latents the decoder is handed, [B * E, L, latent]: E ensemble members of every frame = the batch repeated E times
+    along the sample axis."""
+    B, (n, L) = int(batch["num_CGs"].shape[0]), mask.shape
+    E, device = n // B, str(mask.device)
+    if args.experiment == "recon":
+        # reference test.py:501: the VQ-VAE's own encoder on the batch's atoms, un-quantized (latent_decode
+        # quantizes); deterministic, so the E ensemble members of a frame are equal, as in the reference's loop
+        return nets.vae.get_latent_wovq(batch)[0].repeat(E, 1, 1)
+    if args.experiment == "genzprot":
+        # reference test.py:495-498, 559: a sample of the conditional prior per member
+        return torch.cat([nets.cvae.get_latent_cg(batch, generator=gen)[0] for _ in range(E)], 0)
+    z = torch.randn(n, L, args.latent_size, device=device, generator=gen)
+    kwargs = dict(y=None, mask=mask, batch=dict(batch))
+    if args.model == "diffusion":
+        diffusion, pin = nets.diffusion, None
+        if fixed is not None:
+            # the VQ-VAE encoder's latents of the batch pin the chosen residues of every ensemble member (a PinLatents
+            # denoised_fn: fused into the loop)
+            pin = PinLatents(encode_latents(args, nets.vae, batch).repeat(E, 1, 1).contiguous(), fix_residue_mask(fixed, L, n, device))
+        if args.sampler == "dpmpp":
+            samples = diffusion.dpm_solver_sample_loop(nets.model.forward, z.shape, z, clip_denoised=False, denoised_fn=pin,
+                                                       device=device, model_kwargs=kwargs)
+        elif args.sampler == "ddim":
+            samples = diffusion.ddim_sample_loop(nets.model.forward, z.shape, z, clip_denoised=False, denoised_fn=pin,
+                                                 model_kwargs=kwargs, device=device, eta=args.eta,
+                                                 step_noise=diffusion._draw_noise(z, generator=gen))
+        else:
+            samples = diffusion.p_sample_loop(nets.model.forward, z.shape, z, clip_denoised=False, denoised_fn=pin,
+                                              model_kwargs=kwargs, device=device, step_noise=diffusion._draw_noise(z, generator=gen))
+    else:                                               # --model fm / icfm / otcfm ...: ODE sampling
+        samples = run_sampling(nets.model, args, z, mask=mask, batch=kwargs["batch"])
+    return get_norm_feature(samples, args.vae_type, norm_channel=args.norm, norm_single=args.norm_single,
+                            norm_in=False, dataname=args.data_type)
+
+
+def decode(args, nets, name, batch, info, samples, mask, save_dir):
+    """Latents -> coordinates, member by member -> (xyz [E, B, n_atoms, 3], the Evaluation of the batch or None where the
+    input has no true atoms).  --save_codes writes the VQ codes on the way."""
+    B, (n, L) = int(batch["num_CGs"].shape[0]), mask.shape
+    decoder_model = nets.cvae if args.experiment == "genzprot" else nets.vae
+    if args.save_codes and getattr(decoder_model, "quantize", None) is not None:
+        # the VQ code of every residue of every member, [B * E, L]: what the decoder is handed (latent_decode quantizes)
+        save_arrays(save_dir, name, [("codes", decoder_model.quantize(samples, mask=mask)[1].reshape(n, L))])
+    og = batch["OG_CG_nxyz"].reshape(-1, L + 2, 4)
+    xyz_all = []
+    evaluation = Evaluation() if all(k in batch for k in EVAL_KEYS) else None
+    for e in range(n // B):
+        _, ic_recon = decoder_model.latent_decode(samples[e * B:(e + 1) * B], mask[:B], batch)
+        xyz_all.append(ic_to_xyz(og, ic_recon.reshape(-1, L, 13, 3), info))
+        if evaluation is not None:                               # reference test.py:589-594, per ensemble member
+            evaluation.add(batch, ic_recon, xyz_all[-1], xyz_all[-1].shape[1])
+    return torch.stack(xyz_all), evaluation
+
+
+def save_trajectory(w, save_dir):
+    """--save_pdb: reference test.py:787-796 writes the generated ensemble through mdtraj (.xtc + .pdb); here both directly,
+    frames of member 0 first (multi-model PDB in Angstrom, .xtc in nm as the format has it), superposed as --superpose says."""
+    from codlad_amd.utils.protein_module import write_pdb
+    from codlad_amd.utils.xtc import write_xtc
+    mode, topology = w.args.superpose, _TOPOLOGY[w.name]
+    if mode == "ref" and "nxyz" not in w.batch:
+        raise SystemExit("--superpose ref needs the true coordinates of the batch (nxyz); this input has none: "
+                         "use --superpose first")
+    out = superpose_models(w.xyz, mode, ref=w.batch["nxyz"][:, 1:] if mode == "ref" else None,
+                           sel=(ca_indices(topology) or None) if mode != "none" else None)
+    frames = out.reshape(-1, w.n_atoms, 3).cpu().numpy()
+    write_pdb(os.path.join(save_dir, f"generated_traj_{w.name}.pdb"), frames, *topology)
+    write_xtc(os.path.join(save_dir, f"generated_traj_{w.name}.xtc"), frames)
+
+
+def main(args):
+    check_args(args)
+    saxs_data = read_saxs_data(args.saxs_data) if args.saxs_data else None
+    if not torch.cuda.is_available():
+        raise SystemExit("test.py (codlad_amd) needs an MI355X: there is no CPU path")
+    # one process per GPU under torch.distributed.run: every rank samples and decodes its own batches, rank 0 reports the totals
+    rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
+    check_bpd(args, world)
+    check_fmloss(args, world)
+    device, backend = init_distributed(rank, world)
     torch.set_grad_enabled(False)
     # the global streams are seeded like the reference's (test.py:256) but NOT used for the latents: every batch
     # draws its noise from its own generator (unit_generator), so the numbers a structure gets do not depend on the
@@ -1048,44 +1254,11 @@ def main(args):
         raise NotImplementedError("cfg_scale > 1 calls model.forward_with_cfg, which the reference model "
                                   "does not define (dead path)")
     fixed = check_fix_residues(args)
-    # only rank 0 reads checkpoints; the other ranks receive its weights (reference: one process, test.py:264-286)
-    vae = load_vae(args, device, load=rank == 0)
-    model, cvae = None, None
-    if args.experiment == "genzprot":
-        cvae = load_cvae(args, device, load=rank == 0)
-    if args.experiment in ("latent", "bpd", "fmloss"):
-        model = load_denoiser(args, device, load=rank == 0)
-        diffusion = None if args.model != "diffusion" else create_diffusion(respacing_spec(args), noise_schedule=args.noise_schedule,
-                                     predict_xstart=args.predict_xstart,
-                                     rescale_learned_sigmas=args.rescale_learned_sigmas,
-                                     # reference test.py:297-303
-                                     self_condition=hasattr(model, "self_condition") and args.self_condition)
-        if diffusion is not None and getattr(args, "timestep_spacing", "uniform") == "logsnr" and rank == 0:
-            print(f"--timestep_spacing logsnr: {diffusion.num_timesteps} of {args.num_sampling_steps} requested steps kept "
-                  "(steps on the same base step merge)", flush=True)
-    elif args.experiment not in ("recon", "genzprot"):
-        raise NotImplementedError(f"experiment {args.experiment!r}: latent, recon, genzprot, bpd and fmloss are built")
-    if world > 1:
-        from codlad_amd import parallel
-        mods = [m for m in (model, vae, cvae) if m is not None]
-        parallel.broadcast_module_state(*mods, src=0)
-        # every rank packs the same parameters into its device blobs; prove it (and leave a record of the rank
-        # count and backend the collective ran on)
-        sums = [m.engine().weights.checksum() for m in mods]
-        parallel.verify_checksums(sums, what="weights broadcast from rank 0")
+    nets = load_models(args, device, rank, world)
     save_dir = f"./logs/generated_samples_{args.sample_index}_{args.model_step}/{args.exp}_{args.data_type}"
     os.makedirs(save_dir, exist_ok=True)
     total, t_all = 0, time.time()
-    units = [(g,) + u for g, u in enumerate(iter_batches(args))]      # g: the batch's id, the same on every world size
-    if world > 1:
-        from codlad_amd.parallel import shard_units, unit_cost
-        costs = [int(b["num_CGs"].shape[0]) * unit_cost(int(b["num_CGs"][0])) for _g, _n, b, _i in units]
-        units = [units[u] for u in shard_units(costs, world)[rank]]
-    if fixed is not None:
-        short = min(int(b["num_CGs"][0]) for _g, _n, b, _i in units) if units else None
-        if short is not None and fixed[-1] > short:
-            raise SystemExit(f"--fix_residues: position {fixed[-1]} is out of range (the shortest structure has {short} residues)")
-    for g, name, batch, info in units:
+    for g, name, batch, info in deal_units(args, rank, world, fixed):
         gen = unit_generator(args, g, device)
         batch = {k: (v.to(device) if hasattr(v, "to") else v) for k, v in batch.items()}
         B = int(batch["num_CGs"].shape[0])
@@ -1093,269 +1266,33 @@ def main(args):
         E = args.num_ensemble
         st = time.time()
         mask = torch.ones(B * E, L, dtype=torch.bool, device=device)
-        # E ensemble members of every frame = the batch repeated E times along the sample axis
-        rep = {k: v for k, v in batch.items()}
-        if args.experiment == "bpd":
-            # the frames' own latents (the VQ-VAE encoder on the batch's atoms, normalised exactly as --fix_residues
-            # normalises its known latents) scored by the variational bound over the respaced steps: one fused loop
-            x0 = get_norm_feature(vae.get_latent_wovq(batch)[0], args.vae_type, norm_channel=args.norm,
-                                  norm_single=args.norm_single, norm_in=True, dataname=args.data_type).contiguous()
-            r = diffusion.calc_bpd_loop(model.forward, x0, clip_denoised=False,
-                                        model_kwargs=dict(y=None, mask=mask[:B], batch=rep),
-                                        step_noise=diffusion._draw_noise(x0, generator=gen))
-            torch.cuda.synchronize()
-            dt = time.time() - st
+        if args.experiment in ("bpd", "fmloss"):
+            (score_bpd if args.experiment == "bpd" else score_fmloss)(args, nets, name, batch, mask[:B], gen, save_dir, st)
             total += B
-            for key in ("vb", "mse", "xstart_mse"):                 # [N, T], column k = step T-1-k (the IDDPM layout)
-                np.save(os.path.join(save_dir, f"{name}_bpd_{key}.npy"), r[key].cpu().numpy())
-            print(f"{name}: {B} frames, L={L}, T={diffusion.num_timesteps}: total_bpd {float(r['total_bpd'].mean()):.6f} "
-                  f"prior_bpd {float(r['prior_bpd'].mean()):.6e}: {dt:.2f}s ({B / dt:.1f} structures/s)", flush=True)
             continue
-        if args.experiment == "fmloss":
-            # the frames' own latents (as --experiment bpd obtains them) are the data end x1 of the path; the source end x0
-            # and the path's noise per time come from the batch's generator; times are the midpoints (k + 0.5) / K, never 0
-            # or 1, where the target matcher's flow divides by 1 - t
-            from codlad_amd.diffusion_and_flow.flow import create_flow_matcher
-            K = fmloss_steps(args)
-            ts = [(k + 0.5) / K for k in range(K)]
-            x1 = get_norm_feature(vae.get_latent_wovq(batch)[0], args.vae_type, norm_channel=args.norm,
-                                  norm_single=args.norm_single, norm_in=True, dataname=args.data_type).contiguous()
-            x0 = torch.randn(x1.shape, device=device, dtype=x1.dtype, generator=gen)
-            eps = torch.stack([torch.randn(x1.shape, device=device, dtype=x1.dtype, generator=gen) for _ in range(K)])
-            r = create_flow_matcher(args.model, args.fm_sigma).loss_sweep(
-                model.forward, x0, x1, ts, step_noise=eps, loss_type=args.loss, model_kwargs=dict(y=None, mask=mask[:B], batch=rep))
-            torch.cuda.synchronize()
-            dt = time.time() - st
-            total += B
-            np.save(os.path.join(save_dir, f"{name}_fmloss_{args.loss}.npy"), r["per_sample"].cpu().numpy())     # [N, K]
-            print(f"{name}: {B} frames, L={L}, K={K}, {args.model} sigma={args.fm_sigma}: mean {args.loss} "
-                  f"{float(r['loss'].mean()):.6f}: {dt:.2f}s ({B / dt:.1f} structures/s)", flush=True)
-            for tv, v in zip(ts, r["loss"].tolist()):
-                print(f"  t={tv:.4f} {args.loss} {v:.6f}", flush=True)
-            continue
-        if args.experiment == "latent":
-            z = torch.randn(B * E, L, args.latent_size, device=device, generator=gen)
-            if args.model == "diffusion":
-                pin = None
-                if fixed is not None:
-                    # the VQ-VAE encoder's latents of the batch, normalised as the samples are de-normalised below, pin the
-                    # chosen residues of every ensemble member (a PinLatents denoised_fn: fused into the loop)
-                    known = get_norm_feature(vae.get_latent_wovq(batch)[0], args.vae_type, norm_channel=args.norm,
-                                             norm_single=args.norm_single, norm_in=True, dataname=args.data_type)
-                    pin = PinLatents(known.repeat(E, 1, 1).contiguous(), fix_residue_mask(fixed, L, B * E, device))
-                if args.sampler == "dpmpp":
-                    samples = diffusion.dpm_solver_sample_loop(model.forward, z.shape, z, clip_denoised=False,
-                                                               denoised_fn=pin, device=device,
-                                                               model_kwargs=dict(y=None, mask=mask, batch=rep))
-                elif args.sampler == "ddim":
-                    samples = diffusion.ddim_sample_loop(model.forward, z.shape, z, clip_denoised=False, denoised_fn=pin,
-                                                         model_kwargs=dict(y=None, mask=mask, batch=rep), device=device,
-                                                         eta=args.eta, step_noise=diffusion._draw_noise(z, generator=gen))
-                else:
-                    samples = diffusion.p_sample_loop(model.forward, z.shape, z, clip_denoised=False, denoised_fn=pin,
-                                                      model_kwargs=dict(y=None, mask=mask, batch=rep), device=device,
-                                                      step_noise=diffusion._draw_noise(z, generator=gen))
-            else:                                               # --model fm / icfm / otcfm ...: ODE sampling
-                samples = run_sampling(model, args, z, mask=mask, batch=rep)
-            samples = get_norm_feature(samples, args.vae_type, norm_channel=args.norm, norm_single=args.norm_single,
-                                       norm_in=False, dataname=args.data_type)
-        elif args.experiment == "recon":
-            # reference test.py:501: the VQ-VAE's own encoder on the batch's atoms, un-quantized (latent_decode
-            # quantizes); deterministic, so the E ensemble members of a frame are equal, as in the reference's loop
-            feat = vae.get_latent_wovq(batch)[0]
-            samples = feat.repeat(E, 1, 1)
-        else:
-            # --experiment genzprot (reference test.py:495-498, 559): a sample of the conditional prior per member
-            samples = torch.cat([cvae.get_latent_cg(batch, generator=gen)[0] for _ in range(E)], 0)
-        decoder_model = cvae if args.experiment == "genzprot" else vae
-        if getattr(args, "save_codes", False) and getattr(decoder_model, "quantize", None) is not None:
-            # the VQ code of every residue of every member, [B * E, L]: what the decoder is handed (latent_decode quantizes)
-            codes = decoder_model.quantize(samples, mask=mask)[1]
-            np.save(os.path.join(save_dir, f"{name}_codes.npy"), codes.reshape(B * E, L).cpu().numpy())
-        nres = L + 2
-        og = batch["OG_CG_nxyz"].reshape(-1, nres, 4)
-        xyz_all = []
-        evaluation = Evaluation() if all(k in batch for k in EVAL_KEYS) else None
-        for e in range(E):
-            _, ic_recon = decoder_model.latent_decode(samples[e * B:(e + 1) * B], mask[:B], batch)
-            xyz_all.append(ic_to_xyz(og, ic_recon.reshape(-1, nres - 2, 13, 3), info))
-            if evaluation is not None:                               # reference test.py:589-594, per ensemble member
-                evaluation.add(batch, ic_recon, xyz_all[-1], xyz_all[-1].shape[1])
-        xyz = torch.stack(xyz_all)                                   # [E, B, n_atoms, 3]
+        samples = sample_latents(args, nets, batch, mask, gen, fixed)
+        xyz, evaluation = decode(args, nets, name, batch, info, samples, mask, save_dir)
         rel = None
-        if getattr(args, "relax", 0):
-            if name not in _GEOMETRY_TOP:
-                raise SystemExit(f"--relax: the topology of {name} is not known on this input route")
-            # every member of every frame, each on its own, CAs fixed; everything below sees the relaxed coordinates
-            flat = xyz.reshape(-1, xyz.shape[2], 3)
-            geo0 = metrics.geometry_check(flat, _GEOMETRY_TOP[name], order=args.edgeorder, near_dist=args.atom_cutoff)
-            rel = metrics.relax(flat, _GEOMETRY_TOP[name], n_iter=args.relax, order=args.edgeorder)
-            xyz_unrelaxed, xyz = xyz, rel["xyz"].reshape(xyz.shape)
-        geo = None
-        if args.geometry_check:
-            if name not in _GEOMETRY_TOP:
-                raise SystemExit(f"--geometry_check: the topology of {name} is not known on this input route")
-            # every member of every frame against the template bond graph: one launch, read back after the one sync below
-            geo = metrics.geometry_check(xyz.reshape(-1, xyz.shape[2], 3), _GEOMETRY_TOP[name], order=args.edgeorder,
-                                         near_dist=args.atom_cutoff)
-        ste = None
-        if args.stereo_check:
-            if name not in _GEOMETRY_TOP:
-                raise SystemExit(f"--stereo_check: the topology of {name} is not known on this input route")
-            ste = metrics.stereo_check(xyz.reshape(-1, xyz.shape[2], 3), _GEOMETRY_TOP[name])      # one launch, as above
-        obs = None
-        if getattr(args, "observables", 0):
-            if name not in _GEOMETRY_TOP:
-                raise SystemExit(f"--observables: the topology of {name} is not known on this input route")
-            obs = observables(xyz.reshape(-1, xyz.shape[2], 3), _GEOMETRY_TOP[name], args.observables)    # the written coordinates
-        sx = None
-        if getattr(args, "saxs", 0):
-            if name not in _GEOMETRY_TOP:
-                raise SystemExit(f"--saxs: the topology of {name} is not known on this input route")
-            saxs_q = saxs_data[0] if saxs_data is not None else np.linspace(0.0, 0.5, args.saxs)
-            if getattr(args, "saxs_hydration", None) is not None:
-                sx = saxs_hydrated(xyz.reshape(-1, xyz.shape[2], 3), _GEOMETRY_TOP[name], saxs_q, args.saxs_hydration, saxs_data)
-            else:
-                sx = metrics.saxs_profile(xyz.reshape(-1, xyz.shape[2], 3), _GEOMETRY_TOP[name], q=saxs_q)    # the written coordinates
-        pr = None
-        if getattr(args, "pr", 0):
-            if name not in _GEOMETRY_TOP:
-                raise SystemExit(f"--pr: the topology of {name} is not known on this input route")
-            try:
-                pr = metrics.pair_distribution(xyz.reshape(-1, xyz.shape[2], 3), _GEOMETRY_TOP[name], dr=args.pr)   # the written coordinates
-            except ValueError as e:                               # more bins than the kernel holds: a wider bin is the way out
-                raise SystemExit(f"--pr {args.pr}: {e}") from None
-        cl = None
-        if getattr(args, "cluster", 0):
-            cl_sel = None
-            if getattr(args, "cluster_atoms", "ca") == "ca":
-                cl_sel = ca_indices(_TOPOLOGY[name]) if name in _TOPOLOGY else None
-                if not cl_sel:
-                    raise SystemExit(f"--cluster: the CA atoms of {name} are not known on this input route (use --cluster_atoms all)")
-            cl = metrics.cluster(xyz.reshape(-1, xyz.shape[2], 3), args.cluster, sel=cl_sel)    # members x frames: one pool
-        pc = None
-        if getattr(args, "pca", 0):
-            pc_atoms = getattr(args, "pca_atoms", "ca")
-            pc_sel = pca_selection(name, xyz.shape[2], pc_atoms, ca_indices(_TOPOLOGY[name]) if name in _TOPOLOGY else None)
-            pool = xyz.reshape(-1, xyz.shape[2], 3)                                             # members x frames: one pool
-            pc = metrics.pca(pool, n_components=min(args.pca, 3 * (len(pc_sel) if pc_sel else xyz.shape[2])), sel=pc_sel)
-        cmp = None
-        if getattr(args, "compare", 0):
-            truth = compare_truth(name, batch).reshape(-1, xyz.shape[2], 3)
-            cmp_sel = ca_indices(_TOPOLOGY[name]) if name in _TOPOLOGY else None
-            if not cmp_sel or len(cmp_sel) < 2:
-                raise SystemExit(f"--compare: the CA atoms of {name} are not known on this input route")
-            cmp_top = _GEOMETRY_TOP[name] if name in _GEOMETRY_TOP and compare_no_atom_masked(batch) else None
-            cmp = metrics.ensemble_compare(xyz.reshape(-1, xyz.shape[2], 3), truth, top=cmp_top, sel=cmp_sel, n_bins=args.compare,
-                                           cluster_cutoff=getattr(args, "compare_cluster", None))   # members x frames: one pool
-        ld = None
-        if getattr(args, "lddt", False):
-            if name not in _GEOMETRY_TOP:
-                raise SystemExit(f"--lddt: the topology of {name} is not known on this input route")
-            truth = compare_truth(name, batch, "--lddt").reshape(-1, xyz.shape[2], 3)
-            # member k of frame f against true frame f; atoms the batch masks in a frame take no part
-            ld = metrics.lddt(xyz.reshape(-1, xyz.shape[2], 3), truth, _GEOMETRY_TOP[name],
-                              ref_index=torch.arange(truth.shape[0]).repeat(xyz.shape[0]),
-                              sel=lddt_selection(batch, truth.shape[0], xyz.shape[2]))
-        sec = None
-        if getattr(args, "dssp", False):
-            if name not in _GEOMETRY_TOP:
-                raise SystemExit(f"--dssp: the topology of {name} is not known on this input route")
-            sec = metrics.dssp(xyz.reshape(-1, xyz.shape[2], 3), _GEOMETRY_TOP[name])            # the written coordinates
-            sec_prop = metrics.ss_propensity(sec["ss"])
+        if args.relax:
+            xyz, rel = relax_structures(args, name, xyz)
+        w = Written(args, name, batch, xyz, saxs_data)
+        # one launch set per row that is on, in table order; everything is read back after the one synchronisation
+        results = [(row, row.run(w, topology_of(name, row))) for row in ANALYSES if row.on(args)]
         torch.cuda.synchronize()
         dt = time.time() - st
         total += B * E
         if evaluation is not None:
             evaluation.report(name, args)
         if rel is not None:
-            np.save(os.path.join(save_dir, f"{name}_xyz_unrelaxed.npy"), xyz_unrelaxed.cpu().numpy())
-            # [E * B, 3] float64: total energy before, after, accepted steps
-            np.save(os.path.join(save_dir, f"{name}_relax.npy"),
-                    torch.stack((rel["energy0"], rel["energy"], rel["n_accepted"].to(torch.float64)), 1).cpu().numpy())
-            geo1 = geo if geo is not None else metrics.geometry_check(xyz.reshape(-1, xyz.shape[2], 3), _GEOMETRY_TOP[name],
-                                                                      order=args.edgeorder, near_dist=args.atom_cutoff)
-            print(f"relax {name}: {args.relax} iterations, {float(rel['n_accepted'].to(torch.float64).mean()):.1f} accepted, "
-                  f"energy {float(rel['energy0'].mean()):.3f} -> {float(rel['energy'].mean()):.3f}, clashes "
-                  f"{int(geo0['clash'].sum())} -> {int(geo1['clash'].sum())}, min_dist {float(geo0['min_dist'].min()):.3f} -> "
-                  f"{float(geo1['min_dist'].min()):.3f}", flush=True)
-        np.save(os.path.join(save_dir, f"{name}_xyz_recon.npy"), xyz.cpu().numpy())
-        if geo is not None:
-            np.save(os.path.join(save_dir, f"{name}_geometry.npy"), geo["counts"].cpu().numpy())        # [E * B, 5]
-            np.save(os.path.join(save_dir, f"{name}_geometry_min.npy"), geo["min_dist"].cpu().numpy())
-            geometry_report(name, geo, xyz.shape[2])
-        if ste is not None:
-            np.save(os.path.join(save_dir, f"{name}_stereo.npy"), ste["counts"].cpu().numpy())          # [E * B, 6]
-            np.save(os.path.join(save_dir, f"{name}_stereo_flags.npy"), ste["flags"].cpu().numpy())     # [E * B, R]
-            np.save(os.path.join(save_dir, f"{name}_torsions.npy"), ste["values"].cpu().numpy())        # [E * B, R, 9]
-            stereo_report(name, ste)
-        if obs is not None:
-            np.save(os.path.join(save_dir, f"{name}_sasa_residue.npy"), obs["sasa"]["residue"].cpu().numpy())     # [E * B, R]
-            np.save(os.path.join(save_dir, f"{name}_rg.npy"), obs["rg"].cpu().numpy())                            # [E * B]
-            np.save(os.path.join(save_dir, f"{name}_ca_contacts.npy"), obs["contacts"]["frequency"].cpu().numpy())  # [R, R]
-            observables_report(name, obs)
-        if sx is not None:
-            np.save(os.path.join(save_dir, f"{name}_saxs.npy"), sx["I"].cpu().numpy())                    # float64 [E * B, N_Q]
-            np.save(os.path.join(save_dir, f"{name}_saxs_q.npy"), sx["q"].cpu().numpy())                  # float32 [N_Q]
-            if "partials" in sx:
-                np.save(os.path.join(save_dir, f"{name}_saxs_partials.npy"), sx["partials"].cpu().numpy())  # float64 [E * B, 6, N_Q]
-            saxs_report(name, sx, saxs_data)
-            if getattr(args, "saxs_reweight", ()):
-                weights, rw_mean, _stats = saxs_reweight_report(name, sx, saxs_data, args.saxs_reweight)
-                np.save(os.path.join(save_dir, f"{name}_saxs_weights.npy"), weights)                      # float64 [n_theta, E * B]
-                np.save(os.path.join(save_dir, f"{name}_saxs_reweighted.npy"), rw_mean)                   # float64 [n_theta, N_Q]
-        if pr is not None:
-            np.save(os.path.join(save_dir, f"{name}_pr.npy"), pr["P"].cpu().numpy())                      # float64 [E * B, BINS]
-            np.save(os.path.join(save_dir, f"{name}_pr_r.npy"), pr["r"].cpu().numpy())                    # float64 [BINS]
-            pr_report(name, pr)
-        if cl is not None:
-            np.save(os.path.join(save_dir, f"{name}_cluster_labels.npy"), cl["labels"].cpu().numpy())     # int32 [E * B], -1 = not finite
-            np.save(os.path.join(save_dir, f"{name}_cluster_centres.npy"), cl["centres"].cpu().numpy())   # int32 [K]: indices into the pool
-            np.save(os.path.join(save_dir, f"{name}_cluster_sizes.npy"), cl["sizes"].cpu().numpy())       # int32 [K]
-            cluster_report(name, cl)
-            if getattr(args, "save_pdb", False) and name in _TOPOLOGY and cl["n_clusters"]:
-                from codlad_amd.utils.protein_module import write_pdb
-                centres = xyz.reshape(-1, xyz.shape[2], 3)[cl["centres"].to(torch.int64)].cpu().numpy()
-                write_pdb(os.path.join(save_dir, f"cluster_centres_{name}.pdb"), centres, *_TOPOLOGY[name])
-        if pc is not None:
-            np.save(os.path.join(save_dir, f"{name}_pca_mean.npy"), pc["mean"].cpu().numpy())                # float64 [m, 3]
-            np.save(os.path.join(save_dir, f"{name}_pca_eigenvalues.npy"), pc["eigenvalues"].cpu().numpy())  # float64 [K], descending
-            np.save(os.path.join(save_dir, f"{name}_pca_components.npy"), pc["components"].cpu().numpy())    # float64 [K, m, 3]
-            np.save(os.path.join(save_dir, f"{name}_pca_projections.npy"), pc["projections"].cpu().numpy())  # float64 [E * B, K]
-            np.save(os.path.join(save_dir, f"{name}_rmsf.npy"), pc["rmsf"].cpu().numpy())                    # float64 [m]
-            pca_report(name, pc)
-            if getattr(args, "save_pdb", False) and name in _TOPOLOGY and pc_sel is None:
-                from codlad_amd.utils.protein_module import write_pdb
-                write_pdb(os.path.join(save_dir, f"pca_mean_{name}.pdb"), pc["mean"].cpu().numpy()[None].astype(np.float32),
-                          *_TOPOLOGY[name])
-        if cmp is not None:
-            np.save(os.path.join(save_dir, f"{name}_compare_js_dist.npy"), cmp["js_dist"].cpu().numpy())          # float64 [R, R]
-            if "js_torsion" in cmp:
-                np.save(os.path.join(save_dir, f"{name}_compare_js_torsion.npy"), cmp["js_torsion"].cpu().numpy())  # float64 [R, 7]
-            compare_report(name, cmp)
-        if ld is not None:
-            np.save(os.path.join(save_dir, f"{name}_lddt.npy"), ld["global"].cpu().numpy())              # float64 [E * B]
-            np.save(os.path.join(save_dir, f"{name}_lddt_residue.npy"), ld["residue"].cpu().numpy())     # float64 [E * B, R]
-            lddt_report(name, ld)
-        if sec is not None:
-            np.save(os.path.join(save_dir, f"{name}_dssp.npy"), sec["ss"].cpu().numpy())                  # uint8 [E * B, R]
-            np.save(os.path.join(save_dir, f"{name}_dssp_propensity.npy"), sec_prop.cpu().numpy())       # float64 [R, 8]
-            dssp_report(name, sec, sec_prop)
-        if getattr(args, "save_pdb", False) and name in _TOPOLOGY:
-            # reference test.py:787-796 writes the generated ensemble through mdtraj (.xtc + .pdb); here both directly, frames
-            # of member 0 first (multi-model PDB in Angstrom, .xtc in nm as the format has it)
-            from codlad_amd.utils.protein_module import write_pdb
-            from codlad_amd.utils.xtc import write_xtc
-            mode = getattr(args, "superpose", "none")
-            if mode == "ref" and "nxyz" not in batch:
-                raise SystemExit("--superpose ref needs the true coordinates of the batch (nxyz); this input has none: "
-                                 "use --superpose first")
-            out = superpose_models(xyz, mode, ref=batch["nxyz"][:, 1:] if mode == "ref" else None,
-                                   sel=(ca_indices(_TOPOLOGY[name]) or None) if mode != "none" else None)
-            frames = out.reshape(-1, xyz.shape[2], 3).cpu().numpy()
-            write_pdb(os.path.join(save_dir, f"generated_traj_{name}.pdb"), frames, *_TOPOLOGY[name])
-            write_xtc(os.path.join(save_dir, f"generated_traj_{name}.xtc"), frames)
-        print(f"{name}: {B} frames x {E} members, L={L}, {xyz.shape[2]} atoms: {dt:.2f}s "
+            report_relax(w, rel, dict(results).get(GEOMETRY), save_dir)
+        save_arrays(save_dir, name, [("xyz_recon", xyz)])
+        for row, res in results:
+            print_frame(*row.report(w, res))
+            row.extras(w, res, save_dir)
+            save_arrays(save_dir, name, [(suffix, get(res)) for suffix, get in row.writes])
+        if args.save_pdb and name in _TOPOLOGY:
+            save_trajectory(w, save_dir)
+        print(f"{name}: {B} frames x {E} members, L={L}, {w.n_atoms} atoms: {dt:.2f}s "
               f"({B * E / dt:.1f} structures/s)", flush=True)
     if world > 1:
         import torch.distributed as dist
@@ -1367,7 +1304,8 @@ def main(args):
         print(f"done: {total} structures on {world} GPU(s) in {time.time() - t_all:.1f}s -> {save_dir}")
 
 
-if __name__ == "__main__":
+def build_parser():
+    """The command line: names and defaults as in the reference (test.py:894-961), then the additions."""
     p = argparse.ArgumentParser("parameters")
     # names and defaults as in the reference (test.py:894-961)
     p.add_argument("--seed", type=int, default=42)
@@ -1543,4 +1481,8 @@ if __name__ == "__main__":
                         "reference's respacing) or uniformly in log-SNR (steps on the same base step merge); --model diffusion only")
     p.add_argument("--eta", type=float, default=0.0,
                    help="DDIM noise scale (0 = the deterministic sampler, 1 = the DDPM posterior variance); --sampler ddim only")
-    main(p.parse_args())
+    return p
+
+
+if __name__ == "__main__":
+    main(build_parser().parse_args())

@@ -5,7 +5,6 @@ bit-identical generated coordinates - without ever holding an atom besides the C
 The CPU tests hold the reader, the template topology and the flag checks; the GPU tests build both routes from one golden
 (N6_L46_B3: 46 residues, 3 frames) and run the CLI once per route (a module fixture shared by the tests that read its
 output, the geometry files among them)."""
-import importlib.util
 import os
 import subprocess
 import sys
@@ -23,16 +22,14 @@ from codlad_amd.utils import dataset_builder as db
 from codlad_amd.utils.ic_tables import PDB_ATOM_ORDER
 from codlad_amd.utils.protein_module import info_from_residues
 from codlad_amd.utils.xtc import read_xtc, write_xtc
+from tests.cli_script import load_cli
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PARAMS = {"atom_cutoff": 9.0, "cg_cutoff": 21.0, "edgeorder": 2}
 
 
 def cli_module():
-    spec = importlib.util.spec_from_file_location("codlad_cli_cg", os.path.join(ROOT, "test.py"))
-    cli = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(cli)
-    return cli
+    return load_cli("codlad_cli_cg")
 
 
 def strip_to_ca(src, dst, keep=lambda line: True):

@@ -4,7 +4,6 @@ the references of tests/cluster_ref.py against what they restate: all_pairs agai
 against answers derived by hand, and the condition under which the GPU comparison of the bitmaps is exact - no pair of
 the planted and continuum cases lies within msd_bound of its cut-off."""
 import argparse
-import importlib.util
 import json
 import os
 import re
@@ -16,6 +15,7 @@ import torch
 from codlad_amd import _lib, build, metrics
 from tests import cluster_ref as cr
 from tests import ensemble_ref as er
+from tests.cli_script import load_cli, option
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = (("codlad_rmsd_matrix_scratch_bytes", "long long", 2), ("codlad_rmsd_matrix", "int", 13),
@@ -229,9 +229,7 @@ def test_reference_loop_gives_the_hand_derived_answers(name):
 
 
 def test_cli_refuses_a_cluster_cutoff_that_is_not_positive():
-    spec = importlib.util.spec_from_file_location("codlad_cli", os.path.join(ROOT, "test.py"))
-    cli = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(cli)
+    cli = load_cli("codlad_cli")
     a = argparse.Namespace(cluster=None, experiment="latent")
     assert cli.check_cluster(a) == 0.0 and a.cluster == 0.0
     assert cli.check_cluster(argparse.Namespace(cluster=1.5, experiment="latent")) == 1.5
@@ -240,5 +238,8 @@ def test_cli_refuses_a_cluster_cutoff_that_is_not_positive():
             cli.check_cluster(argparse.Namespace(cluster=bad, experiment="latent"))
     with pytest.raises(SystemExit, match="generates none"):
         cli.check_cluster(argparse.Namespace(cluster=1.0, experiment="bpd"))
-    src = open(os.path.join(ROOT, "test.py")).read()
-    assert '"--cluster", type=float' in src and '"--cluster_atoms", choices=("ca", "all"), default="ca"' in src
+    flag, atoms = option(cli, "--cluster"), option(cli, "--cluster_atoms")
+    assert flag.type is float and flag.nargs is None and flag.default is None
+    assert tuple(atoms.choices) == ("ca", "all") and atoms.default == "ca"
+    parsed = cli.build_parser().parse_args(["--cluster", "1.5", "--cluster_atoms", "all"])
+    assert parsed.cluster == 1.5 and parsed.cluster_atoms == "all"

@@ -3,7 +3,6 @@ codlad_hist_divergence (declared once, exported, counted in _SIGS, bad arguments
 sizes), the kernels' registers, what the Python layer and the CLI refuse, and the references of tests/compare_ref.py
 against answers derived by hand."""
 import argparse
-import importlib.util
 import json
 import os
 import re
@@ -15,6 +14,7 @@ import torch
 from codlad_amd import _lib, build, metrics
 from tests import compare_ref as cr
 from tests.test_cluster_host import _FakeCuda
+from tests.cli_script import load_cli, option
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = (("codlad_dist_hist_bytes", "long long", 2), ("codlad_column_hist_bytes", "long long", 2),
@@ -173,9 +173,7 @@ def test_python_layer_refuses_what_it_cannot_run():
 
 
 def test_cli_refuses_what_compare_cannot_run():
-    spec = importlib.util.spec_from_file_location("codlad_cli", os.path.join(ROOT, "test.py"))
-    cli = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(cli)
+    cli = load_cli("codlad_cli")
     a = argparse.Namespace(compare=None, compare_cluster=None, experiment="latent")
     assert cli.check_compare(a) == 0 and a.compare == 0
     assert cli.check_compare(argparse.Namespace(compare=20, compare_cluster=None, experiment="latent")) == 20
@@ -193,8 +191,12 @@ def test_cli_refuses_what_compare_cannot_run():
         cli.check_compare(argparse.Namespace(compare=None, compare_cluster=2.0, experiment="latent"))
     with pytest.raises(SystemExit, match="has no true frames"):
         cli.compare_truth("p", {"x": 1})
-    src = open(os.path.join(ROOT, "test.py")).read()
-    assert '"--compare", type=int, nargs="?", const=50' in src and '"--compare_cluster", type=float, default=None' in src
+    flag, cut = option(cli, "--compare"), option(cli, "--compare_cluster")
+    assert flag.type is int and flag.nargs == "?" and flag.const == 50 and flag.default is None
+    assert cut.type is float and cut.nargs is None and cut.default is None
+    parse = cli.build_parser().parse_args
+    assert parse(["--compare"]).compare == 50 and parse([]).compare is None
+    assert parse(["--compare", "20", "--compare_cluster", "2.5"]).compare_cluster == 2.5
 
 
 def test_reference_divergences_by_hand():

@@ -4,7 +4,6 @@ codlad_ddpm_pred_xstart / codlad_ddim_step - against the reference's own p_mean_
 DDIM update restated (g18 goldens, tests/ddim_cases.py), and `test.py --sampler ddim` end to end.  The CPU part checks the
 coefficient table against the reference's fp32 values, argument validation and the new C entry points."""
 import ctypes
-import importlib.util
 import os
 import subprocess
 import sys
@@ -21,6 +20,7 @@ from codlad_amd.models.latent_model import MPNN_models
 from tests import cases
 from tests import ddim_cases as dc
 from tests import guidance_cases as gc
+from tests.cli_script import load_cli
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = "cuda:0"
@@ -34,10 +34,7 @@ def rel_err(a, b):
 
 
 def cli_module():
-    spec = importlib.util.spec_from_file_location("codlad_cli", os.path.join(ROOT, "test.py"))
-    cli = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(cli)
-    return cli
+    return load_cli("codlad_cli")
 
 
 def case_diffusion(name):

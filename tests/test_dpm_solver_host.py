@@ -2,7 +2,6 @@
 against DDIM, logsnr_timesteps, the analytic Gaussian problem that says what the second order buys (tests/dpm_solver_ref.py),
 argument validation, the CLI's combinations and the two new C entry points."""
 import ctypes
-import importlib.util
 import os
 import re
 import types
@@ -19,6 +18,7 @@ from codlad_amd.models.latent_model import MPNN_models
 from tests import cases
 from tests import dpm_solver_ref as ref
 from tests import guidance_cases as gc
+from tests.cli_script import load_cli
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SPECS = ("10", "ddim10", "logsnr20")
@@ -32,10 +32,7 @@ def close(a, b, scale=None):
 
 
 def cli_module():
-    spec = importlib.util.spec_from_file_location("codlad_cli", os.path.join(ROOT, "test.py"))
-    cli = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(cli)
-    return cli
+    return load_cli("codlad_cli")
 
 
 # ---------------------------------------------------------------------------------------- 1 --

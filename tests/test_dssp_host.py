@@ -18,6 +18,7 @@ import torch
 
 from codlad_amd import _lib, build, metrics
 from tests import dssp_ref as dr
+from tests.cli_script import load_cli
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = ("codlad_dssp_hbonds", "codlad_dssp_assign")
@@ -209,10 +210,7 @@ def test_python_layer_rejects_what_it_cannot_run():
 
 
 def test_cli_allows_dssp_exactly_where_the_geometry_check_is_allowed():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("codlad_cli", os.path.join(ROOT, "test.py"))
-    cli = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(cli)
+    cli = load_cli("codlad_cli")
 
     def args(**kw):
         base = dict(dssp=True, experiment="latent", data_process=False, synthetic=True, cg_pdb=None)

@@ -3,7 +3,6 @@ SVD reference of tests/ensemble_ref.py.
 
 The bound, everywhere: |msd_dev - max(msd_ref, 0)| <= (n + 16) 2^-52 e0 / n with e0 = Ga + Gb (ensemble_ref.msd_bound
 states where it comes from).  Every (size, category, offset) is asserted; none is skipped."""
-import importlib.util
 import os
 
 import numpy as np
@@ -12,6 +11,7 @@ import torch
 
 from codlad_amd import metrics as gm
 from tests import ensemble_ref as er
+from tests.cli_script import load_cli
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -258,10 +258,7 @@ def test_diversity_terms_and_compute_div_against_the_host_loop():
 
 
 def _cli():
-    spec = importlib.util.spec_from_file_location("codlad_cli_superpose", os.path.join(ROOT, "test.py"))
-    cli = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(cli)
-    return cli
+    return load_cli("codlad_cli_superpose")
 
 
 def test_cli_superpose_helper():

@@ -2,7 +2,6 @@
 reference's own matchers and loss_fn), the new entry points' declarations and argument checks, and the refusals of the
 public interface.  No GPU compute here."""
 import ctypes as C
-import importlib.util
 import os
 import re
 import types
@@ -15,6 +14,7 @@ from codlad_amd import _lib
 from codlad_amd.diffusion_and_flow import flow
 from tests import flow_loss_cases as fc
 from tests import flow_loss_ref as fr
+from tests.cli_script import load_cli
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("codlad_fm_path", "codlad_fm_terms", "codlad_fm_loss_forward", "codlad_fm_loss_loop")
@@ -214,9 +214,7 @@ def test_engine_argument_checks():
 
 
 def test_fmloss_needs_a_flow_matching_model():
-    spec = importlib.util.spec_from_file_location("codlad_test_cli", os.path.join(ROOT, "test.py"))
-    cli = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(cli)
+    cli = load_cli("codlad_test_cli")
     base = dict(experiment="fmloss", model="icfm", vae_type="N6", synthetic=True, data_process=False, num_steps=3,
                 fm_sigma=0.0)
     cli.check_fmloss(types.SimpleNamespace(**base), 1)

@@ -4,7 +4,6 @@ callable between the halves of the split step (codlad_ddpm_pred_xstart / codlad_
 reference's own loops (g17 goldens, tests/guidance_cases.py), and `test.py --fix_residues` end to end.  The CPU part
 checks argument validation: PinLatents, the residue spec and the new C entry points."""
 import ctypes
-import importlib.util
 import os
 import subprocess
 import sys
@@ -20,6 +19,7 @@ from codlad_amd.diffusion_and_flow.schedule import Tables, named_betas, space_ti
 from codlad_amd.models.latent_model import MPNN_models
 from tests import cases
 from tests import guidance_cases as gc
+from tests.cli_script import load_cli
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = "cuda:0"
@@ -33,10 +33,7 @@ def rel_err(a, b):
 
 
 def cli_module():
-    spec = importlib.util.spec_from_file_location("codlad_cli", os.path.join(ROOT, "test.py"))
-    cli = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(cli)
-    return cli
+    return load_cli("codlad_cli")
 
 
 # ---------------------------------------------------------------------------------------- CPU --

@@ -13,6 +13,7 @@ from codlad_amd import _lib, synth
 from codlad_amd.diffusion_and_flow.schedule import Tables, named_betas, space_timesteps
 from codlad_amd.weights import denoiser_tensors, decoder_tensors, pack_block
 from tests import cases
+from tests.cli_script import load_cli
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -276,11 +277,8 @@ def test_split_pack_refuses_weights_outside_fp16_range():
 def test_cli_batches_of_one_file_get_distinct_output_names():
     """A data file of more than 96 frames is cut into several batches (reference dataset_module.py:220-226);
     each must land in its own output file (round-1 bug: all chunks were saved under the file's name)."""
-    import importlib.util
     import types
-    spec = importlib.util.spec_from_file_location("codlad_cli", os.path.join(ROOT, "test.py"))
-    cli = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(cli)
+    cli = load_cli("codlad_cli")
     assert cli.chunk_plan(10) == [(0, 10)] and cli.chunk_plan(96) == [(0, 96)]
     assert cli.chunk_plan(200) == [(0, 96), (96, 192), (192, 200)]
     assert cli.output_name("a.pkl", 0, 1) == "a.pkl"

@@ -7,6 +7,7 @@ import torch
 from codlad_amd import metrics as gm
 from oracle import metrics as om
 from tests import cases
+from tests.cli_script import load_cli
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -94,13 +95,8 @@ def test_bond_graph_validity_matches_reference(name):
 def test_cli_evaluation_block_reports_the_reference_summary():
     """test.py's Evaluation (the reference loop's evaluation block, test.py:566-668, on the device): one ensemble
     member of a fabricated batch -> the summary keys the reference prints, values equal to the helper calls."""
-    import importlib.util
-    import os
     import types
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    spec = importlib.util.spec_from_file_location("codlad_cli_eval", os.path.join(root, "test.py"))
-    cli = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(cli)
+    cli = load_cli("codlad_cli_eval")
     d = on_gpu(cases.metric_inputs("small"))
     n_atoms = d["xyz"].shape[0] // 2                                   # two frames of n_atoms atoms
     z = torch.full((2 * n_atoms,), 6.0, device=DEV)

@@ -15,6 +15,7 @@ import torch
 
 from codlad_amd import _lib, metrics
 from tests import observables_ref as obr
+from tests.cli_script import load_cli
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = ("codlad_sasa", "codlad_contact_counts")
@@ -188,10 +189,7 @@ def test_contact_inputs_keep_their_margin():
 
 
 def test_cli_allows_observables_exactly_where_the_geometry_check_is_allowed():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("codlad_cli", os.path.join(ROOT, "test.py"))
-    cli = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(cli)
+    cli = load_cli("codlad_cli")
 
     def args(**kw):
         base = dict(observables=None, experiment="latent", data_process=False, synthetic=True, cg_pdb=None)

@@ -19,6 +19,7 @@ from codlad_amd import _lib, build, metrics
 from codlad_amd.utils.cg_input import template_topology
 from tests import pair_hist_ref as pr
 from tests import saxs_ref as sr
+from tests.cli_script import load_cli
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pd = importlib.import_module("codlad_amd.metrics.pair_distribution")      # metrics.pair_distribution is the function
@@ -259,9 +260,7 @@ def test_contour_length_default_bounds_the_synthetic_structures():
 
 
 def test_cli_allows_pr_exactly_where_observables_are_allowed():
-    spec = importlib.util.spec_from_file_location("codlad_cli", os.path.join(ROOT, "test.py"))
-    cli = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(cli)
+    cli = load_cli("codlad_cli")
 
     def args(**kw):
         base = dict(pr=None, experiment="latent", data_process=False, synthetic=True, cg_pdb=None)

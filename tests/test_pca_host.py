@@ -2,7 +2,6 @@
 arguments refused before any HIP call, the scratch sizes), the kernels' registers, what the Python layer and the CLI refuse,
 and the reference of tests/pca_ref.py against answers derived by hand and against the planted truth."""
 import argparse
-import importlib.util
 import json
 import os
 import re
@@ -14,6 +13,7 @@ import torch
 from codlad_amd import _lib, build, metrics
 from tests import pca_ref as pr
 from tests.test_cluster_host import _FakeCuda
+from tests.cli_script import load_cli, option
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = (("codlad_pca_fit_scratch_bytes", "long long", 2), ("codlad_pca_fit", "int", 19), ("codlad_pca_align", "int", 11),
@@ -181,9 +181,7 @@ def test_python_layer_refuses_what_it_cannot_run():
 
 
 def test_cli_refuses_what_pca_cannot_run():
-    spec = importlib.util.spec_from_file_location("codlad_cli", os.path.join(ROOT, "test.py"))
-    cli = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(cli)
+    cli = load_cli("codlad_cli")
     a = argparse.Namespace(pca=None, experiment="latent")
     assert cli.check_pca(a) == 0 and a.pca == 0
     assert cli.check_pca(argparse.Namespace(pca=10, experiment="latent")) == 10
@@ -197,8 +195,11 @@ def test_cli_refuses_what_pca_cannot_run():
         cli.pca_selection("p", 1366, "all", [1, 5])
     with pytest.raises(SystemExit, match="the CA atoms of p are not known"):
         cli.pca_selection("p", 100, "ca", None)
-    src = open(os.path.join(ROOT, "test.py")).read()
-    assert '"--pca", type=int, nargs="?", const=10' in src and '"--pca_atoms", choices=("ca", "all"), default="ca"' in src
+    flag, atoms = option(cli, "--pca"), option(cli, "--pca_atoms")
+    assert flag.type is int and flag.nargs == "?" and flag.const == 10 and flag.default is None
+    assert tuple(atoms.choices) == ("ca", "all") and atoms.default == "ca"
+    parse = cli.build_parser().parse_args
+    assert parse(["--pca"]).pca == 10 and parse(["--pca", "3", "--pca_atoms", "all"]).pca == 3 and parse([]).pca is None
 
 
 def test_cases_are_the_shapes_the_issue_names():

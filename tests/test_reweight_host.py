@@ -4,7 +4,6 @@ refuse, and the float64 reference of tests/reweight_ref.py against the theory it
 np.longdouble, the weights' normalisation, the large-theta limit, the range of phi_eff, and the secant loop of the fitted
 scale."""
 import argparse
-import importlib.util
 import os
 import re
 
@@ -14,6 +13,7 @@ import torch
 
 from codlad_amd import _lib, build, metrics
 from tests import reweight_ref as rr
+from tests.cli_script import load_cli, option
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GTOL = 1e-9
@@ -222,9 +222,7 @@ def test_secant_loop_finds_the_fixed_point_of_the_scale(N, M):
 
 
 def test_cli_refuses_each_misuse_of_saxs_reweight():
-    spec = importlib.util.spec_from_file_location("codlad_cli", os.path.join(ROOT, "test.py"))
-    cli = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(cli)
+    cli = load_cli("codlad_cli")
 
     def args(**kw):
         base = dict(saxs=51, saxs_data="curve.dat", saxs_reweight=None)
@@ -244,5 +242,7 @@ def test_cli_refuses_each_misuse_of_saxs_reweight():
     for bad in (0.0, -1.0, float("nan"), float("inf")):
         with pytest.raises(SystemExit, match="positive finite number"):
             cli.check_saxs_reweight(args(saxs_reweight=[1.0, bad]))
-    parser_src = open(os.path.join(ROOT, "test.py")).read()
-    assert '"--saxs_reweight", nargs="*", type=float' in parser_src
+    flag = option(cli, "--saxs_reweight")
+    assert flag.nargs == "*" and flag.type is float and flag.default is None
+    parse = cli.build_parser().parse_args
+    assert parse(["--saxs_reweight", "10", "1"]).saxs_reweight == [10.0, 1.0] and parse(["--saxs_reweight"]).saxs_reweight == []

@@ -16,6 +16,7 @@ import torch
 from codlad_amd import _lib, build, metrics
 from codlad_amd.utils.cg_input import template_topology
 from tests import saxs_ref as sr
+from tests.cli_script import load_cli
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 Z = {"H": 1, "C": 6, "N": 7, "O": 8, "P": 15, "S": 16}
@@ -249,10 +250,7 @@ def test_cases_cover_the_sizes_the_issue_names():
 
 
 def test_cli_allows_saxs_exactly_where_observables_are_allowed(tmp_path):
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("codlad_cli", os.path.join(ROOT, "test.py"))
-    cli = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(cli)
+    cli = load_cli("codlad_cli")
 
     def args(**kw):
         base = dict(saxs=None, saxs_data=None, experiment="latent", data_process=False, synthetic=True, cg_pdb=None)

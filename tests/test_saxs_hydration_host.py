@@ -21,6 +21,7 @@ from codlad_amd.metrics import saxs as saxs_mod
 from codlad_amd.utils.cg_input import template_topology
 from tests import saxs_hydration_ref as hr
 from tests import saxs_ref as sr
+from tests.cli_script import load_cli
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -265,10 +266,7 @@ def test_fit64_recovers_a_planted_grid_point():
 
 
 def test_cli_allows_saxs_hydration_only_with_saxs_and_fits_only_with_a_curve():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("codlad_cli", os.path.join(ROOT, "test.py"))
-    cli = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(cli)
+    cli = load_cli("codlad_cli")
 
     def args(**kw):
         base = dict(saxs=51, saxs_data=None, saxs_hydration=None, experiment="latent", data_process=False, synthetic=True, cg_pdb=None)

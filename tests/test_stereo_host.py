@@ -2,7 +2,6 @@
 before any HIP call, `metrics.stereo_tables` lists the right atoms for every residue template and chain end, the CLI
 refuses --stereo_check where it refuses --geometry_check, and the reference the GPU tests compare with
 (tests/stereo_ref.py) returns the angles, inversions and peptide-bond classes its builder planted."""
-import importlib.util
 import os
 import re
 import types
@@ -14,15 +13,13 @@ import torch
 from codlad_amd import _lib, metrics
 from codlad_amd.utils.cg_input import template_topology
 from tests import stereo_ref as sr
+from tests.cli_script import load_cli
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def cli_module():
-    spec = importlib.util.spec_from_file_location("codlad_cli_stereo", os.path.join(ROOT, "test.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+    return load_cli("codlad_cli_stereo")
 
 
 def test_header_declares_and_library_exports_the_entry_point():
