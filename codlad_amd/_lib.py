@@ -139,6 +139,7 @@ PCA_SCALARS, PCA_SC_W, PCA_SC_STEP = 4, 0, 1           # CODLAD_PCA_SCALARS, _SC
 PCA_STATUS = ("converged", "limit", "no_weight")       # CODLAD_PCA_CONVERGED, _LIMIT, _NO_WEIGHT = 0 .. 2
 COMPARE_MAX_ROWS, COMPARE_MAX_BINS, DIST_HIST_MAX_SEL, DIVERGENCE_MAX_COLS = 1048576, 256, 2048, 4098   # CODLAD_COMPARE_MAX_*, ..
 LDDT_MAX_THRESHOLDS, LDDT_MAX_ATOMS = 8, 46340         # CODLAD_LDDT_MAX_THRESHOLDS, _MAX_ATOMS
+POLYMER_MAX_SEL, POLYMER_SPLIT_MAX_N, POLYMER_SPLIT_MIN_SEL = 8192, 256, 512   # CODLAD_POLYMER_MAX_SEL, _SPLIT_MAX_N, _SPLIT_MIN_SEL
 REWEIGHT_STATUS = ("converged", "cap", "stalled", "failed", "none")   # CODLAD_REWEIGHT_CONVERGED .. _NONE = 0 .. 4
 ODE_NORM_WORDS = 257                                   # CODLAD_ODE_NORM_WORDS
 
@@ -197,6 +198,9 @@ _SIGS = {
     "codlad_hist_divergence": (C.c_int, [P, P, C.c_int, C.c_int, P, P, P, P]),
     "codlad_lddt": (C.c_int, [P, C.c_int, P, C.c_int, P, C.c_int, P, C.c_int, P, C.c_int, P, P, P, P, C.c_int, C.c_float, P, C.c_int,
                               C.c_int] + [P] * 11),
+    "codlad_chain_sums_groups": (C.c_int, [C.c_int] * 2),
+    "codlad_chain_sums": (C.c_int, [P, C.c_int, C.c_int, P, C.c_int, P, P, P, P, P]),
+    "codlad_gyration": (C.c_int, [P, C.c_int, C.c_int, P, C.c_int, P, P, P, P, P, P]),
     "codlad_last_error": (C.c_char_p, []),
     "codlad_struct_sizes": (None, [C.POINTER(C.c_int)]),
     "codlad_pack_block_host": (None, [P, C.c_int, C.c_float, P]),

@@ -5,7 +5,8 @@ dssp: secondary structure; saxs: scattering profiles; pair_distribution: typed p
 profiles made from them; reweight: maximum-entropy weights against data; cluster: the all-pairs RMSD matrix of a pool and
 Daura's clustering; pca: the mean structure after mutual superposition, RMSF, covariance and principal components; compare: distance,
 torsion, Rg and cluster-population divergences of two ensembles; lddt: the local distance difference test against the true
-frames; _inputs: what they share."""
+frames; polymer: the chain statistics of a disordered ensemble - hydrodynamic radius, gyration-tensor shape, end-to-end
+distance, internal distance scaling and its Flory exponent; _inputs: what they share."""
 from .. import _lib   # noqa: F401
 from ._inputs import COV_CUTOFF, exclusion_csr   # noqa: F401
 from .recon import *   # noqa: F401,F403 (every public name of a module, C and torch among them as in the module this replaced)
@@ -26,3 +27,4 @@ from .cluster import *   # noqa: F401,F403
 from .pca import *   # noqa: F401,F403 (pca the function takes the module's name here)
 from .compare import *   # noqa: F401,F403
 from .lddt import *   # noqa: F401,F403 (lddt the function takes the module's name here)
+from .polymer import *   # noqa: F401,F403

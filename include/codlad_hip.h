@@ -1620,6 +1620,76 @@ int codlad_lddt(const float *xyz, int n_struct, const float *ref, int n_ref, con
                 int32_t *residue_preserved, double *residue_score, long long *counts, double *score, uint8_t *swapped,
                 uint8_t *finite, long long *scratch, void *stream);
 
+/* Chain statistics of disordered ensembles (csrc/polymer_kernels.hip): what the hydrodynamic radius, the internal
+ * distance scaling R(s) with its Flory exponent, and the shape of the gyration tensor are made of.  Added to ABI version
+ * 19 without changing the number: two new entry points and one size helper, no existing signature, struct or option
+ * changes.
+ *
+ * x [N][n_atoms][3] (device fp32, ONE topology).  sel, device int32 [n_sel], is an ORDERED selection of m = n_sel atoms
+ * (NULL with n_sel 0: all, m = n_atoms): position k of sel is chain position k.  Every entry is clamped into [0, n_atoms)
+ * before it is used, so a wrong table gives wrong sums and never an access out of bounds.
+ *
+ * codlad_chain_sums: for every structure and every separation s = 1 .. m - 1, float64:
+ *   sep_r2  [N][m - 1]   sum over k = 0 .. m - s - 1 of r2(k, k + s)            (element [n][s - 1])
+ *   sep_inv [N][m - 1]   the same sum of 1 / r(k, k + s)
+ *   inv_sum [N]          sum over s of sep_inv[s] = half of Kirkwood's double sum over i != j
+ *   finite  uint8 [N]
+ * Per pair, in float64 from the fp32 coordinates (converted exactly), one rounding per operation in the written order
+ * (no contraction; sqrt and the division are the correctly rounded ones), i = k the lower chain position, j = k + s:
+ *   dx = (double)x_j - (double)x_i per component, r2 = (dx*dx + dy*dy) + dz*dz, r = sqrt(r2), inv = 1.0 / r
+ * The order of every sum, a function of m and s alone: the n = m - s terms of a separation are dealt to the
+ * CODLAD_POLYMER_LANES = 64 lanes of one wave, lane l adds the terms k = l, l + 64, .. to 0 in ascending k, and the 64
+ * partials are added by the xor butterfly with strides 32, 16, .. 1 (lane l takes its own partial plus lane l ^ stride's,
+ * every level).  inv_sum = ((0 + sep_inv[1]) + sep_inv[2]) + .., s ascending, in one chain, by a second launch.
+ * Neither N, nor the grid, nor the structure's place in the batch enters: when N < CODLAD_POLYMER_SPLIT_MAX_N and m >=
+ * CODLAD_POLYMER_SPLIT_MIN_SEL a structure's separations are split across codlad_chain_sums_groups(N, m) workgroups (s
+ * paired with m - s: m terms per pair, equal shares), which changes WHICH wave computes an element and no bit of it.
+ * One writer per element; no atomics, no scratch memory; the bits repeat from call to call.
+ * A structure with a NaN or +-inf coordinate among its SELECTED atoms gets finite = 0 and NaN in its two rows and its
+ * inv_sum; every other structure keeps its bits.  Coincident atoms are no error, the IEEE result stands: r = 0 gives
+ * inv = +inf in that pair's separation and in inv_sum (1 / inv_sum = 0: the caller's Rh is 0), and finite stays 1.
+ * Bounds against the exact sums of the exact per-pair values, first order, with 2^-52 standing for the unit roundoff
+ * 2^-53 (a factor 2 in hand).  Every term is positive, so sum |terms| is the sum itself and the bounds are RELATIVE:
+ *   a term carries at most CODLAD_POLYMER_TERM_OPS = 5 roundings' worth of relative error (r2: two for the squared
+ *   difference, one for the product, two additions; inv: half of r2's five, one for sqrt, one for the division), and a
+ *   term passes through at most ceil(m / 64) additions in its lane and CODLAD_POLYMER_TREE_ADDS = 6 in the butterfly:
+ *   |sep_r2 - exact| <= CODLAD_POLYMER_SUM_BOUND(m) * exact,  the same for sep_inv
+ *   |inv_sum - exact| <= CODLAD_POLYMER_INV_SUM_BOUND(m) * exact     (m - 2 further additions in the chain)
+ * A null pointer (sel excepted), N or n_atoms < 1, sel and n_sel that disagree, m < 2 or m > CODLAD_POLYMER_MAX_SEL
+ * returns -1 (codlad_last_error) before any HIP call.  codlad_chain_sums_groups returns the workgroups per structure (1:
+ * no split), or -1 for N < 1 or m outside 2 .. CODLAD_POLYMER_MAX_SEL; a host function.
+ *
+ * codlad_gyration: per structure, float64, with mom [N][4] from codlad_ens_moments for the same sel (its centroid c):
+ *   tensor [N][6]   (xx, yy, zz, xy, xz, yz) of sum (x - c)(x - c)^T / m: d = (double)x - c per component, six products
+ *                   per atom, lane l of one wave adds the atoms l, l + 64, .. in ascending order, the butterfly above,
+ *                   one correctly rounded division by (double)m
+ *   eig    [N][3]   the eigenvalues of that matrix in ascending order by cyclic Jacobi (a sweep starts while off(A)^2 >
+ *                   2^-120 ||A||_F^2, so at most CODLAD_POLYMER_JACOBI_STOP = 2^-60 of the norm is left), clamped at 0
+ *   ree    [N]      sqrt(r2) of the first and the last selected atom, the per-pair sequence above
+ *   finite uint8 [N]: 0 for a NaN or +-inf among the selected atoms; then tensor, eig and ree are NaN.
+ * |tensor - exact| <= CODLAD_POLYMER_TENSOR_BOUND(m) * trace, element by element, against the tensor about the EXACT
+ * centroid: three roundings per term (two differences, the product; |dx dy| <= (dx^2 + dy^2) / 2, so an off-diagonal's
+ * sum |terms| / m is at most the trace), the additions of the sum above and the division.  The rounding of c enters in
+ * second order only (sum (x - c) = 0 about the exact centroid: what is left is |dc|^2, below the bound while the
+ * centroid is less than 2^16 radii of gyration from the origin).  No atomics, one writer per element.
+ * A null pointer (sel excepted), N or n_atoms < 1, sel and n_sel that disagree or m > CODLAD_POLYMER_MAX_SEL returns -1
+ * before any HIP call. */
+#define CODLAD_POLYMER_MAX_SEL 8192
+#define CODLAD_POLYMER_SPLIT_MAX_N 256
+#define CODLAD_POLYMER_SPLIT_MIN_SEL 512
+#define CODLAD_POLYMER_LANES 64
+#define CODLAD_POLYMER_TERM_OPS 5
+#define CODLAD_POLYMER_TREE_ADDS 6
+#define CODLAD_POLYMER_SUM_BOUND(m) ((((m) + 63) / 64 + 11.0) * 2.220446049250313e-16)
+#define CODLAD_POLYMER_INV_SUM_BOUND(m) ((((m) + 63) / 64 + 11.0 + ((m) - 2.0)) * 2.220446049250313e-16)
+#define CODLAD_POLYMER_TENSOR_BOUND(m) ((((m) + 63) / 64 + 10.0) * 2.220446049250313e-16)
+#define CODLAD_POLYMER_JACOBI_STOP 8.673617379884035e-19
+int codlad_chain_sums_groups(int N, int m);
+int codlad_chain_sums(const float *x, int N, int n_atoms, const int32_t *sel, int n_sel, double *sep_r2, double *sep_inv,
+                      double *inv_sum, uint8_t *finite, void *stream);
+int codlad_gyration(const float *x, int N, int n_atoms, const int32_t *sel, int n_sel, const double *mom, double *tensor,
+                    double *eig, double *ree, uint8_t *finite, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
