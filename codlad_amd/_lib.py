@@ -140,6 +140,7 @@ PCA_STATUS = ("converged", "limit", "no_weight")       # CODLAD_PCA_CONVERGED, _
 COMPARE_MAX_ROWS, COMPARE_MAX_BINS, DIST_HIST_MAX_SEL, DIVERGENCE_MAX_COLS = 1048576, 256, 2048, 4098   # CODLAD_COMPARE_MAX_*, ..
 LDDT_MAX_THRESHOLDS, LDDT_MAX_ATOMS = 8, 46340         # CODLAD_LDDT_MAX_THRESHOLDS, _MAX_ATOMS
 POLYMER_MAX_SEL, POLYMER_SPLIT_MAX_N, POLYMER_SPLIT_MIN_SEL = 8192, 256, 512   # CODLAD_POLYMER_MAX_SEL, _SPLIT_MAX_N, _SPLIT_MIN_SEL
+DRMSD_MAX_SEL, DRMSD_WINDOW, DRMSD_SLAB_TILES, DRMSD_SPLIT_MAX_BLOCKS = 8192, 16, 64, 256   # CODLAD_DRMSD_MAX_SEL, _WINDOW, _SLAB_TILES, ..
 REWEIGHT_STATUS = ("converged", "cap", "stalled", "failed", "none")   # CODLAD_REWEIGHT_CONVERGED .. _NONE = 0 .. 4
 ODE_NORM_WORDS = 257                                   # CODLAD_ODE_NORM_WORDS
 
@@ -201,6 +202,10 @@ _SIGS = {
     "codlad_chain_sums_groups": (C.c_int, [C.c_int] * 2),
     "codlad_chain_sums": (C.c_int, [P, C.c_int, C.c_int, P, C.c_int, P, P, P, P, P]),
     "codlad_gyration": (C.c_int, [P, C.c_int, C.c_int, P, C.c_int, P, P, P, P, P, P]),
+    "codlad_drmsd_groups": (C.c_int, [C.c_int] * 4),
+    "codlad_drmsd_matrix_scratch_bytes": (C.c_longlong, [C.c_int] * 4),
+    "codlad_drmsd_matrix": (C.c_int, [P, C.c_int, P, C.c_int, C.c_int, P, C.c_int, C.c_int, C.c_double, C.c_int, P, P, P, P, P, P]),
+    "codlad_drmsd_pairs": (C.c_int, [P, C.c_int, P, C.c_int, C.c_int, P, C.c_int, C.c_int, P, C.c_int, P, P, P]),
     "codlad_last_error": (C.c_char_p, []),
     "codlad_struct_sizes": (None, [C.POINTER(C.c_int)]),
     "codlad_pack_block_host": (None, [P, C.c_int, C.c_float, P]),

@@ -6,7 +6,8 @@ profiles made from them; reweight: maximum-entropy weights against data; cluster
 Daura's clustering; pca: the mean structure after mutual superposition, RMSF, covariance and principal components; compare: distance,
 torsion, Rg and cluster-population divergences of two ensembles; lddt: the local distance difference test against the true
 frames; polymer: the chain statistics of a disordered ensemble - hydrodynamic radius, gyration-tensor shape, end-to-end
-distance, internal distance scaling and its Flory exponent; _inputs: what they share."""
+distance, internal distance scaling and its Flory exponent; drmsd: the superposition-free distance RMSD of every pair of a
+pool or of two pools, of a list of pairs, and Daura's clustering at a dRMSD cut-off; _inputs: what they share."""
 from .. import _lib   # noqa: F401
 from ._inputs import COV_CUTOFF, exclusion_csr   # noqa: F401
 from .recon import *   # noqa: F401,F403 (every public name of a module, C and torch among them as in the module this replaced)
@@ -28,3 +29,4 @@ from .pca import *   # noqa: F401,F403 (pca the function takes the module's name
 from .compare import *   # noqa: F401,F403
 from .lddt import *   # noqa: F401,F403 (lddt the function takes the module's name here)
 from .polymer import *   # noqa: F401,F403
+from .drmsd import *   # noqa: F401,F403

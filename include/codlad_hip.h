@@ -1690,6 +1690,84 @@ int codlad_chain_sums(const float *x, int N, int n_atoms, const int32_t *sel, in
 int codlad_gyration(const float *x, int N, int n_atoms, const int32_t *sel, int n_sel, const double *mom, double *tensor,
                     double *eig, double *ree, uint8_t *finite, void *stream);
 
+/* Superposition-free distance RMSD (csrc/drmsd_kernels.hip): for two conformations a and b over the P pairs (k, l) of an
+ * ordered selection, dRMSD(a, b) = sqrt(sum (d_kl(a) - d_kl(b))^2 / P) - the structural distance that means something for
+ * a disordered chain, where no frame makes a global superposition meaningful.  Added to ABI version 19 without changing
+ * the number: four new entry points, no existing signature, struct or option changes.
+ *
+ * The pairs: positions k < l of the selection with l - k >= min_sep (min_sep >= 1; 2 or 3 drop the constant neighbour
+ * distances of a CA trace), P = (m - min_sep)(m - min_sep + 1) / 2 of them.  sel, device int32 [n_sel], is an ORDERED
+ * selection of m = n_sel atoms (NULL with n_sel 0: all, m = n_atoms); position k of sel is chain position k; every entry is
+ * clamped into [0, n_atoms) before it is used.  The distance of a pair is fp32, pair_hist_kernels.hip's sequence:
+ *   dx = x_l - x_k per component (fp32), d = sqrtf((dx*dx + dy*dy) + dz*dz), one rounding per operation
+ * and everything after d is float64.  dRMSD is DEFINED on these fp32 distances (their relative 6e-8 is far below any
+ * cut-off anyone clusters at): the product of two of them is exact in float64, so the Gram route below rounds in its
+ * additions alone.
+ *
+ * codlad_drmsd_matrix: every pair of the structures of one pool x [Na][n_atoms][3] (y NULL, Nb 0: msd [Na][Na], Na <=
+ * CODLAD_CLUSTER_MAX_N), or every structure of x against every structure of y [Nb][n_atoms][3] (cross mode: msd
+ * [Na][Nb], no bitmap).  2 <= m <= CODLAD_DRMSD_MAX_SEL.
+ *   msd_ij = max(G_i + G_j - 2 C_ij, 0) / P,   C_ij = sum_p d_p(i) d_p(j),   G_i = C_ii
+ * as ONE float64 matrix product on v_mfma_f64_16x16x4_f64 whose K dimension is the pair index and whose operand is made
+ * inside the kernel from the coordinates, never stored.  A workgroup owns a 64 x 64 block of structure pairs (one pool:
+ * J >= I only, the element and its mirror written by the same lane from the same value).
+ * The pair order, a function of (m, min_sep) alone: the triangle of positions is cut into windows of CODLAD_DRMSD_WINDOW
+ * x CODLAD_DRMSD_WINDOW positions (rows k, columns l), the windows on or above the diagonal taken row by row, the
+ * 256 slots of a window row by row; a slot that is no pair (l - k < min_sep, k or l >= m) is an exact zero in both
+ * operands, as is every slot of a structure that is not finite.  CODLAD_DRMSD_SLAB_TILES consecutive windows are a
+ * slab.  Every slab's products are accumulated from zero, in slot order, and the slabs' partial sums are added to zero
+ * in ascending slab order - whether one workgroup ran all slabs of its block, or (few blocks, many pairs) a workgroup
+ * per slab wrote its partial block and a finishing launch added them: the split changes WHICH workgroup computes an
+ * element and no bit of it.  The split is taken when there is more than one slab, the call has fewer than
+ * CODLAD_DRMSD_SPLIT_MAX_BLOCKS blocks and the partial blocks (32 KiB each) fit CODLAD_DRMSD_SCRATCH_BUDGET bytes;
+ * codlad_drmsd_groups returns the workgroups per block (1: no split).
+ * G_i is C_ii BY THE SAME SEQUENCE (a first launch over the diagonal blocks, the same kernel body), and the products
+ * are exact, so two structures with identical distance vectors - a duplicate, a mirror image, a copy moved by an
+ * fp32-exact translation - are at exactly 0 of each other at any two indices, and Daura treats them as one.  An element
+ * depends on its two structures, sel and min_sep alone: not on N, its place in the pool or in a block, or which of the
+ * two is the row.  No atomics, no scratch memory of the kernels' own, one writer per element; the bits repeat.
+ *   msd     device float64 [Na][Na] / [Na][Nb] or NULL: the msd with squared != 0, else its square root; the diagonal
+ *           of one pool is 0; rows and columns of a structure with a NaN or an infinity among its selected atoms are NaN
+ *   bits    device uint64 [Na][ceil(Na / 64)] or NULL (one pool only): codlad_rmsd_matrix's layout, bit j set iff both
+ *           structures are finite and msd_ij <= cut2 (the diagonal bit of a finite structure set, bits at j >= Na zero)
+ *   finite_x uint8 [Na], finite_y uint8 [Nb] (cross mode only)
+ *   scratch device, codlad_drmsd_matrix_scratch_bytes(Na, Nb, n_sel, min_sep) bytes (n_sel = m; written before read)
+ * Bound, against the exact sums of the fp32 distances: one rounding per accumulated product covers any order of
+ * addition inside a K step and between slabs (a sum of P non-negative terms in any order is within (P - 1) roundings of
+ * relative error), for each of G_i, G_j and C_ij; two additions and the division on top; 2^-52 stands for 2^-53:
+ *   |msd - exact| <= CODLAD_DRMSD_MATRIX_BOUND(P) * (G_i + G_j + 2 C_ij) / P
+ * Finite coordinates whose differences overflow fp32 give the IEEE result (inf or NaN), and finite stays 1.
+ *
+ * codlad_drmsd_pairs: for the pairs int32 [K][2] (index into a [na][n_atoms][3], index into b [nb][n_atoms][3]) the
+ * direct sum, no cancellation: term = (double)d_kl(a) - (double)d_kl(b), squared.  A workgroup of four waves per pair;
+ * wave w takes the positions k = w, w + 4, ..; for a position its lanes add the terms of the partners l = lane, lane + 64,
+ * .. (|l - k| >= min_sep, BOTH sides of k) in ascending l, the 64 partials by the xor butterfly 32 .. 1: row_k.  A wave adds
+ * its rows in ascending k, the four waves are added in ascending order, and msd = (that sum / 2) / P: every pair was
+ * met from both ends.  The order is a function of (m, min_sep) alone.
+ *   msd      float64 [K]       (the msd; NaN for a pair with a structure that is not finite or an index out of range)
+ *   position float64 [K][m] or NULL: row_k / (the partners of k): where the two structures differ (NaN without partners)
+ *   |msd - exact| <= CODLAD_DRMSD_PAIRS_BOUND(m) * exact: two roundings per term, ceil(m / 64) additions in the lane,
+ *   6 in the butterfly, ceil(m / 4) in the wave, 3 across the waves, the division;
+ *   |position - exact| <= CODLAD_DRMSD_POSITION_BOUND(m) * exact: the term, the lane, the butterfly, the division.
+ * A null pointer (sel, y, msd or bits, position excepted), a size < 1, m outside 2 .. CODLAD_DRMSD_MAX_SEL, min_sep
+ * outside 1 .. m - 1, sel and n_sel that disagree, neither msd nor bits, bits in cross mode or a cut2 that is no finite
+ * number >= 0 return -1 (codlad_last_error) before any HIP call; the two size helpers are host functions. */
+#define CODLAD_DRMSD_MAX_SEL 8192
+#define CODLAD_DRMSD_WINDOW 16
+#define CODLAD_DRMSD_SLAB_TILES 64
+#define CODLAD_DRMSD_SPLIT_MAX_BLOCKS 256
+#define CODLAD_DRMSD_SCRATCH_BUDGET 268435456
+#define CODLAD_DRMSD_MATRIX_BOUND(P) (((P) + 3.0) * 2.220446049250313e-16)
+#define CODLAD_DRMSD_PAIRS_BOUND(m) ((((m) + 63) / 64 + ((m) + 3) / 4 + 12.0) * 2.220446049250313e-16)
+#define CODLAD_DRMSD_POSITION_BOUND(m) ((((m) + 63) / 64 + 9.0) * 2.220446049250313e-16)
+int codlad_drmsd_groups(int Na, int Nb, int n_sel, int min_sep);
+long long codlad_drmsd_matrix_scratch_bytes(int Na, int Nb, int n_sel, int min_sep);
+int codlad_drmsd_matrix(const float *x, int Na, const float *y, int Nb, int n_atoms, const int32_t *sel, int n_sel,
+                        int min_sep, double cut2, int squared, double *msd, uint64_t *bits, uint8_t *finite_x,
+                        uint8_t *finite_y, void *scratch, void *stream);
+int codlad_drmsd_pairs(const float *a, int na, const float *b, int nb, int n_atoms, const int32_t *sel, int n_sel,
+                       int min_sep, const int32_t *pairs, int K, double *msd, double *position, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
