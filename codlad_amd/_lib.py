@@ -141,6 +141,7 @@ COMPARE_MAX_ROWS, COMPARE_MAX_BINS, DIST_HIST_MAX_SEL, DIVERGENCE_MAX_COLS = 104
 LDDT_MAX_THRESHOLDS, LDDT_MAX_ATOMS = 8, 46340         # CODLAD_LDDT_MAX_THRESHOLDS, _MAX_ATOMS
 POLYMER_MAX_SEL, POLYMER_SPLIT_MAX_N, POLYMER_SPLIT_MIN_SEL = 8192, 256, 512   # CODLAD_POLYMER_MAX_SEL, _SPLIT_MAX_N, _SPLIT_MIN_SEL
 DRMSD_MAX_SEL, DRMSD_WINDOW, DRMSD_SLAB_TILES, DRMSD_SPLIT_MAX_BLOCKS = 8192, 16, 64, 256   # CODLAD_DRMSD_MAX_SEL, _WINDOW, _SLAB_TILES, ..
+TORSION_MAX_T, TORSION_X_OPS, TORSION_Y_OPS = 2048, 11, 13   # CODLAD_TORSION_MAX_T, _X_OPS, _Y_OPS
 REWEIGHT_STATUS = ("converged", "cap", "stalled", "failed", "none")   # CODLAD_REWEIGHT_CONVERGED .. _NONE = 0 .. 4
 ODE_NORM_WORDS = 257                                   # CODLAD_ODE_NORM_WORDS
 
@@ -206,6 +207,14 @@ _SIGS = {
     "codlad_drmsd_matrix_scratch_bytes": (C.c_longlong, [C.c_int] * 4),
     "codlad_drmsd_matrix": (C.c_int, [P, C.c_int, P, C.c_int, C.c_int, P, C.c_int, C.c_int, C.c_double, C.c_int, P, P, P, P, P, P]),
     "codlad_drmsd_pairs": (C.c_int, [P, C.c_int, P, C.c_int, C.c_int, P, C.c_int, C.c_int, P, C.c_int, P, P, P]),
+    "codlad_torsion_features": (C.c_int, [P, C.c_int, C.c_int, P, C.c_int, P, P, P]),
+    "codlad_torsion_mean_scratch_bytes": (C.c_longlong, [C.c_int] * 2),
+    "codlad_torsion_mean": (C.c_int, [P, P, P, C.c_int, C.c_int, P, P, P, P, P]),
+    "codlad_torsion_matrix_scratch_bytes": (C.c_longlong, [C.c_int] * 2),
+    "codlad_torsion_matrix": (C.c_int, [P, P, C.c_int, P, P, C.c_int, C.c_int, C.c_double, C.c_int, P, P, P, P]),
+    "codlad_torsion_pairs": (C.c_int, [P, C.c_int, P, C.c_int, C.c_int, P, C.c_int, P, P, P]),
+    "codlad_feature_covariance_scratch_bytes": (C.c_longlong, [C.c_int] * 2),
+    "codlad_feature_covariance": (C.c_int, [P, P, P, C.c_int, C.c_int, P, P, P, P, P]),
     "codlad_last_error": (C.c_char_p, []),
     "codlad_struct_sizes": (None, [C.POINTER(C.c_int)]),
     "codlad_pack_block_host": (None, [P, C.c_int, C.c_float, P]),

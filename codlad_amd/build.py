@@ -18,7 +18,7 @@ SOURCES = ["api.hip", "host_util.hip", "edge_plan.hip", "denoiser_forward.hip", 
            "geometry_kernels.hip", "stereo_kernels.hip", "relax_kernels.hip", "observables_kernels.hip", "dssp_kernels.hip", "saxs_kernels.hip",
            "saxs_hydration_kernels.hip", "pair_hist_kernels.hip", "reweight_kernels.hip", "cluster_kernels.hip",
            "pca_kernels.hip", "compare_kernels.hip", "lddt_kernels.hip", "polymer_kernels.hip",
-           "drmsd_kernels.hip"]
+           "drmsd_kernels.hip", "torsion_kernels.hip"]
 # Geometry / VQ kernels must round like the reference's unfused CPU ops (bit-exact neighbour lists
 # and code indices): no implicit FMA contraction there; intended FMAs are written as fmaf().
 EXTRA_FLAGS = {"features_kernels.hip": ["-ffp-contract=off"], "ode_kernels.hip": ["-ffp-contract=off"], "decode_kernels.hip": ["-ffp-contract=off"],
@@ -61,6 +61,9 @@ EXTRA_FLAGS = {"features_kernels.hip": ["-ffp-contract=off"], "ode_kernels.hip":
                "polymer_kernels.hip": ["-ffp-contract=off"],
                # the fp32 distance is pair_hist_kernels.hip's sequence and every float64 sum has one order; the MFMA is asked for by name
                "drmsd_kernels.hip": ["-ffp-contract=off"],
+               # the float64 feature sequence is restated in numpy to the bit and every sum has one order; the MFMA and the
+               # fused multiply-adds of the mean are asked for by name
+               "torsion_kernels.hip": ["-ffp-contract=off"],
                "metrics_kernels.hip": ["-ffp-contract=off"], "encoder_kernels.hip": ["-ffp-contract=off"],
                # the SLP vectoriser pairs multiply-adds of different result blocks into v_pk_fma_f32 and pays for it in register
                # moves (337 -> 80 v_mov at depth 0, 14 scratch accesses -> 0 at depth 2 without it)

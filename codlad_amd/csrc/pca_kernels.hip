@@ -24,6 +24,8 @@
 //                   A row of a panel is 64 + 16 doubles, so the four k of an operand start on other banks.
 //   cov_reduce_kernel  the chunks of an element in ascending order, / W, the element and its mirror from the one value
 //   corr_kernel     the per-atom cross-correlation and the trace
+//   trace_kernel    the trace alone, for codlad_feature_covariance: cov_kernel and cov_reduce_kernel on a table of any
+//                   dimension d (torsion features; the 3 x 3 blocks of corr_kernel are what asks d % 3 == 0)
 // The structures are cut into at most 32 chunks whose size depends on N alone (reduce_math.h's chunks_of).  No atomics, no scratch memory.
 //
 // The eigenpairs: blocked subspace iteration with a Rayleigh-Ritz step on b = min(k + 8, d) <= 72 columns, every block
@@ -791,6 +793,35 @@ extern "C" int codlad_pca_covariance(const double *D, const double *w, const uin
     hipLaunchKernelGGL(pca_corr_kernel, dim3((unsigned)(((long long)m * m + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st,
                        (const double *)cov, d, m, corr, total);
     return codlad_check_launch("codlad_pca_covariance");
+}
+
+// the diagonal of C in ascending order, as pca_corr_kernel's block 0 adds it
+namespace {
+__global__ void pca_trace_kernel(const double *C, int d, double *total) {
+    double s = 0.0;
+    for (int i = 0; i < d; ++i) s += C[(size_t)i * d + i];
+    *total = s;
+}
+}  // namespace
+
+extern "C" long long codlad_feature_covariance_scratch_bytes(int N, int d) {
+    CODLAD_REQUIRE(N > 0 && N <= MAX_N && d > 0 && d <= MAX_D, "bad sizes (1 <= N <= CODLAD_PCA_MAX_N, 1 <= d <= CODLAD_PCA_MAX_DIM)");
+    return 8ll * chunks_of(N).nch * tri_tiles_of(d, TILE) * TILE * TILE;
+}
+
+extern "C" int codlad_feature_covariance(const double *D, const double *w, const uint8_t *finite, int N, int d, const double *scal,
+                                         double *cov, double *total, void *scratch, void *stream) {
+    CODLAD_REQUIRE(D && finite && scal && cov && total && scratch, "null pointer");
+    CODLAD_REQUIRE(N > 0 && N <= MAX_N && d > 0 && d <= MAX_D, "bad sizes (1 <= N <= CODLAD_PCA_MAX_N, 1 <= d <= CODLAD_PCA_MAX_DIM)");
+    const Chunks c = chunks_of(N);
+    Cov p;
+    p.D = D, p.w = w, p.scal = scal, p.finite = finite, p.N = N, p.d = d, p.ntiles = tri_tiles_of(d, TILE);
+    p.nch = c.nch, p.chunk = c.chunk, p.part = (double *)scratch, p.C = cov;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(pca_cov_kernel, dim3((unsigned)p.ntiles, (unsigned)p.nch), dim3(CT), 0, st, p);
+    hipLaunchKernelGGL(pca_cov_reduce_kernel, dim3((unsigned)p.ntiles), dim3(BLOCK), 0, st, p);
+    hipLaunchKernelGGL(pca_trace_kernel, dim3(1), dim3(1), 0, st, (const double *)cov, d, total);
+    return codlad_check_launch("codlad_feature_covariance");
 }
 
 extern "C" long long codlad_pca_eigen_scratch_bytes(int d, int k) {

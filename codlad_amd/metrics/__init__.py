@@ -7,7 +7,9 @@ Daura's clustering; pca: the mean structure after mutual superposition, RMSF, co
 torsion, Rg and cluster-population divergences of two ensembles; lddt: the local distance difference test against the true
 frames; polymer: the chain statistics of a disordered ensemble - hydrodynamic radius, gyration-tensor shape, end-to-end
 distance, internal distance scaling and its Flory exponent; drmsd: the superposition-free distance RMSD of every pair of a
-pool or of two pools, of a list of pairs, and Daura's clustering at a dRMSD cut-off; _inputs: what they share."""
+pool or of two pools, of a list of pairs, and Daura's clustering at a dRMSD cut-off; torsion: the ensemble in its torsion
+angles - (cos, sin) features, circular statistics, dihedral PCA, the torsion distance of every pair and Daura's clustering
+at a torsion cut-off; _inputs: what they share."""
 from .. import _lib   # noqa: F401
 from ._inputs import COV_CUTOFF, exclusion_csr   # noqa: F401
 from .recon import *   # noqa: F401,F403 (every public name of a module, C and torch among them as in the module this replaced)
@@ -30,3 +32,4 @@ from .compare import *   # noqa: F401,F403
 from .lddt import *   # noqa: F401,F403 (lddt the function takes the module's name here)
 from .polymer import *   # noqa: F401,F403
 from .drmsd import *   # noqa: F401,F403
+from .torsion import *   # noqa: F401,F403

@@ -1768,6 +1768,107 @@ int codlad_drmsd_matrix(const float *x, int Na, const float *y, int Nb, int n_at
 int codlad_drmsd_pairs(const float *a, int na, const float *b, int nb, int n_atoms, const int32_t *sel, int n_sel,
                        int min_sep, const int32_t *pairs, int K, double *msd, double *position, void *stream);
 
+/* Torsion-space analysis of an ensemble (csrc/torsion_kernels.hip, and codlad_feature_covariance in csrc/pca_kernels.hip):
+ * every structure as the unit vectors f_t = (cos theta_t, sin theta_t) of its T torsions, the periodicity-free
+ * representation of dihedral PCA (Mu, Nguyen and Stock 2005), and what is made of that table - circular statistics, the
+ * covariance for dPCA, the torsion distance of every pair.  Added to ABI version 19 without changing the number: eight new
+ * entry points, no existing signature, struct or option changes.  1 <= T <= CODLAD_TORSION_MAX_T (2 T <=
+ * CODLAD_PCA_MAX_DIM), 1 <= N <= CODLAD_CLUSTER_MAX_N.
+ *
+ * codlad_torsion_features: x [N][n_atoms][3] (device fp32), quads int32 [T][4] (device; every index is clamped into [0,
+ * n_atoms) before it is used - the caller checks them) -> F double [N][2 T] laid out (cos_0, sin_0, cos_1, sin_1, ..) and
+ * finite uint8 [N].  Per torsion p0-p1-p2-p3 (IUPAC sign), in float64 after the exact fp32 -> fp64 conversion of the
+ * coordinates, one rounding per operation in the written order, no contraction, sqrt and / the correctly rounded ones, no
+ * transcendental (a float64 numpy restatement gives the same bits):
+ *   b1 = p1 - p0, b2 = p2 - p1, b3 = p3 - p2                                   (per component)
+ *   cross(a, b) = (a.y*b.z - a.z*b.y,  a.z*b.x - a.x*b.z,  a.x*b.y - a.y*b.x),   dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z
+ *   n1 = cross(b1, b2), n2 = cross(b2, b3)
+ *   x = dot(n1, n2),  y = sqrt(dot(b2, b2)) * dot(b1, n2),  h = sqrt(x*x + y*y),  cos = x / h,  sin = y / h
+ * (relax_kernels.hip's torsion() in float64).  A structure gets finite = 0 and a row of NaN when, among its quads, an
+ * atom has a NaN or +-inf coordinate or a torsion has h == 0 (collinear atoms: no angle) or a NaN h; every other structure
+ * keeps its bits.  An atom that no quad names is never read.  One writer per element, no atomics, no scratch memory.
+ * Bound, first order, 2^-52 standing for the unit roundoff 2^-53.  With X = the value of x when every product of four
+ * bond components it expands into is taken by its absolute value (dot(|n1|, |n2|) with |n| = cross with + for -), Y the
+ * same for y: a product of x passes through CODLAD_TORSION_X_OPS = 11 roundings (four differences, the two products and
+ * the two subtractions of the crosses, the product and two additions of the dot), one of y through
+ * CODLAD_TORSION_Y_OPS = 13 (3.5 for |b2|: five of dot(b2, b2) halved by the root, the root; 8 for dot(b1, n2); the
+ * product), so |x - exact| <= 11 u X, |y - exact| <= 13 u Y, and through h (two roundings' worth) and the division
+ *   |cos - exact|, |sin - exact| <= CODLAD_TORSION_FEATURE_BOUND(r),  r = (11 X + 13 Y) / h
+ * The bound grows as 1 / h: a nearly collinear quad is ill-conditioned (X and Y stay, h goes to 0) and the bound says so.
+ *
+ * codlad_torsion_mean: the weighted resultant mean [2 T] = sum_s w_s F_s / W over the structures with finite != 0 and
+ * w_s > 0 (w NULL: 1), scal [CODLAD_PCA_SCALARS] with W at CODLAD_PCA_SC_W (the rest NaN), and optionally D [N][2 T] = F -
+ * mean (NaN rows where finite is 0; one rounding).  The structures are cut into codlad_pca_fit's chunks (at most 32, a
+ * size that depends on N alone); per element the structures of a chunk are added to 0 in ascending order by fused
+ * multiply-adds fma(w_s, F_se, acc), the chunks are added to 0 in ascending order, then one division by W.  W: per chunk,
+ * lane l of one wave adds the weights of the chunk's structures l, l + 64, .. to 0 in ascending order, the 64 partials by
+ * the xor butterfly (strides 32 .. 1), the chunks to 0 in ascending order.  A weight enters as one exact factor, so
+ * uniform weights that are a power of two give the bits of w NULL.  No structure of positive weight: 0 / 0, NaN.
+ *   |mean - exact| <= CODLAD_TORSION_MEAN_BOUND(N) * sum_s w_s |F_se| / W: c for a chunk of at most c =
+ *   CODLAD_TORSION_CHUNK_MAX(N) structures, 32 for the chunks, the division; for W c / 64 + 1 in the lane, 6 in the
+ *   butterfly, 32 for the chunks
+ *   scratch: codlad_torsion_mean_scratch_bytes(N, T) bytes, written before read
+ *
+ * codlad_torsion_matrix: tmsd_ij = max(G_i + G_j - 2 C_ij, 0) / T with C = F F^T (K = 2 T) and G_i = C_ii, whose root is
+ * the TORSION DISTANCE |f_i - f_j| / sqrt(T) = sqrt((1 / T) sum_t 2 (1 - cos(theta_t(i) - theta_t(j)))): the RMS angular
+ * difference in radians for small differences, at most 2.  One float64 matrix product on v_mfma_f64_16x16x4_f64; a
+ * workgroup owns 64 x 64 structure pairs (one pool: the blocks J >= I only, an element and its mirror written by one lane
+ * from one value).  Every element has ONE accumulator that starts at +0 and takes the MFMA steps of four features in
+ * ascending order; features past 2 T and the rows of a structure that is not finite are zeros.  G_i is C_ii BY THE SAME
+ * SEQUENCE (a first launch over the diagonal blocks, the same kernel body), and a product does not depend on which
+ * factor is the row, so C_ij = C_ji to the bit and two structures with equal features - a duplicate, an fp32-exact
+ * translate - are at exactly 0 of each other at any two indices.  An element depends on its two rows of F and T alone.
+ *   Fx [Na][2 T], finite_x [Na]; Fy [Nb][2 T], finite_y [Nb] or both NULL with Nb 0 (one pool).  The tables are 16-byte
+ *   aligned (a row is read as (cos, sin) pairs).
+ *   tmsd    device float64 [Na][Na] / [Na][Nb] or NULL: tmsd with squared != 0, else its square root; the diagonal of one
+ *           pool is 0; rows and columns of a structure with finite == 0 are NaN
+ *   bits    device uint64 [Na][ceil(Na / 64)] or NULL (one pool only): codlad_rmsd_matrix's layout, bit j set iff both
+ *           structures are finite and tmsd_ij <= cut2 (the diagonal bit of a finite structure set, bits at j >= Na zero)
+ *   scratch device, codlad_torsion_matrix_scratch_bytes(Na, Nb) bytes (G of both pools; written before read)
+ * Bound against the exact sums over the float64 features: a product carries one rounding and passes through at most 2 T
+ * additions, whatever the order inside an MFMA step: (2 T + 1) u sum |terms| for each of G_i, G_j and C_ij, and
+ * 2 sum_t |f_i f_j| <= G_i + G_j; two additions and the division on top (the "+ 3"; 2^-52 stands for 2^-53):
+ *   |tmsd - exact| <= CODLAD_TORSION_MATRIX_BOUND(T) * (G_i + G_j + 2 |C_ij|) / T
+ *
+ * codlad_torsion_pairs: for the pairs int32 [K][2] (row of Fa [na][2 T], row of Fb [nb][2 T]) the direct sum, no
+ * cancellation: dc = cos_a - cos_b, ds = sin_a - sin_b, term_t = dc*dc + ds*ds.  A wave per pair: lane l adds the terms t
+ * = l, l + 64, .. to 0 in ascending order, the 64 partials by the xor butterfly (strides 32 .. 1), one division by T: the
+ * order is a function of T alone.  tmsd float64 [K] (NaN for a row of NaN or an index out of range); terms float64 [K][T]
+ * or NULL: term_t, where the two structures differ.
+ *   |term - exact| <= CODLAD_TORSION_TERM_BOUND * exact (two roundings for each squared difference, the product, the sum)
+ *   |tmsd - exact| <= CODLAD_TORSION_PAIRS_BOUND(T) * exact: the term, ceil(T / 64) in the lane, 6 in the butterfly, the division
+ *
+ * codlad_feature_covariance: codlad_pca_covariance's two launches (the same kernels, the same bits, the same bound (N +
+ * 34) 2^-52 T_ij) on a deviation table D [N][d] of ANY 1 <= d <= CODLAD_PCA_MAX_DIM - the 3 x 3 correlation blocks are what
+ * asks d % 3 == 0 of that entry - and total [1] = trace(C), the diagonal added to 0 in ascending order.  scal: W at
+ * CODLAD_PCA_SC_W.  codlad_pca_eigen and codlad_pca_project take any d and are used as they are.
+ *
+ * A null pointer (w, D of the mean, Fy and finite_y, tmsd or bits, terms excepted), a size out of range, neither tmsd
+ * nor bits, bits with two pools or a cut2 that is no finite number >= 0 return -1 (codlad_last_error) before any HIP
+ * call; the size helpers are host functions. */
+#define CODLAD_TORSION_MAX_T 2048
+#define CODLAD_TORSION_X_OPS 11
+#define CODLAD_TORSION_Y_OPS 13
+#define CODLAD_TORSION_FEATURE_BOUND(r) (((r) + 2.0) * 2.220446049250313e-16)
+#define CODLAD_TORSION_CHUNK_MAX(N) ((N) < 16384 ? ((N) < 528 ? (N) : 528) : (N) / 32 + 16)
+#define CODLAD_TORSION_MEAN_BOUND(N) ((CODLAD_TORSION_CHUNK_MAX(N) + CODLAD_TORSION_CHUNK_MAX(N) / 64 + 72.0) * 2.220446049250313e-16)
+#define CODLAD_TORSION_MATRIX_BOUND(T) ((2.0 * (T) + 3.0) * 2.220446049250313e-16)
+#define CODLAD_TORSION_TERM_BOUND (4.0 * 2.220446049250313e-16)
+#define CODLAD_TORSION_PAIRS_BOUND(T) ((((T) + 63) / 64 + 11.0) * 2.220446049250313e-16)
+int codlad_torsion_features(const float *x, int N, int n_atoms, const int32_t *quads, int T, double *F, uint8_t *finite,
+                            void *stream);
+long long codlad_torsion_mean_scratch_bytes(int N, int T);
+int codlad_torsion_mean(const double *F, const uint8_t *finite, const double *w, int N, int T, double *mean, double *scal,
+                        double *D, void *scratch, void *stream);
+long long codlad_torsion_matrix_scratch_bytes(int Na, int Nb);
+int codlad_torsion_matrix(const double *Fx, const uint8_t *finite_x, int Na, const double *Fy, const uint8_t *finite_y, int Nb,
+                          int T, double cut2, int squared, double *tmsd, uint64_t *bits, void *scratch, void *stream);
+int codlad_torsion_pairs(const double *Fa, int na, const double *Fb, int nb, int T, const int32_t *pairs, int K, double *tmsd,
+                         double *terms, void *stream);
+long long codlad_feature_covariance_scratch_bytes(int N, int d);
+int codlad_feature_covariance(const double *D, const double *w, const uint8_t *finite, int N, int d, const double *scal,
+                              double *cov, double *total, void *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
